@@ -18,6 +18,11 @@ C5 (BASELINE configs[4]): python bench.py --gpus 8 --scene dino --width 4096 --h
 (the scene is uploaded by rt_multi_create, before any step; the warm-up render allocates the pass workspace, so the one
 timed step is the render alone -- the reference times engine::run only, main.cpp:44-46)
 
+A plain run sets up, warms up, times the K steps and prints the result line; --dump-outputs DIR also writes what the
+last timed step returned (dump_outputs below: DIR/frame.npy, DIR/stats.npy).  `cpu_baseline` and `parity` below take
+runs of their own on the host CPUs after the timed steps and are measured only with --full (--no-cpu-baseline and
+--no-parity then drop one of the two); `roofline` comes from the timed steps themselves and is in every line.
+
 Extra fields:
   roofline      the dominant kernel (k_paths / k_paths_g) on the slowest GPU, each launch timed live with HIP events on
                 its render stream during the timed steps.  bound "hbm": achieved = SURVEY.md §8(d) algorithmic bytes per
@@ -27,12 +32,12 @@ Extra fields:
                 else null.  The kernels' actual limiter, VALU issue and lane divergence, is under `valu`
                 from the same build-matched summary: VALU lane-slots issued per second vs 78.6 T/s, lane_util,
                 useful_frac.
-  cpu_baseline  the reference itself (oracle/_ref/ref_harness = /root/reference/src compiled unmodified), its own
+  cpu_baseline  (--full) the reference itself (oracle/_ref/ref_harness = its sources compiled unmodified), its own
                 CPU-parallel mode (engine.h:335-376: 4 row stripes, 4 threads, shared global RNG) on a bounded sample
                 of the same workload (same scene, full 1920x1080, reduced spp), median and spread of 5 runs, N = 1 only;
                 plus `all_cores`: the oracle's restatement on every host thread the job may use (median of 5).
-  parity        the timed frame itself checked per pixel, after the timed steps: a bounded set of full-spp rows of the
-                last timed step's RGB8 against the oracle's CPU restatement driven by the same PCG streams (rmse_lsb,
+  parity        (--full) the timed frame itself checked per pixel, after the timed steps: a bounded set of full-spp rows of
+                the last timed step's RGB8 against the oracle's CPU restatement driven by the same PCG streams (rmse_lsb,
                 max_dlsb, within_1lsb, bit_exact; SURVEY.md §8(d) tolerance: RMSE <= 1.0 LSB).
   config.phases where the step time goes: rt_multi_times (renders slowest/fastest device, ncclGather, unpack) with the
                 one-process driver; per-rank render and step times under torchrun.
@@ -99,8 +104,12 @@ def parse():
     ap.add_argument("--split-shade", action="store_true", help="keep per-material k_shade launches (A/B vs fused shading)")
     ap.add_argument("--wavefront", action="store_true", help="one fused extend launch per depth (A/B vs persistent paths)")
     ap.add_argument("--cpu-baseline-spp", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle check of the timed frame's rows")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the CPU baselines and the oracle parity check of the timed frame")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the oracle check of the timed frame's rows")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (frame, stats) as DIR/<name>.npy")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="rt_option_set before the scene is built (builder experiments, e.g. bvh.sah_ci=1.0; repeatable)")
     return ap.parse_args()
@@ -193,6 +202,27 @@ def frame_parity(args, frame, budget_segments=2.5e8):
             "max_dlsb": int(np.abs(d).max()), "within_1lsb": float(np.mean(np.all(np.abs(d) <= 1, axis=-1))),
             "bit_exact": bool(np.array_equal(got, o["rgb"])), "tolerance": "RMSE <= 1.0 LSB and >= 99.5 % of pixels within 1 LSB (SURVEY 8(d) 2)",
             "oracle": f"oracle/restate.cpp pcg mode, orc_render_rows over {nt} threads ({o['segments']} segments, {time.perf_counter() - t0:.1f} s)"}
+
+
+DUMP_SAMPLE_PIXELS = 4_000_000  # x 3 channels x 4 bytes = 48 MB: the most of one frame that --dump-outputs writes
+
+
+def dump_outputs(path, frame, stats):
+    """--dump-outputs: what a caller of the timed path holds after the last timed step, as float arrays under `path`:
+      frame.npy  float32 [H, W, 3], the RGB8 frame on GPU 0 (exact in float32).  A frame of more than DUMP_SAMPLE_PIXELS
+                 pixels is written as [DUMP_SAMPLE_PIXELS, 3]: the pixels (row-major index, ascending) drawn without
+                 replacement by numpy's default_rng(0), the same for every run of the same frame size;
+      stats.npy  float64 [segments, primary]: the step's exact device counts of traced segments and primary rays.
+    The scene, camera and RNG streams (seed 0, keyed by pixel and sample) are fixed by the arguments, so two builds run
+    with the same arguments can be compared array for array."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    rgb = np.ascontiguousarray(frame).reshape(-1, frame.shape[-2], 3)
+    if rgb.shape[0] * rgb.shape[1] > DUMP_SAMPLE_PIXELS:
+        pick = np.sort(np.random.default_rng(0).choice(rgb.shape[0] * rgb.shape[1], DUMP_SAMPLE_PIXELS, replace=False))
+        rgb = rgb.reshape(-1, 3)[pick]
+    np.save(os.path.join(path, "frame.npy"), rgb.astype(np.float32))
+    np.save(os.path.join(path, "stats.npy"), np.array([stats["segments"], stats["primary"]], dtype=np.float64))
 
 
 def latest_pmc(precision, scene, variant, build):
@@ -441,11 +471,16 @@ def main():
             line["config"]["phases"] = phase
         if profile and acc and any(a["extend_ms"] > 0 for a in acc):
             line["roofline"] = roofline_of(acc, args.width, scene_bytes, variant, args.precision, args.scene, build)
-        if n == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(args)
-        if not args.no_parity:
+        f = None
+        if args.dump_outputs or (args.full and not args.no_parity):
             f = last_frame()
-            line["parity"] = frame_parity(args, f.cpu().numpy() if hasattr(f, "cpu") else f)
+            f = f.cpu().numpy() if hasattr(f, "cpu") else f
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, f, st)
+        if args.full and n == 1 and not args.no_cpu_baseline:
+            line["cpu_baseline"] = cpu_baseline(args)
+        if args.full and not args.no_parity:
+            line["parity"] = frame_parity(args, f)
         print(json.dumps(line), flush=True)
     if driver == "procs":
         dist.destroy_process_group()

@@ -25,6 +25,8 @@ fixtures pin:
                        RGB8 and segment count (`python tests/golden/make_golden.py adaptive` makes only these)
   * render_images_<scene>.npz  engine_mode::parallel_images renders (engine.h:378-445, its 4 partial images traced
                        in order): RGB8, the pixel_acc sums and the segment count (`make_golden.py images_mode`)
+  * render_other_<scene>_37x23x3.npz  engine_mode::single renders of four scenes at a second, odd frame size: RGB8 and
+                       the segment count (`make_golden.py other_size`)
 Assets written by the same harness: assets/*.tris (the reference's post-triangulation triangle lists: cow,
 dino, capsule incl. its texture coordinates; the oracle's mesh input and the pin of the product's OBJ loader),
 assets/earthmap.rgb and assets/models/capsule/capsule.rgb.gz (stb_image-decoded texels, the latter gzipped).
@@ -70,6 +72,21 @@ def adaptive_fixtures():
         np.savez_compressed(os.path.join(HERE, f"render_adaptive_{sc}_{W}x{H}x{spp}.npz"), rgb=rgb,
                             segments=np.int64(info["segments"]), W=W, H=H, spp=spp)
         print("adaptive", sc, info)
+
+
+# a second, odd frame size (engine_mode::single) of four scenes: what tests/test_oracle.py's
+# test_live_reference_other_size compares the restatement with wherever the harness itself is not built
+OTHER_SIZE_SCENES = ["c1", "1", "7", "8"]
+OTHER_SIZE = (37, 23, 3)
+
+
+def other_size_fixtures():
+    W, H, spp = OTHER_SIZE
+    for sc in OTHER_SIZE_SCENES:
+        rgb, _, info = render(sc, W, H, spp)
+        np.savez_compressed(os.path.join(HERE, f"render_other_{sc}_{W}x{H}x{spp}.npz"), rgb=rgb,
+                            segments=np.int64(info["segments"]), W=W, H=H, spp=spp)
+        print("other size", sc, info)
 
 
 # engine_mode::parallel_images (engine.h:378-445; the four partial images traced in order): spp not a multiple of 4,
@@ -207,6 +224,9 @@ def main():
     if sys.argv[1:] == ["images_mode"]:
         images_mode_fixtures()
         return
+    if sys.argv[1:] == ["other_size"]:
+        other_size_fixtures()
+        return
     if sys.argv[1:2] == ["scene"]:
         path = os.path.join(HERE, "scenes.json")
         scenes = json.load(open(path))
@@ -234,6 +254,7 @@ def main():
     stat_fixtures()
     image_fixtures()
     images_mode_fixtures()
+    other_size_fixtures()
 
 
 if __name__ == "__main__":

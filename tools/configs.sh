@@ -10,7 +10,8 @@ mkdir -p gpurun_out
 out=gpurun_out/configs_$TAG.jsonl
 : > $out
 for cfg in "--scene 1 --spp 1024" "--scene cow --spp 512" "--scene 8 --spp 4096" "--scene dino --width 4096 --height 4096 --spp 512" "--scene 9 --spp 512"; do
-  timeout -k 10 300 python bench.py --steps 1 --warmup 1 --no-cpu-baseline $cfg > gpurun_out/cfg.log 2>&1
+  # --full: every config's line carries the parity rows of its timed frame
+  timeout -k 10 300 python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline $cfg > ${out%/*}/cfg.log 2>&1
   rc=$?; echo "rc=$rc $cfg"
   [ $rc -eq 0 ] || { tail -5 gpurun_out/cfg.log; exit $rc; }
   tail -1 gpurun_out/cfg.log >> $out

@@ -22,6 +22,7 @@ if [ -z "$SKIP_PMC" ]; then
   # the summary lands in profiles/ here (so the bench below prices `traffic` with it) and in gpurun_out/ (to commit)
   python tools/pmc_summary.py $TAG 1 f64 $SEGS $VAR > gpurun_out/pmc_summary_$TAG.txt && cp profiles/${TAG}_pmc_scene1_f64.json gpurun_out/ || exit 1
 fi
+BENCH_ARGS="--full $BENCH_ARGS"  # the official line carries cpu_baseline and the parity rows
 run 600 python bench.py $BENCH_ARGS > gpurun_out/bench_$TAG.log 2>&1
 tail -1 gpurun_out/bench_$TAG.log
 run 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_$TAG -o run -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline $BENCH_ARGS > gpurun_out/rocprof_$TAG.log 2>&1

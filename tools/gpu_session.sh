@@ -11,11 +11,14 @@
 #   pmc:TAG:SCENE[:SPP[:OPTS]]  tools/pmc.sh counter passes + kernel trace of the current libart (ART_LIB honoured);
 #                               OPTS: library options NAME=V,NAME=V (bench.py --option)
 #   bench:TAG[:ARGS]            bench.py line -> gpurun_out/bench_TAG.log
+#                               (always with --full: cpu_baseline and the parity rows are part of that line)
 #   prof:TAG[:ARGS]             rocprofv3 --kernel-trace --stats of a bench run -> gpurun_out/prof_TAG
 #   configs:TAG                 tools/configs.sh (one bench line per BASELINE GPU config, plus the capsule)
 #   defaultrun:TAG[:CPURUNS]    tools/default_run.py: the reference's default run (capsule, adaptive, 720x540x100) on the GPU and
 #                               the reference itself on the host CPU (CPURUNS pinned 4-thread runs, default 9)
 #   c5full:TAG                  C5 as configured on one GPU: dino 4096^2 x 8192 spp, one timed step after a warm-up
+#                               (a plain run; for its parity rows: bench:TAG:"--scene dino --width 4096 --height 4096
+#                               --spp 8192 --steps 1 --warmup 1 --no-cpu-baseline")
 #   stats:TAG                   tools/stats_configs.sh over the four GPU configs (libart_stats.so: divergence counters
 #                               and the per-phase cycle split) -> gpurun_out/stats_TAG.txt
 # Usage (GPU box): bash tools/gpu_session.sh tests ab:libart_x.so,libart.so pmc:r2b:1
@@ -62,6 +65,7 @@ for step in "$@"; do
       python tools/pmc_summary.py $a $b f64 $SEGS $VAR > gpurun_out/pmc_summary_$a.txt || exit 1
       cp profiles/${a}_pmc_scene${b}_f64.json gpurun_out/ && cat gpurun_out/pmc_summary_$a.txt ;;
     bench)
+      b="--full $b"
       run 600 python bench.py $b > gpurun_out/bench_$a.log 2>&1
       tail -1 gpurun_out/bench_$a.log ;;
     prof)
