@@ -21,6 +21,8 @@ RT_OK = 0
 RT_FP64 = 0  # the only fp_mode since ABI 2 (include/art.h)
 RT_ABI_VERSION = 5
 RT_OUT_DEVICE, RT_PROFILE, RT_GLOBAL_SCENE, RT_SPLIT_SHADE, RT_ADAPTIVE, RT_WAVEFRONT, RT_PARALLEL_IMAGES = 1, 2, 4, 8, 16, 32, 64
+RT_GUIDE_DOUBLES = 10  # rt_render_guides: albedo[3], normal[3], position[3], t per pixel
+RT_DN_NO_DEMODULATE = 256
 ERRORS = {-1: "RT_E_INVALID", -2: "RT_E_SCENE", -3: "RT_E_DEVICE", -4: "RT_E_INTERNAL"}
 
 
@@ -59,6 +61,12 @@ class rt_scene_info(ctypes.Structure):
                 ("max_bvh_depth", ctypes.c_int32), ("device_bytes_f64", ctypes.c_uint64)]
 
 
+class rt_denoise_params(ctypes.Structure):  # zero-initialised = defaults
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("iterations", ctypes.c_int32),
+                ("normal_squarings", ctypes.c_int32), ("sigma_color", ctypes.c_double), ("sigma_plane", ctypes.c_double),
+                ("albedo_floor", ctypes.c_double), ("flags", ctypes.c_int32), ("stream", ctypes.c_void_p)]
+
+
 class rt_multi_times(ctypes.Structure):
     _fields_ = [("total_ms", ctypes.c_double), ("render_ms_max", ctypes.c_double), ("render_ms_min", ctypes.c_double),
                 ("gather_ms", ctypes.c_double), ("unpack_ms", ctypes.c_double), ("wait_ms", ctypes.c_double),
@@ -91,6 +99,10 @@ SIGNATURES = {
     "rt_render_progressive": (_I, [_P, ctypes.POINTER(rt_camera), ctypes.POINTER(rt_params), _P, _P, rt_progress_fn, _P,
                                    ctypes.POINTER(rt_stats)]),
     "rt_trace_rays": (_I, [_P, _P, ctypes.c_int64, ctypes.c_int32, _P, _P]),
+    "rt_render_guides": (_I, [_P, ctypes.POINTER(rt_camera), ctypes.POINTER(rt_params), _P, _P]),
+    "rt_denoise": (_I, [_I, ctypes.POINTER(rt_denoise_params), _P, _P, ctypes.c_int32, _P, _P, _P, _DP]),
+    "rt_render_denoised": (_I, [_P, ctypes.POINTER(rt_camera), ctypes.POINTER(rt_params), ctypes.POINTER(rt_denoise_params), _P, _P,
+                                ctypes.POINTER(rt_stats)]),
     "rt_image_load": (_I, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                            ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8))]),
     "rt_image_free": (None, [ctypes.POINTER(ctypes.c_uint8)]),

@@ -1,4 +1,6 @@
 // abi.cpp — the extern "C" boundary (include/art.h).  No exception crosses it.
+#include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
@@ -9,6 +11,7 @@
 #include <vector>
 
 #include "art.h"
+#include "denoise.h"
 #include "imagedec.h"
 #include "multi.h"
 #include "renderer.h"
@@ -325,6 +328,104 @@ int rt_trace_rays(rt_scene* s, const double* rays, int64_t n, int32_t flags, dou
         if (!s->renderer) s->renderer = std::make_unique<art::Renderer>(s->flat, s->device);
         std::vector<double> nrm(normal_out ? 0 : 3 * static_cast<size_t>(n));
         s->renderer->trace_rays(rays, static_cast<size_t>(n), (flags & RT_GLOBAL_SCENE) != 0, t_out, normal_out ? normal_out : nrm.data());
+        return RT_OK;
+    });
+}
+
+int rt_render_guides(rt_scene* s, const rt_camera* cam, const rt_params* p, double* guides, double* rays_out) {
+    std::string why;
+    if (!s || !cam || !guides) return fail(RT_E_INVALID, "scene, camera and guides must be non-NULL");
+    if (!p) return fail(RT_E_INVALID, "params is NULL");
+    rt_params q = *p;  // spp, seed, max_depth and samples_per_pass are ignored
+    q.spp = 1;
+    q.max_depth = 0;
+    if (!valid_params(&q, why)) return fail(RT_E_INVALID, why);
+    if (p->flags & ~(RT_OUT_DEVICE | RT_GLOBAL_SCENE)) return fail(RT_E_INVALID, "rt_render_guides takes RT_OUT_DEVICE and RT_GLOBAL_SCENE only");
+    return guard(RT_E_DEVICE, [&] {
+        if (!s->renderer) s->renderer = std::make_unique<art::Renderer>(s->flat, s->device);
+        s->renderer->render_guides(camera_of(cam), render_params(&q), guides, rays_out);
+        return RT_OK;
+    });
+}
+
+namespace {
+// rt_denoise_params -> DenoiseParams with the defaults filled in; false (why) for a value outside its range
+bool denoise_params(const rt_denoise_params* p, int width, int height, art::DenoiseParams& d, std::string& why) {
+    d.width = width;
+    d.height = height;
+    if (width < 1 || height < 1) { why = "width and height must be >= 1"; return false; }
+    if (static_cast<int64_t>(width) * height > (int64_t(1) << 31)) { why = "image too large"; return false; }
+    if (!p) return true;
+    if (p->iterations < 0 || p->iterations > 8) { why = "iterations must be 1..8 (0 = the default, 5)"; return false; }
+    if (p->normal_squarings < 0 || p->normal_squarings > 10) { why = "normal_squarings must be 1..10 (0 = the default, 6)"; return false; }
+    if (!(p->sigma_color >= 0) || !(p->sigma_plane >= 0) || !(p->albedo_floor >= 0) || std::isinf(p->sigma_color) || std::isinf(p->sigma_plane) ||
+        std::isinf(p->albedo_floor)) {
+        why = "sigma_color, sigma_plane and albedo_floor must be finite and >= 0 (0 = the default)";
+        return false;
+    }
+    if (p->flags & ~(RT_OUT_DEVICE | RT_DN_NO_DEMODULATE)) { why = "rt_denoise_params.flags takes RT_OUT_DEVICE and RT_DN_NO_DEMODULATE only"; return false; }
+    if (p->iterations) d.iterations = p->iterations;
+    if (p->normal_squarings) d.normal_squarings = p->normal_squarings;
+    if (p->sigma_color != 0) d.sigma_color = p->sigma_color;
+    if (p->sigma_plane != 0) d.sigma_plane = p->sigma_plane;
+    if (p->albedo_floor != 0) d.albedo_floor = p->albedo_floor;
+    d.demodulate = !(p->flags & RT_DN_NO_DEMODULATE);
+    d.stream = p->stream;
+    return true;
+}
+}  // namespace
+
+int rt_denoise(int device, const rt_denoise_params* p, const double* accum_a, const double* accum_b, int32_t spp_each, const double* guides,
+               double* out_color, uint8_t* out_rgb8, double* ms) {
+    if (!p || !accum_a || !accum_b || !guides || !out_color) return fail(RT_E_INVALID, "params, accum_a, accum_b, guides and out_color must be non-NULL");
+    if (spp_each < 1) return fail(RT_E_INVALID, "spp_each must be >= 1");
+    if (device < 0) return fail(RT_E_INVALID, "device must be >= 0");
+    art::DenoiseParams d;
+    std::string why;
+    if (!denoise_params(p, p->width, p->height, d, why)) return fail(RT_E_INVALID, why);
+    return guard(RT_E_DEVICE, [&] {
+        art::denoise(device, d, accum_a, accum_b, spp_each, guides, out_color, out_rgb8, (p->flags & RT_OUT_DEVICE) != 0, ms);
+        return RT_OK;
+    });
+}
+
+int rt_render_denoised(rt_scene* s, const rt_camera* cam, const rt_params* p, const rt_denoise_params* dn, uint8_t* out_rgb8, double* out_color,
+                       rt_stats* stats) {
+    std::string why;
+    if (!s || !cam || !out_rgb8) return fail(RT_E_INVALID, "scene, camera and out_rgb8 must be non-NULL");
+    if (!valid_params(p, why)) return fail(RT_E_INVALID, why);
+    if (p->band_count != 1) return fail(RT_E_INVALID, "rt_render_denoised filters a whole frame: band_count must be 1");
+    if (p->spp < 2 || p->spp % 2 != 0) return fail(RT_E_INVALID, "rt_render_denoised splits spp into two half-renders: spp must be even and >= 2");
+    if (p->flags & (RT_ADAPTIVE | RT_PARALLEL_IMAGES)) return fail(RT_E_INVALID, "rt_render_denoised renders engine_mode::single frames (no RT_ADAPTIVE or RT_PARALLEL_IMAGES)");
+    art::DenoiseParams d;
+    if (!denoise_params(dn, p->width, p->height, d, why)) return fail(RT_E_INVALID, why);
+    if (!d.stream) d.stream = p->stream;
+    return guard(RT_E_DEVICE, [&] {
+        const auto t0 = std::chrono::steady_clock::now();
+        if (!s->renderer) s->renderer = std::make_unique<art::Renderer>(s->flat, s->device);
+        const art::DenoiseFrame fb = art::denoise_reserve(s->device, p->width, p->height);
+        art::RenderParams rp = render_params(p);
+        rp.spp = p->spp / 2;
+        rp.flags |= RT_OUT_DEVICE;
+        art::RenderStats st[2];
+        for (int half = 0; half < 2; ++half) {
+            rp.seed = p->seed + static_cast<uint64_t>(half);
+            s->renderer->render(camera_of(cam), rp, nullptr, half ? fb.accum_b : fb.accum_a, st[half]);
+        }
+        art::RenderParams gp = rp;
+        gp.flags = RT_OUT_DEVICE | (p->flags & RT_GLOBAL_SCENE);
+        s->renderer->render_guides(camera_of(cam), gp, fb.guides, nullptr);
+        art::denoise_reserved(s->device, d, rp.spp, out_color, out_rgb8, (p->flags & RT_OUT_DEVICE) != 0, nullptr);
+        art::RenderStats sum = st[1];
+        sum.segments += st[0].segments;
+        sum.primary += st[0].primary;
+        sum.extend_ms += st[0].extend_ms;
+        sum.shade_ms += st[0].shade_ms;
+        sum.extend_launches += st[0].extend_launches;
+        sum.shade_launches += st[0].shade_launches;
+        sum.passes += st[0].passes;
+        sum.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        fill_stats(sum, stats);
         return RT_OK;
     });
 }

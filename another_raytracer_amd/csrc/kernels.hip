@@ -1513,6 +1513,66 @@ __global__ __launch_bounds__(L ? kBlockL : kBlock) void k_trace_rays(DevScene<do
     }
 }
 
+// First-hit guide buffers (rt_render_guides): one ray per local pixel through the pixel centre -- no render RNG draw,
+// no lens offset, time0 -- traced exactly as k_trace_rays traces it (ray index = global pixel gy * W + i, so a whole
+// frame's t and normal equal rt_trace_rays of rays_out), plus the hit point (Surf::p) and the first hit's albedo:
+// mat_tex_value for lambertian / isotropic, MatRec::albedo for metal, 1 for dielectric, diffuse_light and a miss.
+// Record per local pixel (RT_GUIDE_DOUBLES = 10): albedo[3], normal[3], position[3], t; a miss has t = position = +inf.
+struct GuideGeom {
+    int32_t W, H, rows;
+    int32_t band_rows, band_count, band_index;
+};
+template <uint32_t F, bool L, uint32_t TF>
+__global__ __launch_bounds__(L ? kBlockL : kBlock) void k_guides(DevScene<double> S, GuideGeom g, CameraRec<double> cam, double* guides, double* rays_out) {
+    using R = double;
+    constexpr int B = L ? kBlockL : kBlock;
+    extern __shared__ __align__(16) uint8_t smem[];
+    StackT<L>* stk = reinterpret_cast<StackT<L>*>(smem + (L ? kLdsImageBytes : 0u)) + B + stack_column<L>(threadIdx.x);
+    stk[-B] = static_cast<StackT<L>>(kNodeEmpty);
+    if constexpr (L) {
+        load_lds_image<B>(S.lds_image, smem);
+        __syncthreads();
+    }
+    const uint32_t lp = blockIdx.x * B + threadIdx.x;
+    if (lp >= static_cast<uint32_t>(g.rows) * static_cast<uint32_t>(g.W)) return;
+    const int ly = static_cast<int>(lp / static_cast<uint32_t>(g.W));
+    const int lx = static_cast<int>(lp - static_cast<uint32_t>(ly) * static_cast<uint32_t>(g.W));
+    const int gy = band_global_row(ly, g.band_rows, g.band_count, g.band_index);
+    const R s = (R(lx) + R(0.5)) / R(g.W - 1);
+    const R t_img = (R(g.H - 1 - gy) + R(0.5)) / R(g.H - 1);
+    Ray<R> r;
+    r.o = ld3(cam.origin);
+    r.d = ld3(cam.llc) + s * ld3(cam.horizontal) + t_img * ld3(cam.vertical) - ld3(cam.origin);
+    r.tm = cam.time0;
+    if (rays_out) {
+        double* q = rays_out + 7 * static_cast<size_t>(lp);
+        q[0] = r.o.x; q[1] = r.o.y; q[2] = r.o.z;
+        q[3] = r.d.x; q[4] = r.d.y; q[5] = r.d.z;
+        q[6] = r.tm;
+    }
+    uint64_t rng = pcg_seed(0, static_cast<uint32_t>(gy) * static_cast<uint32_t>(g.W) + static_cast<uint32_t>(lx), 0);
+    R t = R(0);
+    HitOut h{0, 0, kMatUnknown};
+    const R inf = __builtin_inf();
+    V3<R> alb = mk(R(1), R(1), R(1)), nrm = mk(R(0), R(0), R(0)), pos = mk(inf, inf, inf);
+    R t_hit = inf;
+    if (trace_world<R, F, B, L>(S, L ? smem : nullptr, r, stk, rng, t, h)) {
+        Surf<R> sf;
+        world_surface<R, F, (TF & TF_IMAGE) != 0, (TF & (TF_IMAGE | TF_BARY)) != 0>(S, h, r, t, sf, uv_table(S));
+        const MatRec<R>& m = S.mats[sf.mat];
+        if (m.type == MAT_LAMBERTIAN || m.type == MAT_ISOTROPIC) alb = mat_tex_value<R, TF>(S, m, sf.u, sf.v, sf.p);
+        else if (m.type == MAT_METAL) alb = ld3(m.albedo);
+        nrm = sf.n;
+        pos = sf.p;
+        t_hit = t;
+    }
+    double* o = guides + 10 * static_cast<size_t>(lp);
+    o[0] = alb.x; o[1] = alb.y; o[2] = alb.z;
+    o[3] = nrm.x; o[4] = nrm.y; o[5] = nrm.z;
+    o[6] = pos.x; o[7] = pos.y; o[8] = pos.z;
+    o[9] = t_hit;
+}
+
 __global__ void k_finalize(const double* acc, uint8_t* rgb, uint32_t n, int spp) {  // color.h:6-22
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -2208,6 +2268,7 @@ Renderer::~Renderer() {
     }
 }
 size_t Renderer::scene_bytes() const { return impl_->s64.bytes; }
+int Renderer::device() const { return impl_->device; }
 const FlatScene& Renderer::flat() const { return impl_->flat; }
 
 #endif
@@ -2859,6 +2920,57 @@ void Renderer::trace_rays(const double* rays, size_t n, bool global_scene, doubl
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpyAsync(t_out, d_t, t_b, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(n_out, d_n, n_b, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+}
+
+template <uint32_t F, bool L>
+static void launch_guides(const DeviceScene<double>& ds, hipStream_t st, const GuideGeom& g, const CameraRec<double>& cam, double* guides, double* rays) {
+    const uint32_t stack = stack_rows(ds.max_stack), npix = static_cast<uint32_t>(g.rows) * static_cast<uint32_t>(g.W);
+    constexpr int B = L ? kBlockL : kBlock;
+    const size_t lds = L ? kLdsImageBytes + paths_stack_bytes(stack) : sizeof(int32_t) * stack * kBlock;
+    const dim3 grid((npix + B - 1) / B);
+    auto go = [&](auto kernel) {
+        if constexpr (L) {
+            static const bool checked = static_lds_is_zero(reinterpret_cast<const void*>(kernel));
+            (void)checked;
+            (void)blocks_per_cu(reinterpret_cast<const void*>(kernel), B, lds);  // the > 64 KiB dynamic-LDS attribute
+        }
+        hipLaunchKernelGGL(kernel, grid, dim3(B), lds, st, ds.view, g, cam, guides, rays);
+    };
+    // the texture kinds the scene needs: solid + checker, those plus barycentric images on triangles, or all
+    if (ds.tex_basic) return go(k_guides<F, L, kTexBasic>);
+    if constexpr ((F & F_TRI) != 0)
+        if (ds.tex_bary) return go(k_guides<F, L, kTexBary>);
+    go(k_guides<F, L, TF_ALL>);
+}
+
+void Renderer::render_guides(const CameraRec<double>& cam, const RenderParams& p, double* guides, double* rays_out) {
+    upload();
+    Impl& I = *impl_;
+    const DeviceScene<double>& ds = I.s64;
+    hipStream_t st = p.stream ? static_cast<hipStream_t>(p.stream) : I.own_stream;
+    GuideGeom g{p.width, p.height, band_local_rows(p.height, p.band_rows, p.band_count, p.band_index), p.band_rows, p.band_count, p.band_index};
+    if (g.rows == 0) return;
+    const size_t npix = static_cast<size_t>(g.rows) * p.width;
+    const size_t g_b = sizeof(double) * 10 * npix, r_b = sizeof(double) * 7 * npix;
+    const bool dev_out = (p.flags & RT_OUT_DEVICE) != 0;
+    double* d_g = guides;
+    double* d_r = rays_out;
+    if (!dev_out) {  // host buffers: the kernel writes the workspace, copied out below
+        char* base = static_cast<char*>(I.workspace(g_b + (rays_out ? r_b : 0)));
+        d_g = reinterpret_cast<double*>(base);
+        d_r = rays_out ? reinterpret_cast<double*>(base + g_b) : nullptr;
+    }
+    const uint32_t feat = ds.features;
+    if (ds.lds_scene && !(p.flags & RT_GLOBAL_SCENE) && (feat & ~kFeatSpheres) == 0) launch_guides<kFeatSpheres, true>(ds, st, g, cam, d_g, d_r);
+    else if ((feat & ~kFeatSpheres) == 0) launch_guides<kFeatSpheres, false>(ds, st, g, cam, d_g, d_r);
+    else if ((feat & ~kFeatMesh) == 0) launch_guides<kFeatMesh, false>(ds, st, g, cam, d_g, d_r);
+    else launch_guides<F_ALL, false>(ds, st, g, cam, d_g, d_r);
+    HIP_OK(hipGetLastError());
+    if (!dev_out) {
+        HIP_OK(hipMemcpyAsync(guides, d_g, g_b, hipMemcpyDeviceToHost, st));
+        if (rays_out) HIP_OK(hipMemcpyAsync(rays_out, d_r, r_b, hipMemcpyDeviceToHost, st));
+    }
     HIP_OK(hipStreamSynchronize(st));
 }
 

@@ -26,6 +26,8 @@ enum class Opt : int {
     LdsNodesMax,   // render.lds_nodes_max: cap on the LDS-resident nodes of a partial-LDS (LM 2) kernel (diagnostic)
     Leaf2,         // render.leaf2: 1 (default) pair-aligned leaves where 16-bit codes need them (F_LEAF2), 0 off
     TexBary,       // render.tex_bary: 1 (default) the TF_BARY kernels for meshes whose only images are barycentric, 0 off
+    DenoiseLdsIterations,  // denoise.lds_iterations: how many of rt_denoise's first iterations (tap spacings 1, 2) run the
+                           // LDS-tile kernel instead of the direct-load one (0..2; same result either way, A/B)
     // multi-GPU
     MultiTimeoutMs,  // multi.timeout_ms: deadline of RCCL init / gather waits (unset: ART_MULTI_TIMEOUT_MS, else 120000;
                      // inf, or anything beyond ~292 years, means no deadline)

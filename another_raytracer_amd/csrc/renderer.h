@@ -47,6 +47,10 @@ public:
     // Closest hit of n rays (rays: n x {ox, oy, oz, dx, dy, dz, tm}) through the renderer's traversal: t (inf on a
     // miss) and the face normal (n x 3), host buffers; global_scene forces the HBM traversal on an LDS-image scene.
     void trace_rays(const double* rays, size_t n, bool global_scene, double* t_out, double* n_out);
+    // First-hit guide buffers of the local rows (k_guides): 10 doubles per pixel {albedo, normal, position, t} and,
+    // when rays_out is non-NULL, the 7 doubles of every pixel-centre ray; host buffers, or device ones with RT_OUT_DEVICE.
+    void render_guides(const CameraRec<double>& cam, const RenderParams& p, double* guides, double* rays_out);
+    int device() const;
     size_t scene_bytes() const;
     const FlatScene& flat() const;
 

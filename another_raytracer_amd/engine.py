@@ -10,7 +10,7 @@ import enum
 
 import numpy as np
 
-from ._lib import RT_ADAPTIVE, RT_FP64, RT_PARALLEL_IMAGES, rt_progress_fn, RT_GLOBAL_SCENE, RT_OUT_DEVICE, RT_PROFILE, RT_SPLIT_SHADE, RT_WAVEFRONT, check, dvec, lib, rt_camera, rt_params, rt_stats
+from ._lib import RT_ADAPTIVE, RT_DN_NO_DEMODULATE, RT_FP64, RT_GUIDE_DOUBLES, rt_denoise_params, RT_PARALLEL_IMAGES, rt_progress_fn, RT_GLOBAL_SCENE, RT_OUT_DEVICE, RT_PROFILE, RT_SPLIT_SHADE, RT_WAVEFRONT, check, dvec, lib, rt_camera, rt_params, rt_stats
 from .scene import compile_world
 
 
@@ -47,6 +47,71 @@ def _pointer(out, nbytes):
             raise ValueError(f"output tensor must be contiguous with >= {nbytes} bytes")
         return out.data_ptr(), out.device.type != "cpu"
     raise TypeError("output must be a numpy array or a torch tensor")
+
+
+def _f64_pointer(buf, count, what):
+    """(address, is_device) of a float64 buffer of >= count elements: numpy array or torch tensor."""
+    if isinstance(buf, np.ndarray):
+        if not buf.flags.c_contiguous or buf.dtype != np.float64 or buf.size < count:
+            raise ValueError(f"{what} must be a C-contiguous float64 array of >= {count} elements")
+        return buf.ctypes.data, False
+    if hasattr(buf, "data_ptr"):
+        if not buf.is_contiguous() or buf.element_size() != 8 or buf.numel() < count:
+            raise ValueError(f"{what} must be a contiguous float64 tensor of >= {count} elements")
+        return buf.data_ptr(), buf.device.type != "cpu"
+    raise TypeError(f"{what} must be a numpy array or a torch tensor")
+
+
+def _denoise_params(width, height, iterations=0, normal_squarings=0, sigma_color=0.0, sigma_plane=0.0, albedo_floor=0.0,
+                    demodulate=True, stream=None):
+    """rt_denoise_params; 0 keeps a field's default (include/art.h: 5 iterations, 6 squarings, sigma_color 1,
+    sigma_plane 0.1, albedo_floor 0.5)."""
+    d = rt_denoise_params()
+    d.width, d.height = int(width), int(height)
+    d.iterations, d.normal_squarings = int(iterations), int(normal_squarings)
+    d.sigma_color, d.sigma_plane, d.albedo_floor = float(sigma_color), float(sigma_plane), float(albedo_floor)
+    d.flags = 0 if demodulate else RT_DN_NO_DEMODULATE
+    d.stream = stream
+    return d
+
+
+def denoise(accum_a, accum_b, spp_each, guides, out_color=None, out_rgb8=None, device=0, **denoise_options):
+    """rt_denoise: the variance-guided a-trous filter over two half-renders (H x W x 3 float64 radiance sums of
+    spp_each samples each, rendered with different seeds) and the frame's guides (engine.render_guides, H x W x 10).
+    Returns (out_color, ms): the filtered per-sample radiance (H x W x 3 float64; allocated next to accum_a unless
+    given) and the device time of the filter.  out_rgb8 (optional, uint8 H x W x 3) receives write_color of it.  All
+    buffers live on the host (numpy) or all on `device` (torch).  denoise_options: iterations, normal_squarings,
+    sigma_color, sigma_plane, albedo_floor, demodulate, stream."""
+    if accum_a.ndim != 3 or accum_a.shape[2] != 3:
+        raise ValueError("accum_a must have shape (H, W, 3)")
+    h, w = int(accum_a.shape[0]), int(accum_a.shape[1])
+    n = h * w
+    if out_color is None:
+        if isinstance(accum_a, np.ndarray):
+            out_color = np.empty((h, w, 3), np.float64)
+        else:
+            import torch
+            out_color = torch.empty((h, w, 3), dtype=torch.float64, device=accum_a.device)
+    pa, dev = _f64_pointer(accum_a, 3 * n, "accum_a")
+    ptrs = [pa]
+    for buf, count, what in ((accum_b, 3 * n, "accum_b"), (guides, RT_GUIDE_DOUBLES * n, "guides"), (out_color, 3 * n, "out_color")):
+        ptr, d = _f64_pointer(buf, count, what)
+        if d != dev:
+            raise ValueError("accum_a, accum_b, guides and out_color must all live on the host or all on the device")
+        ptrs.append(ptr)
+    rgb_ptr = None
+    if out_rgb8 is not None:
+        rgb_ptr, d = _pointer(out_rgb8, 3 * n)
+        if d != dev:
+            raise ValueError("out_rgb8 must live where the other buffers do")
+    p = _denoise_params(w, h, **denoise_options)
+    if dev:
+        p.flags |= RT_OUT_DEVICE
+    ms = ctypes.c_double()
+    check(lib.rt_denoise(int(device), ctypes.byref(p), ctypes.c_void_p(ptrs[0]), ctypes.c_void_p(ptrs[1]), int(spp_each),
+                         ctypes.c_void_p(ptrs[2]), ctypes.c_void_p(ptrs[3]), ctypes.c_void_p(rgb_ptr) if rgb_ptr else None,
+                         ctypes.byref(ms)), "denoise")
+    return out_color, ms.value
 
 
 class engine:
@@ -134,6 +199,60 @@ class engine:
         st = rt_stats()
         check(lib.rt_render(self._scene, ctypes.byref(self.cam.c), ctypes.byref(p), ctypes.c_void_p(ptr),
                             ctypes.c_void_p(acc_ptr) if acc_ptr else None, ctypes.byref(st)), "engine.run")
+        self.stats = st.as_dict()
+        return int(round(st.ms))
+
+    def render_guides(self, guides=None, rays=None, band_rows=None, band_count=1, band_index=0, stream=None):
+        """First-hit guide buffers (rt_render_guides): float64 (local_rows, W, 10) = albedo, normal, position, t of the
+        pixel-centre ray of every local pixel (a miss: t = position = inf, normal 0, albedo 1).  `guides` / `rays`
+        (optional, (local_rows, W, 7): the rays themselves, as rt_trace_rays takes them) may be numpy arrays or
+        device tensors; returns the guides array."""
+        if self._scene is None:
+            raise ValueError("no scene set")
+        p = self.params(band_rows, band_count, band_index, RT_GLOBAL_SCENE if self.global_scene else 0, stream)
+        rows = check(lib.rt_local_rows(ctypes.byref(p), None), "rt_local_rows")
+        n = rows * self.width
+        if guides is None:
+            guides = np.empty((rows, self.width, RT_GUIDE_DOUBLES), np.float64)
+        ptr, dev = _f64_pointer(guides, RT_GUIDE_DOUBLES * n, "guides")
+        rays_ptr = None
+        if rays is not None:
+            rays_ptr, rays_dev = _f64_pointer(rays, 7 * n, "rays")
+            if rays_dev != dev:
+                raise ValueError("guides and rays must both live on the host or both on the device")
+        if dev:
+            p.flags |= RT_OUT_DEVICE
+        check(lib.rt_render_guides(self._scene, ctypes.byref(self.cam.c), ctypes.byref(p), ctypes.c_void_p(ptr),
+                                   ctypes.c_void_p(rays_ptr) if rays_ptr else None), "engine.render_guides")
+        return guides
+
+    def run_denoised(self, output_image, color=None, **denoise_options):
+        """One-call denoised render (rt_render_denoised): two half-renders of samples_per_pixel / 2 samples (seeds
+        `seed` and `seed + 1`), the guide pass and the a-trous filter, all on the device; output_image (uint8 H x W x
+        3) receives write_color of the filtered frame and `color` (optional float64 H x W x 3) the frame itself.
+        samples_per_pixel must be even.  denoise_options as for denoise().  Returns elapsed ms (the whole call), or -1
+        on an empty world."""
+        if self._scene is None:
+            print("Invalid input scene!")
+            return -1
+        if self.m in (engine_mode.adaptive, engine_mode.parallel_images):
+            raise ValueError("run_denoised renders whole frames of independent samples (engine_mode.adaptive / parallel_images do not)")
+        flags = ((RT_GLOBAL_SCENE if self.global_scene else 0) | (RT_SPLIT_SHADE if self.split_shade else 0)
+                 | (RT_WAVEFRONT if self.wavefront else 0))
+        p = self.params(None, 1, 0, flags, denoise_options.pop("stream", None))
+        n = self.height * self.width
+        ptr, dev = _pointer(output_image, 3 * n)
+        color_ptr = None
+        if color is not None:
+            color_ptr, color_dev = _f64_pointer(color, 3 * n, "color")
+            if color_dev != dev:
+                raise ValueError("output_image and color must both live on the host or both on the device")
+        if dev:
+            p.flags |= RT_OUT_DEVICE
+        d = _denoise_params(self.width, self.height, **denoise_options)
+        st = rt_stats()
+        check(lib.rt_render_denoised(self._scene, ctypes.byref(self.cam.c), ctypes.byref(p), ctypes.byref(d), ctypes.c_void_p(ptr),
+                                     ctypes.c_void_p(color_ptr) if color_ptr else None, ctypes.byref(st)), "engine.run_denoised")
         self.stats = st.as_dict()
         return int(round(st.ms))
 

@@ -3,12 +3,14 @@
 //
 //   art_render SCENE W H SPP OUT.png [--mode single|stripes|images|adaptive] [--seed N] [--max-depth D] [--device I]
 //                                    [--assets DIR] [--gpus N] [--progressive K] [--save-scene FILE] [--option NAME=VALUE]
+//                                    [--denoise]
 //   art_render --info SCENE [--assets DIR]     scene_manager::build only (no GPU needed): prints the scene summary
 //
 // SCENE is a scene_manager alias, or file:PATH for a flat-scene file written by --save-scene.  --gpus N renders on
 // devices 0..N-1 through multi_engine (RCCL); --progressive K traces K samples per pass and prints one JSON line per
-// pass (the headless live preview); --option sets a library option (rt_option_set, include/art.h) before the scene is
-// built, e.g. --option bvh.sah_ci=1.0 (repeatable).  Prints one JSON line: {"scene", "W", "H", "spp", "ms", "segments",
+// pass (the headless live preview); --denoise renders SPP (even) as two half-renders and filters the frame
+// (engine::run_denoised: first-hit guides + variance-guided a-trous filter; one GPU, single / stripes modes);
+// --option sets a library option (rt_option_set, include/art.h) before the scene is built, e.g. --option bvh.sah_ci=1.0 (repeatable).  Prints one JSON line: {"scene", "W", "H", "spp", "ms", "segments",
 // "msamples_per_s", "extend_variant"}.
 #include <cstdlib>
 #include <cstring>
@@ -29,7 +31,7 @@ std::string default_assets(const char* argv0) {  // <repo>/assets next to <repo>
 
 int usage() {
     std::cerr << "usage: art_render SCENE W H SPP OUT.png [--mode single|stripes|images|adaptive] [--seed N] [--max-depth D]"
-                 " [--device I] [--assets DIR] [--gpus N] [--progressive K] [--save-scene FILE] [--option NAME=VALUE]\n"
+                 " [--device I] [--assets DIR] [--gpus N] [--progressive K] [--save-scene FILE] [--option NAME=VALUE] [--denoise]\n"
                  "       art_render --info SCENE [--assets DIR]\n";
     return 2;
 }
@@ -42,7 +44,7 @@ int main(int argc, char** argv) try {
     uint64_t seed = 0;
     int max_depth = 50, device = 0, gpus = 0, progressive = -1;
     std::string save_path;
-    bool info = false;
+    bool info = false, denoise = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> std::string {
@@ -50,6 +52,7 @@ int main(int argc, char** argv) try {
             return argv[++i];
         };
         if (a == "--info") info = true;
+        else if (a == "--denoise") denoise = true;
         else if (a == "--assets") assets = next();
         else if (a == "--mode") mode = next();
         else if (a == "--seed") seed = std::strtoull(next().c_str(), nullptr, 10);
@@ -94,6 +97,7 @@ int main(int argc, char** argv) try {
                     1.0);  // main.cpp:35 (aspect W/H: SURVEY Q6)
     std::vector<std::uint8_t> image(static_cast<size_t>(W) * H * 3);
     rt_stats st{};
+    if (denoise && (gpus > 0 || progressive >= 0)) throw std::invalid_argument("--denoise renders on one GPU, not with --gpus or --progressive");
     if (gpus > 0) {  // engine.h:335-376's parallel drivers over GPUs
         if (from_file) throw std::invalid_argument("--gpus builds the scene on every device: give a scene alias");
         std::vector<int> devs;
@@ -111,6 +115,8 @@ int main(int argc, char** argv) try {
                 std::cout << "{\"pass_samples_done\":" << done << "}" << std::endl;
                 return true;
             }, progressive);
+        } else if (denoise) {
+            ms = eng.run_denoised(image.data());
         } else {
             ms = eng.run(image.data());  // main.cpp:45
         }
@@ -120,7 +126,7 @@ int main(int argc, char** argv) try {
     if (!art::imageio::save_image(pos[4], W, H, 3, image.data())) throw std::runtime_error("cannot write " + pos[4]);
     std::cout << "{\"scene\":\"" << pos[0] << "\",\"W\":" << W << ",\"H\":" << H << ",\"spp\":" << spp << ",\"ms\":" << st.ms
               << ",\"segments\":" << st.segments << ",\"msamples_per_s\":" << (st.ms > 0 ? st.segments / st.ms / 1e3 : 0.0)
-              << ",\"extend_variant\":" << st.extend_variant << "}" << std::endl;
+              << ",\"extend_variant\":" << st.extend_variant << (denoise ? ",\"denoised\":true" : "") << "}" << std::endl;
     return 0;
 } catch (const std::exception& e) {
     std::cerr << "art_render: " << e.what() << std::endl;

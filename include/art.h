@@ -27,6 +27,8 @@
  *   hittable_list::hit(r, 0.001, inf, rec)   hittable_list.cpp:5 rt_trace_rays(scene, rays, n, flags, t, normals)
  *   (scene construction every run)           scene_manager.cpp,  rt_scene_save / rt_scene_load (flat-scene files)
  *                                            mesh.h, bvh.cpp
+ *   (none: engine_mode::adaptive interpolates     engine.h:96-333  rt_render_guides + rt_denoise, or rt_render_denoised
+ *    untraced pixels; there is no denoiser)                          (first-hit guides, variance-guided a-trous filter)
  *
  * RNG contract: the reference draws from one global std::mt19937 (tracer_utils.h:27-31).  Scene construction here
  * replays that generator exactly (seed 5489, same draw order), so scenes are bit-identical.  Rendering draws come
@@ -52,7 +54,9 @@ extern "C" {
  * collective (RT_E_DEVICE on an RCCL error or timeout, after which the rt_multi refuses further renders).
  * ABI 5: rt_option_set / rt_option_get (process-wide options; the library reads no environment knobs but the documented
  * ART_MULTI_TIMEOUT_MS); rt_stats.kernel_features / kernel_textures / kernel_lds_mode name the persistent kernel a
- * render ran; rt_multi_create uploads the scene to every device before it returns. */
+ * render ran; rt_multi_create uploads the scene to every device before it returns.
+ * Additive since ABI 5 (the version stays 5): rt_render_guides, rt_denoise, rt_render_denoised, rt_denoise_params,
+ * RT_GUIDE_DOUBLES, RT_DN_NO_DEMODULATE. */
 #define RT_ABI_VERSION 5
 
 /* return codes */
@@ -155,6 +159,8 @@ int rt_device_count(void);
  *   of more than 8192 references takes the 32-bit-code kernels), render.tex_bary (1; 0 = meshes whose only images are
  *   barycentric take the all-textures kernels), render.lds_nodes_max (diagnostic cap on LDS nodes): uploads and
  *   renders after the call (kernel-selection switches for A/B; images are identical either way);
+ *   denoise.lds_iterations (2; how many of rt_denoise's first iterations -- tap spacings 1, 2 -- read their taps from an
+ *   LDS tile instead of loading each directly; 0..2, the result is identical either way);
  *   multi.timeout_ms (the RCCL deadline; inf = none), multi.rccl_blocking (0; 1 = blocking communicators, diagnosis:
  *   gives up the deadline and the error-path protection);
  *   test.fault_workspace_bytes (0 = off; N refuses workspace growth beyond N bytes), test.fault_gather_abort (0; 1 = the
@@ -217,6 +223,53 @@ int rt_local_rows(const rt_params* params, int32_t* rows_out);
 int rt_band_block_rows(int32_t height, int32_t band_rows, int32_t n);
 int rt_unpack_bands(const uint8_t* packed, size_t packed_bytes, uint8_t* frame, size_t frame_bytes, int32_t width, int32_t height,
                     int32_t band_rows, int32_t n, int32_t flags, void* stream);
+
+/* ---- denoising (additive since ABI 5; the reference has none) ----
+ * rt_render_guides: the first-hit guide buffers of the local rows (ordered as in rt_render), RT_GUIDE_DOUBLES per pixel:
+ * albedo[3], normal[3], position[3], t.  One ray per pixel with no render RNG draw: through the pixel centre
+ * (s = (i + 0.5) / (W - 1), t = ((H - 1 - gy) + 0.5) / (H - 1)) of rt_render's camera basis, from `origin` (no lens
+ * offset), d = llc + s * horizontal + t * vertical - origin, time = time0; its constant_medium draws come from the PCG
+ * stream keyed (seed 0, global pixel gy * W + i, sample 0), so a whole frame's t and normal equal rt_trace_rays of
+ * rays_out (optional: the 7 doubles of every ray) with ray index = pixel index.  position is the hit point as the
+ * hit_record holds it.  albedo: the texture value at the hit for lambertian and isotropic, the albedo of a metal,
+ * (1, 1, 1) for dielectric and diffuse_light.  A miss has t = +inf, normal 0, position +inf, albedo 1.
+ * Honours width, height, the band fields, stream, RT_OUT_DEVICE and RT_GLOBAL_SCENE; ignores spp, seed, max_depth and
+ * samples_per_pass; any other flag is RT_E_INVALID.  Blocking. */
+#define RT_GUIDE_DOUBLES 10
+int rt_render_guides(rt_scene* scene, const rt_camera* cam, const rt_params* params, double* guides, double* rays_out);
+/* rt_denoise: a variance-guided edge-avoiding a-trous filter.  accum_a / accum_b: two rt_render out_accum frames of the
+ * same whole width x height image (bands unpacked by the caller), spp_each samples each, rendered with different seeds
+ * (independent estimates: their mean is the frame, their half difference squared its variance); guides: that frame's
+ * rt_render_guides.  out_color: width * height * 3 filtered radiance (per sample, i.e. already divided by the sample
+ * count); out_rgb8 (optional): write_color of it (gamma 2, clamp, quantize, as rt_render with spp = 1).  The mean is
+ * divided by max(albedo, albedo_floor) before filtering and multiplied back after it unless RT_DN_NO_DEMODULATE.  Each of
+ * the `iterations` passes (tap spacing 1, 2, 4, ...) is a 5x5 B3-spline average weighted by the normals
+ * (max(0, n.n')^(2^normal_squarings)), the distance from the centre's tangent plane (sigma_plane), hit / miss, and the
+ * colour difference against sigma_color^2 times the 3x3-blurred variance, which is filtered along.  All f64 + - * / in a
+ * fixed order: tests/dn_reference.py restates it and the result equals it bit for bit.  Host buffers, or device buffers
+ * on `device` with RT_OUT_DEVICE; ms (optional): device time of the filter kernels.  One call at a time per device. */
+#define RT_DN_NO_DEMODULATE 256
+typedef struct rt_denoise_params {   /* zero-initialised = defaults */
+    int32_t width, height;
+    int32_t iterations;         /* 0 -> 5; 1..8 */
+    int32_t normal_squarings;   /* 0 -> 6 (normal weight = max(0, n.n')^(2^k)); 1..10 */
+    double sigma_color;         /* 0 -> 1.0 */
+    double sigma_plane;         /* 0 -> 0.1 */
+    double albedo_floor;        /* 0 -> 0.5 (measured: smaller floors let a dark albedo channel's 1/A^2 dominate the weights) */
+    int32_t flags;              /* RT_OUT_DEVICE | RT_DN_NO_DEMODULATE */
+    void* stream;               /* hipStream_t to run on, or NULL for the library's own */
+} rt_denoise_params;
+int rt_denoise(int device, const rt_denoise_params* p, const double* accum_a, const double* accum_b, int32_t spp_each,
+               const double* guides, double* out_color, uint8_t* out_rgb8, double* ms);
+/* rt_render_denoised: two rt_render passes of spp / 2 samples (seeds `seed` and `seed + 1`), rt_render_guides and
+ * rt_denoise in one call; the frames stay on the device until the final copy.  Needs the whole frame (band_count 1) and
+ * an even spp >= 2; no RT_ADAPTIVE or RT_PARALLEL_IMAGES.  dn: NULL = defaults (its width / height are taken from
+ * params; of its flags only RT_DN_NO_DEMODULATE is read, RT_OUT_DEVICE comes from params).  out_rgb8: W*H*3;
+ * out_color (optional): W*H*3 f64.  stats: segments / primary / passes / launches summed over the two renders, the
+ * kernel identity of the second; ms = host wall time of the whole call.  The result equals the same steps made through
+ * the public calls, bit for bit. */
+int rt_render_denoised(rt_scene* scene, const rt_camera* cam, const rt_params* params, const rt_denoise_params* dn, uint8_t* out_rgb8,
+                       double* out_color, rt_stats* stats);
 
 /* ---- images (imageio::load_image, imageio.cpp:11-15: stbi_load(path, &w, &h, &c, 0) of stb_image v2.27) ----
  * Decodes a JPEG (baseline or progressive) or PNG file to 8-bit samples, native channel count, row 0 = top, the bytes

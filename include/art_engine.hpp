@@ -187,6 +187,21 @@ public:
         check(rc, "engine::run_progressive");
         return static_cast<int>(stats_.ms);
     }
+    // Denoised render (rt_render_denoised; the reference has no denoiser): two half-renders of spp / 2 samples (seeds
+    // seed and seed + 1), the first-hit guide pass and the variance-guided a-trous filter, all on the device.  `out`
+    // receives write_color of the filtered frame, `color` (optional, W*H*3 doubles) the frame itself; `dn` NULL = the
+    // filter's defaults.  spp must be even; single / parallel_stripes only.  Returns the elapsed milliseconds of the
+    // whole call, or -1 for an empty world.
+    int run_denoised(std::uint8_t* out, double* color = nullptr, const rt_denoise_params* dn = nullptr) {
+        if (!world_.objects || world_.info.objects == 0) {
+            std::fprintf(stderr, "Invalid input scene!\n");
+            return -1;
+        }
+        const rt_params p = params();
+        if (p.flags & (RT_ADAPTIVE | RT_PARALLEL_IMAGES)) throw std::logic_error("engine::run_denoised: adaptive and parallel_images frames are not denoised");
+        check(rt_render_denoised(world_.objects.get(), &cam_.raw(), &p, dn, out, color, &stats_), "engine::run_denoised");
+        return static_cast<int>(stats_.ms);
+    }
     const rt_stats& stats() const { return stats_; }
 
 private:
