@@ -244,7 +244,7 @@ struct Work {
     uint32_t* counters;         // [(depth * kQueueKinds + kind) * kShards + shard] * kCounterStride
     unsigned long long* segments;
     double* acc;                // local pixels * 3
-    void* pool;                 // k_paths camera-ray rings: kPoolRing PoolRays per wave
+    void* pool;                 // k_paths first-bounce rings: kPoolRing + kPoolPark PoolRays per wave
 };
 template <class R>
 __host__ __device__ __forceinline__ uint32_t* counter(const Work<R>& w, int d, int kind, int s) {
@@ -673,16 +673,20 @@ __global__ __launch_bounds__(L ? kBlockL : kBlock, L ? 1 : ART_EXTEND_MIN_WAVES)
 // increasing order in wave chunks of PassGeom::chunk from one counter (one atomic per chunk).  The bounce arithmetic
 // and the RNG draws are those of the fused k_extend, so images are bit-identical to the wavefront variants.
 // The slots a wave claims per atomic on the pass counter: PassGeom::chunk = path_chunk (pass_plan.h).
-// Camera-ray pool: a path start is run by the whole wave for however few lanes start a path (~a third
-// of them per round), so the camera rays are generated 64 at a time -- one per lane, converged -- into a per-wave ring
-// in global memory (L2-resident: 8 KiB per wave), and a starting lane loads the next ring entry instead.  Entry pos
-// holds the ray of slot base[(pos / 64) & 1] + pos % 64; tm = NaN marks a padding slot of a partial tile.
-// ART_POOL_RING: ring entries per wave.  128: two batches of 64, refilled when a batch's worth is free, so a round's
-// takers always find entries; 96 (default): refilled when at most 32 are left, so a round with more takers than
-// entries leaves the rest idle for that round.  Measured (r3m, scene 1, PMC per segment; XCD-contiguous rings): HBM
-// reads 3.50 B (128) -> 0.10 B (96), writes 33.5 -> 27.9 B: the 3 MiB of rings per XCD stay in its 4 MiB L2 between a
-// refill and the takes (the writes left are the 8.9 B of radiance records and dirty ring lines evicted between
-// laps); Msamples/s +0.4 % (within the run-to-run spread).
+// First-bounce pool: a path start is run by the whole wave for however few lanes start a path (~a third of them per
+// round), so paths are started 64 at a time -- one per lane, converged -- in a round of their own: the wave claims 64
+// consecutive slots, generates their camera rays and traces and shades their first segment with the loop's own trace
+// and shading code while the 64 rays are still together (sample-major slots: one 8x8-pixel patch; entry-major: one
+// pixel -- nearly identical traversals, instead of one lane each in waves of unrelated secondary rays).  A path that
+// ends there (miss, light, absorbed, max_depth 1) writes its radiance; one that continues is appended, compacted, to
+// a per-wave ring in global memory as it stands after the bounce (scattered ray, throughput, RNG state, slot), and a
+// lane that falls idle loads the next ring entry and goes on at depth 1.  The paths the lanes hold meanwhile are
+// parked in a per-lane area behind the wave's ring for the round (plain vector stores and loads; their registers are
+// the batch's), so the kernel keeps one trace and one shading site and its register count.
+// ART_POOL_RING: ring entries per wave.  A batch runs whenever 64 entries are free (a batch may append fewer, a sky
+// tile none); a round with more takers than entries leaves the rest idle for that round.  Measured for the camera-ray
+// ring this one replaces (r3m, scene 1, PMC per segment; XCD-contiguous rings): HBM reads 3.50 B (128 entries) ->
+// 0.10 B (96), writes 33.5 -> 27.9 B, Msamples/s +0.4 % (within the run-to-run spread).
 #ifndef ART_POOL_RING
 #define ART_POOL_RING 96
 #endif
@@ -692,17 +696,20 @@ static_assert(kPoolRing >= 96 && kPoolRing <= 128, "a ring holds the unread part
 // block-major layout, Msamples/s unchanged
 constexpr uint32_t kXcds = 8;  // MI355X
 constexpr uint32_t kPoolWavesPerCu = 32;  // rings allocated per CU: the most waves a CU holds
-struct PoolRay {
-    double ox, oy, oz, dx;
-    double dy, dz, tm;
+struct __align__(16) PoolRay {  // a path after its first bounce: six 16-B pieces
+    double2 a, b, c;  // (ox,oy) (oz,dx) (dy,dz)
+    double2 d, e;     // (tm,Tr) (Tg,Tb)
     uint64_t rng;
+    uint32_t slot, pad;
 };
-// A wave's ring.  Fields other than the pointer are wave-uniform.  refill() is called by the whole wave; take() by
-// the idle lanes of a round, before the round's refill (whose stores then go to entries already read).
+static_assert(sizeof(PoolRay) == 96, "ring entries and parked lanes are six 16-B pieces");
+constexpr uint32_t kPoolPark = 64;  // PoolRay-sized records behind a wave's ring: the parked path of each lane
+// A wave's ring.  Fields other than the pointer are wave-uniform.  batch(), append(), park() and unpark() are called
+// by the whole wave in a first-bounce round; take() by the idle lanes of an ordinary round.  An entry is read at least
+// one round after its stores: a first-bounce round ends with s_waitcnt vmcnt(0).
 struct RayRing {
     PoolRay* ring;
     uint32_t head, tail;    // positions consumed / produced
-    uint32_t base0, base1;  // first slot of the batch in ring half 0 / 1
     uint32_t cur, end;      // the wave's claimed slot chunk [cur, end)
     bool exhausted;         // every slot of the pass is in a batch
     // wave w of block b: the rings of one XCD's blocks are contiguous (blocks go to the 8 XCDs round
@@ -714,70 +721,93 @@ struct RayRing {
             const uint32_t per_xcd = (nblocks + kXcds - 1) / kXcds;
             wave = ((block % kXcds) * per_xcd + block / kXcds) * waves_per_block + w;
         }
-        ring = static_cast<PoolRay*>(pool) + static_cast<size_t>(wave) * kPoolRing;
-        head = tail = base0 = base1 = cur = end = 0;
+        ring = static_cast<PoolRay*>(pool) + static_cast<size_t>(wave) * (kPoolRing + kPoolPark);
+        head = tail = cur = end = 0;
         exhausted = false;
     }
-    __device__ __forceinline__ void refill(const PassGeom& sg, const CameraRec<double>& sc, uint32_t* next_slot, uint32_t lane) {
+    // a first-bounce round is due: the ring has room for a whole batch's paths
+    __device__ __forceinline__ bool room() const { return !exhausted && tail - head <= kPoolRing - 64u; }
+    // Claims the next 64 slots and generates their camera rays: true for a lane whose slot is a pixel of the pass
+    // (st: the new path, q: its slot); a padding slot of a partial tile or a slot >= P does nothing.
+    __device__ __forceinline__ bool batch(const PassGeom& sg, const CameraRec<double>& sc, uint32_t* next_slot, uint32_t lane, PathState<double>& st,
+                                          uint32_t& q) {
         if (cur == end) {
             const uint32_t chunk = sg.chunk;
             uint32_t nb = 0;
             if (lane == 0) nb = atomicAdd(next_slot, chunk);
-            nb = __shfl(nb, 0);
+            nb = __builtin_amdgcn_readfirstlane(nb);  // the whole wave is here: lane 0's
             cur = nb;
             end = nb + chunk;
         }
         const uint32_t b = cur;
         cur += 64;
-        const uint32_t slot = b + lane;
+        q = b + lane;
         __asm__ volatile("" ::: "memory");  // the LDS camera loads stay here
-        PoolRay e;
-        e.tm = __builtin_nan("");
+        if (b + 64u >= sg.P) exhausted = true;
         int lx, ly;
         uint32_t qi, j;
-        slot_split(sg, slot, qi, j);
-        if (slot < sg.P && slot_pixel(sg, qi, lx, ly)) {
-            Ray<double> r;
-            uint64_t rng;
-            cam_ray(sg, sc, j, lx, ly, r, rng);
-            e.ox = r.o.x; e.oy = r.o.y; e.oz = r.o.z; e.dx = r.d.x;
-            e.dy = r.d.y; e.dz = r.d.z; e.tm = r.tm; e.rng = rng;
-        }
-        ring[(tail + lane) % kPoolRing] = e;
-        if ((tail / 64u) & 1u) base1 = b;
-        else base0 = b;
-        tail += 64;
-        if (b + 64u >= sg.P) exhausted = true;
-    }
-    // The idle lane of rank `rank`: 1 = a path starts (st, q), 0 = a padding slot (the lane idles a round),
-    // 2 = the pass is drained.
-    __device__ __forceinline__ int take(uint32_t rank, uint32_t P, PathState<double>& st, uint32_t& q) const {
-        const uint32_t pos = head + rank;
-        const uint32_t slot = (((pos / 64u) & 1u) ? base1 : base0) + pos % 64u;
-        if (pos >= tail) return exhausted ? 2 : 0;  // 0: the ring ran dry this round (kPoolRing < 128 only)
-        if (slot >= P) return 2;
-        const PoolRay& e = ring[pos % kPoolRing];
-        const double tm = e.tm;
-        if (tm != tm) return 0;
-        st.ray.o = mk(e.ox, e.oy, e.oz);
-        st.ray.d = mk(e.dx, e.dy, e.dz);
-        st.ray.tm = tm;
-        st.rng = e.rng;
+        slot_split(sg, q, qi, j);
+        if (!(q < sg.P && slot_pixel(sg, qi, lx, ly))) return false;
+        cam_ray(sg, sc, j, lx, ly, st.ray, st.rng);
         st.T = mk(1.0, 1.0, 1.0);
-        st.L = mk(0.0, 0.0, 0.0);
-        q = slot;
+        return true;
+    }
+    // The batch's continuing paths, compacted: position = tail + the lane's rank among them.
+    __device__ __forceinline__ void append(bool cont, uint64_t below, const PathState<double>& st, uint32_t q) {
+        const uint64_t m = __ballot(cont);
+        if (cont) {
+            PoolRay& e = ring[(tail + static_cast<uint32_t>(__popcll(m & below))) % kPoolRing];
+            e.a = make_double2(st.ray.o.x, st.ray.o.y);
+            e.b = make_double2(st.ray.o.z, st.ray.d.x);
+            e.c = make_double2(st.ray.d.y, st.ray.d.z);
+            e.d = make_double2(st.ray.tm, st.T.x);
+            e.e = make_double2(st.T.y, st.T.z);
+            e.rng = st.rng;
+            e.slot = q;
+        }
+        tail += static_cast<uint32_t>(__popcll(m));
+    }
+    // The idle lane of rank `rank`: 1 = a path goes on after its first bounce (st, q), 0 = the ring ran dry this round
+    // (the lane idles a round), 2 = the pass is drained.
+    __device__ __forceinline__ int take(uint32_t rank, PathState<double>& st, uint32_t& q) const {
+        const uint32_t pos = head + rank;
+        if (pos >= tail) return exhausted ? 2 : 0;
+        const PoolRay& e = ring[pos % kPoolRing];
+        const double2 a = e.a, b = e.b, c = e.c, d = e.d, f = e.e;
+        st.ray.o = mk(a.x, a.y, b.x);
+        st.ray.d = mk(b.y, c.x, c.y);
+        st.ray.tm = d.x;
+        st.T = mk(d.y, f.x, f.y);
+        st.rng = e.rng;
+        q = e.slot;
         return 1;
     }
-    // after the round's take(): n entries consumed; refill when a batch's worth is free, so an entry is read at
-    // least one round after its stores (ordered by the s_waitcnt vmcnt(0) the path loops place after the trace)
-    __device__ __forceinline__ void advance(uint32_t n, const PassGeom& sg, const CameraRec<double>& sc, uint32_t* next_slot, uint32_t lane) {
-        head = min(head + n, tail);
-        if (!exhausted && tail - head <= kPoolRing - 64u) refill(sg, sc, next_slot, lane);
+    // after the round's take(): n entries consumed
+    __device__ __forceinline__ void advance(uint32_t n) { head = min(head + n, tail); }
+    // The lane's path for the length of a first-bounce round, piece-major behind the ring (each piece of the wave is
+    // 1 KiB contiguous).  The compiler barriers keep the values dead between the stores and the loads.
+    __device__ __forceinline__ void park(uint32_t lane, const PathState<double>& st, uint32_t q, int depth) const {
+        double2* p = reinterpret_cast<double2*>(ring + kPoolRing) + lane;
+        p[0 * 64] = make_double2(st.ray.o.x, st.ray.o.y);
+        p[1 * 64] = make_double2(st.ray.o.z, st.ray.d.x);
+        p[2 * 64] = make_double2(st.ray.d.y, st.ray.d.z);
+        p[3 * 64] = make_double2(st.ray.tm, st.T.x);
+        p[4 * 64] = make_double2(st.T.y, st.T.z);
+        p[5 * 64] = make_double2(__longlong_as_double(static_cast<long long>(st.rng)),
+                                 __hiloint2double(depth, static_cast<int>(q)));
+        __asm__ volatile("" ::: "memory");
     }
-    __device__ __forceinline__ void start(const PassGeom& sg, const CameraRec<double>& sc, uint32_t* next_slot, uint32_t lane) {
-        refill(sg, sc, next_slot, lane);
-        if (kPoolRing >= 128 && !exhausted) refill(sg, sc, next_slot, lane);
-        __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __device__ __forceinline__ void unpark(uint32_t lane, PathState<double>& st, uint32_t& q, int& depth) const {
+        __asm__ volatile("" ::: "memory");
+        const double2* p = reinterpret_cast<const double2*>(ring + kPoolRing) + lane;
+        const double2 a = p[0 * 64], b = p[1 * 64], c = p[2 * 64], d = p[3 * 64], e = p[4 * 64], f = p[5 * 64];
+        st.ray.o = mk(a.x, a.y, b.x);
+        st.ray.d = mk(b.y, c.x, c.y);
+        st.ray.tm = d.x;
+        st.T = mk(d.y, e.x, e.y);
+        st.rng = static_cast<uint64_t>(__double_as_longlong(f.x));
+        q = static_cast<uint32_t>(__double2loint(f.y));
+        depth = __double2hiint(f.y);
     }
 };
 __host__ __device__ constexpr size_t paths_stack_bytes(uint32_t stack) { return (sizeof(int16_t) * stack * kBlockL + 15u) & ~size_t(15); }
@@ -839,63 +869,91 @@ __global__ __launch_bounds__(kBlockL, 1) void k_paths(DevScene<double> S0, PassG
     PathState<R> st;
     unsigned long long segs = 0;
 #ifdef ART_STATS
-    unsigned long long tm_load = 0, tm_trace = 0, tm_shade = 0, tm_app = 0, tm_prev = __builtin_amdgcn_s_memtime();
+    unsigned long long tm_load = 0, tm_trace = 0, tm_shade = 0, tm_app = 0, tm_fb = 0, tm_prev = __builtin_amdgcn_s_memtime();
 #endif
     RayRing rr;
     rr.init(w.pool, blockIdx.x, gridDim.x, B / 64, threadIdx.x / 64);
-    rr.start(s_g, s_cam, next_slot, lane);
     for (;;) {
-        // every idle lane takes the next ring entry (a padding slot of a partial tile leaves it idle a round)
-        const uint64_t idle = __ballot(!busy && !drained);
-        if (idle) {
-            const uint32_t n = static_cast<uint32_t>(__popcll(idle));
-            const uint32_t rank = static_cast<uint32_t>(__popcll(idle & below));
-            if (!busy && !drained) {
-                const int got = rr.take(rank, s_g.P, st, q);  // g.P, or the device count's (list_mode): read where used
-                drained = got == 2;
-                busy = got == 1;
-                depth = 0;
+        // A round is either a first-bounce round (the ring has room for a batch: all 64 lanes start a path, the paths
+        // they hold are parked) or an ordinary one (idle lanes take ring entries, busy lanes trace their segment).
+        // `act`: the lane traces and shades this round.  The ring and the area are private to the wave and no lane or
+        // wave waits on another; every first-bounce round consumes 64 slots, so their number is bounded by the pass.
+        const bool fb = rr.room();
+        const bool held = __ballot(busy) != 0;
+        bool act;
+        if (fb) {
+            if (held) rr.park(lane, st, q, depth);
+            act = rr.batch(s_g, s_cam, next_slot, lane, st, q);
+            depth = 0;
+        } else {
+            // every idle lane takes the next ring entry (more takers than entries: the rest idle a round)
+            const uint64_t idle = __ballot(!busy && !drained);
+            if (idle) {
+                const uint32_t n = static_cast<uint32_t>(__popcll(idle));
+                const uint32_t rank = static_cast<uint32_t>(__popcll(idle & below));
+                if (!busy && !drained) {
+                    const int got = rr.take(rank, st, q);
+                    drained = got == 2;
+                    busy = got == 1;
+                    depth = 1;
+                }
+                rr.advance(n);
             }
-            rr.advance(n, s_g, s_cam, next_slot, lane);
+            if (__ballot(busy) == 0) {
+                ART_TICK(tm_load);
+                if (__ballot(!drained) == 0) break;
+                continue;
+            }
+            act = busy;
         }
-        ART_TICK(tm_load);
-        if (__ballot(busy) == 0) {
-            if (__ballot(!drained) == 0) break;
-            continue;
-        }
+        ART_TICK((fb ? tm_fb : tm_load));
         R t = R(0);
         HitOut h{0, 0, kMatUnknown};
         bool hitw = false;
-        if (busy) {
+        if (act) {
             ++segs;
             hitw = trace_world<R, kFeatSpheres, B, true>(S, lds, st.ray, stk, st.rng, t, h);
 #if ART_LDS_LEAF_NOREF
             if (hitw) h.mt = reinterpret_cast<const uint32_t*>(lds + kLdsOffRef)[h.obj >> 16] >> kLdsRefMatShift;
 #endif
         }
-        // the ring stores of this round's refill (issued before the trace) are complete before the next round's loads
+        // an ordinary round's ring loads are complete
         __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        ART_TICK(tm_trace);
+        ART_TICK((fb ? tm_fb : tm_trace));
         // the whole wave draws random_in_unit_sphere for its lambertian and metal hits (material.h:33, :55), which
         // scatter with it first; lights and the max_depth bounce draw nothing
-        const bool need = busy && hitw && (h.mt == MAT_LAMBERTIAN || h.mt == MAT_METAL) && depth + 1 < g.max_depth;
+        const bool need = act && hitw && (h.mt == MAT_LAMBERTIAN || h.mt == MAT_METAL) && depth + 1 < g.max_depth;
         const V3<R> ps = coop_unit_sphere<R>(need, st.rng, jt);
-        if (busy) {
-            bool cont = false;
+        bool cont = false;
+        if (act) {
+            // a live path's radiance is zero: only a miss (engine.h:455-456) or a light adds to it, and both end the path
+            st.L = mk(R(0), R(0), R(0));
             if (hitw) {
                 cont = shade_hit_lds(lds, h.obj >> 16, h.mt, t, depth + 1 >= g.max_depth, st, &ps);
             } else {  // engine.h:455-456: miss -> background
                 st.L = st.L + st.T * bg;
             }
-            ART_TICK(tm_shade);
-            if (cont) {
-                ++depth;
-            } else {
-                store_res(w.res, q, st.L);
-                busy = false;
-            }
+            if (!cont) store_res(w.res, q, st.L);
         }
-        ART_TICK(tm_app);
+        ART_TICK((fb ? tm_fb : tm_shade));
+        if (fb) {
+#ifdef ART_STATS
+            const uint64_t m_act = __ballot(act), m_cont = __ballot(cont);
+            if (lane == 0) {
+                atomicAdd(&g_art_stats[49], 1ull);
+                atomicAdd(&g_art_stats[50], static_cast<unsigned long long>(__popcll(m_act)));
+                atomicAdd(&g_art_stats[51], static_cast<unsigned long long>(__popcll(m_cont)));
+            }
+#endif
+            rr.append(cont, below, st, q);
+            if (held) rr.unpark(lane, st, q, depth);
+            // the ring entries are stored before a later round loads them, and the parked paths are back
+            __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        } else if (act) {
+            if (cont) ++depth;
+            else busy = false;
+        }
+        ART_TICK((fb ? tm_fb : tm_app));
     }
     for (int off = 32; off > 0; off >>= 1) segs += __shfl_xor(segs, off);
     if (lane == 0) atomicAdd(w.segments, segs);
@@ -905,6 +963,7 @@ __global__ __launch_bounds__(kBlockL, 1) void k_paths(DevScene<double> S0, PassG
         atomicAdd(&g_art_stats[9], tm_trace);
         atomicAdd(&g_art_stats[10], tm_shade);
         atomicAdd(&g_art_stats[11], tm_app);
+        atomicAdd(&g_art_stats[48], tm_fb);
     }
 #endif
 }
@@ -2586,7 +2645,7 @@ static void render_impl(Renderer::Impl& I, DeviceScene<R>& ds, const CameraRec<d
     const size_t o_acc = off; off += al(sizeof(double) * 3 * local_pix);
     const size_t o_rgb = off; off += al(3 * local_pix);
     const size_t o_qsum = off; off += images ? al(sizeof(double) * 3 * local_pix) : 0;  // parallel_images quarter sums
-    const size_t o_pool = off; off += (variant == EXT_MEGA) ? al(sizeof(PoolRay) * kPoolRing * kPoolWavesPerCu * static_cast<size_t>(I.num_cu)) : 0;
+    const size_t o_pool = off; off += (variant == EXT_MEGA) ? al(sizeof(PoolRay) * (kPoolRing + kPoolPark) * kPoolWavesPerCu * static_cast<size_t>(I.num_cu)) : 0;
     // adaptive mode: int work frame, pixel list (<= 80 of every 144 pixels per level), square flags, list counter
     const bool adapt_ws = (p.flags & RT_ADAPTIVE) != 0;
     const size_t nsq_ws = adapt_ws ? local_pix / (kBig * kBig) : 0;
@@ -2825,11 +2884,14 @@ static void render_impl(Renderer::Impl& I, DeviceScene<R>& ds, const CameraRec<d
         if (st[15] + st[17] + st[19] + st[21] > 0)
             std::fprintf(stderr, "ART_STATS leaf tests by type (lane tests, wave iterations running it): box %llu %llu sphere %llu %llu triangle %llu %llu rect %llu %llu\n",
                          st[15], st[16], st[17], st[18], st[19], st[20], st[21], st[22]);
-        const double tt = double(st[8] + st[9] + st[10] + st[11] + st[24] + st[25] + st[26]);
+        const double tt = double(st[8] + st[9] + st[10] + st[11] + st[24] + st[25] + st[26] + st[48]);
         if (tt > 0)
             std::fprintf(stderr, "ART_STATS cycles: load/claim %.3f trace %.3f shade %.3f append/store %.3f (k_paths_g shading split: surface %.3f "
                          "coop-sphere %.3f texture+unit %.3f scatter %.3f)\n",
                          st[8] / tt, st[9] / tt, (st[10] + st[24] + st[25] + st[26]) / tt, st[11] / tt, st[24] / tt, st[25] / tt, st[26] / tt, st[10] / tt);
+        if (st[49] > 0)
+            std::fprintf(stderr, "ART_STATS first bounce: cycles %.3f batches %llu camera rays %llu (util %.3f) entries appended %llu (%.2f per batch)\n",
+                         st[48] / tt, st[49], st[50], st[50] / (64.0 * st[49]), st[51], double(st[51]) / st[49]);
         if (st[28] + st[30] > 0)
             std::fprintf(stderr, "ART_STATS texture evaluations (wave iterations, lanes): noise %llu %llu image %llu %llu\n", st[28], st[29], st[30], st[31]);
         if (st[46] > 0)
