@@ -67,6 +67,18 @@ class rt_denoise_params(ctypes.Structure):  # zero-initialised = defaults
                 ("albedo_floor", ctypes.c_double), ("flags", ctypes.c_int32), ("stream", ctypes.c_void_p)]
 
 
+class rt_noise_params(ctypes.Structure):  # zero-initialised = defaults
+    _fields_ = [("min_spp", ctypes.c_int32), ("step_spp", ctypes.c_int32), ("dilate", ctypes.c_int32),
+                ("rel_tol", ctypes.c_double), ("lum_floor", ctypes.c_double)]
+
+
+class rt_noise_result(ctypes.Structure):
+    _fields_ = [("rounds", ctypes.c_int32), ("converged_pixels", ctypes.c_int64), ("samples", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class rt_multi_times(ctypes.Structure):
     _fields_ = [("total_ms", ctypes.c_double), ("render_ms_max", ctypes.c_double), ("render_ms_min", ctypes.c_double),
                 ("gather_ms", ctypes.c_double), ("unpack_ms", ctypes.c_double), ("wait_ms", ctypes.c_double),
@@ -103,6 +115,8 @@ SIGNATURES = {
     "rt_denoise": (_I, [_I, ctypes.POINTER(rt_denoise_params), _P, _P, ctypes.c_int32, _P, _P, _P, _DP]),
     "rt_render_denoised": (_I, [_P, ctypes.POINTER(rt_camera), ctypes.POINTER(rt_params), ctypes.POINTER(rt_denoise_params), _P, _P,
                                 ctypes.POINTER(rt_stats)]),
+    "rt_render_noise_target": (_I, [_P, ctypes.POINTER(rt_camera), ctypes.POINTER(rt_params), ctypes.POINTER(rt_noise_params), _P, _P, _P, _P,
+                                    ctypes.POINTER(rt_stats), ctypes.POINTER(rt_noise_result)]),
     "rt_image_load": (_I, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                            ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8))]),
     "rt_image_free": (None, [ctypes.POINTER(ctypes.c_uint8)]),

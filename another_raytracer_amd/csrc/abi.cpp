@@ -430,6 +430,45 @@ int rt_render_denoised(rt_scene* s, const rt_camera* cam, const rt_params* p, co
     });
 }
 
+int rt_render_noise_target(rt_scene* s, const rt_camera* cam, const rt_params* p, const rt_noise_params* noise, uint8_t* out_rgb8, double* out_accum,
+                           int32_t* out_count, double* out_moments, rt_stats* stats, rt_noise_result* result) {
+    std::string why;
+    if (!s || !cam || !out_rgb8) return fail(RT_E_INVALID, "scene, camera and out_rgb8 must be non-NULL");
+    if (!valid_params(p, why)) return fail(RT_E_INVALID, why);
+    if (p->flags & (RT_ADAPTIVE | RT_PARALLEL_IMAGES | RT_WAVEFRONT | RT_SPLIT_SHADE))
+        return fail(RT_E_INVALID, "rt_render_noise_target traces engine_mode::single samples through the persistent-path kernels "
+                                  "(no RT_ADAPTIVE, RT_PARALLEL_IMAGES, RT_WAVEFRONT or RT_SPLIT_SHADE)");
+    art::NoiseParams np;
+    if (noise) {
+        if (noise->min_spp < 0 || noise->min_spp == 1) return fail(RT_E_INVALID, "min_spp must be >= 2 (the variance needs two samples; 0 = the default, 32)");
+        if (noise->step_spp < 0) return fail(RT_E_INVALID, "step_spp must be >= 1 (0 = the default, 32)");
+        if (noise->dilate != 0 && noise->dilate != 1) return fail(RT_E_INVALID, "dilate must be 0 or 1");
+        if (!(noise->rel_tol >= 0) || !(noise->lum_floor >= 0) || std::isinf(noise->rel_tol) || std::isinf(noise->lum_floor))
+            return fail(RT_E_INVALID, "rel_tol and lum_floor must be finite and >= 0 (0 = the default)");
+        if (noise->min_spp) np.min_spp = noise->min_spp;
+        if (noise->step_spp) np.step_spp = noise->step_spp;
+        np.dilate = noise->dilate == 1;
+        if (noise->rel_tol != 0) np.rel_tol = noise->rel_tol;
+        if (noise->lum_floor != 0) np.lum_floor = noise->lum_floor;
+    }
+    if (np.min_spp > p->spp) return fail(RT_E_INVALID, "min_spp (" + std::to_string(np.min_spp) + ") exceeds the per-pixel cap spp (" + std::to_string(p->spp) + ")");
+    if (np.dilate && p->band_count > 1)
+        return fail(RT_E_INVALID, "dilate = 1 needs the whole frame (band_count 1): a pixel's 3x3 neighbourhood would depend on the partition");
+    return guard(RT_E_DEVICE, [&] {
+        if (!s->renderer) s->renderer = std::make_unique<art::Renderer>(s->flat, s->device);
+        art::RenderStats st;
+        art::NoiseResult nr;
+        s->renderer->render_noise_target(camera_of(cam), render_params(p), np, out_rgb8, out_accum, out_count, out_moments, st, nr);
+        fill_stats(st, stats);
+        if (result) {
+            result->rounds = nr.rounds;
+            result->converged_pixels = nr.converged_pixels;
+            result->samples = nr.samples;
+        }
+        return RT_OK;
+    });
+}
+
 int rt_image_load(const char* path, int32_t* width, int32_t* height, int32_t* channels, uint8_t** pixels) {
     if (!path || !width || !height || !channels || !pixels) return fail(RT_E_INVALID, "NULL argument");
     *pixels = nullptr;

@@ -3042,6 +3042,217 @@ void Renderer::render(const CameraRec<double>& cam, const RenderParams& p, uint8
     render_impl<double>(*impl_, impl_->s64, cam, p, out_rgb, out_acc, stats);
 }
 
+// Noise-target rendering (rt_render_noise_target; render_impl's sibling, the kernels in noise_target.hip).  The base
+// pass traces samples [0, min_spp) of every local pixel through the whole-image path; every refinement round then
+// traces the next step_spp samples of the pixels the test left active, through the persistent kernel in pixel-list
+// mode with entry-major slots (PassGeom::list_mode 1) and one sample_base: retirement is sticky, so every active pixel
+// has the same count.  Every sum is continued in sample order, so a pixel with n samples equals rt_render's at spp = n.
+// The host reads the 4-byte entry count back once per round: it ends the loop, and sizes g.P, path_chunk, the grids and
+// the split of a round that exceeds the pass workspace into sub-passes by sample range.
+void Renderer::render_noise_target(const CameraRec<double>& cam, const RenderParams& p, const NoiseParams& np, uint8_t* out_rgb, double* out_acc,
+                                   int32_t* out_count, double* out_moments, RenderStats& stats, NoiseResult& result) {
+    if (p.fp_mode != RT_FP64) throw std::runtime_error("fp_mode must be RT_FP64");
+    upload();
+    Impl& I = *impl_;
+    DeviceScene<double>& ds = I.s64;
+    hipStream_t stream = p.stream ? static_cast<hipStream_t>(p.stream) : I.own_stream;
+    for (int a = 0; a < 3; ++a) ds.view.bg[a] = p.background[a];
+    const int nrows = band_local_rows(p.height, p.band_rows, p.band_count, p.band_index);
+    stats.local_rows = nrows;
+    result = NoiseResult{};
+    if (nrows == 0) return;
+    PassGeom g{};
+    g.W = p.width;
+    g.H = p.height;
+    g.rows = nrows;
+    g.band_rows = p.band_rows;
+    g.band_count = p.band_count;
+    g.band_index = p.band_index;
+    g.tiles_x = static_cast<uint32_t>((p.width + 7) / 8);
+    const uint32_t tile_pad = g.tiles_x * static_cast<uint32_t>((nrows + 7) / 8) * 64u;
+    g.npix_pad = tile_pad;
+    g.max_depth = p.max_depth;
+    g.seed = p.seed;
+    g.seed_mix = splitmix64(p.seed);
+    g.fd_tiles_x = FastDiv::make(g.tiles_x);
+    g.fd_band_rows = FastDiv::make(static_cast<uint32_t>(p.band_rows));
+    g.fd_w = FastDiv::make(static_cast<uint32_t>(p.width));
+    g.fd_npix = FastDiv::make(g.npix_pad);
+    g.inv_w1 = 1.0 / static_cast<double>(p.width - 1);
+    g.inv_h1 = 1.0 / static_cast<double>(p.height - 1);
+    g.stack = stack_rows(ds.max_stack);
+    const int variant = extend_variant(ds, p.flags);
+    if (variant != EXT_MEGA && variant != EXT_MEGA_G) throw std::runtime_error("internal: noise-target rendering needs a persistent-path kernel");
+    KernelId kid;
+    // samples per whole-image pass and the pass workspace: render_impl's rule (a slot is its radiance record)
+    size_t free_b = 0, total_b = 0;
+    HIP_OK(hipMemGetInfo(&free_b, &total_b));
+    const uint64_t target = std::min<uint64_t>((free_b + I.ws_bytes) / 2 / sizeof(ResRec<double>), kMaxPassSlots);
+    if (tile_pad > kMaxPassSlots) throw std::runtime_error("image too large for one pass (more than 2^31 padded pixels)");
+    const uint64_t k_cap = std::max<uint64_t>(1, kMaxPassSlots / tile_pad);
+    uint64_t k64 = p.samples_per_pass > 0 ? static_cast<uint64_t>(p.samples_per_pass) : std::max<uint64_t>(1, target / tile_pad);
+    const uint32_t k = static_cast<uint32_t>(std::min<uint64_t>(std::min<uint64_t>(k64, k_cap), static_cast<uint64_t>(p.spp)));
+    const uint32_t Pmax = k * tile_pad;  // <= kMaxPassSlots
+    g.cap = shard_cap(Pmax);
+    const size_t local_pix = static_cast<size_t>(nrows) * p.width;
+    const uint32_t npix = static_cast<uint32_t>(local_pix);
+
+    auto al = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
+    size_t off = 0;
+    const size_t o_res = off; off += al(sizeof(ResRec<double>) * Pmax);
+    const size_t o_cnt = off; off += al(4ull * kCounterStride);
+    const size_t o_seg = off; off += al(sizeof(unsigned long long));
+    const size_t o_acc = off; off += al(sizeof(double) * 3 * local_pix);
+    const size_t o_mom = off; off += al(sizeof(double) * 2 * local_pix);
+    const size_t o_count = off; off += al(sizeof(int32_t) * local_pix);
+    const size_t o_flag = off; off += al(local_pix);
+    const size_t o_rgb = off; off += al(3 * local_pix);
+    const size_t list_bytes = 4 * nt_list_words(local_pix);  // both lists with their count lines: allocation == memset
+    const size_t o_list = off; off += al(list_bytes);
+    const size_t o_conv = off; off += al(4);
+    const size_t o_pool = off; off += (variant == EXT_MEGA) ? al(sizeof(PoolRay) * (kPoolRing + kPoolPark) * kPoolWavesPerCu * static_cast<size_t>(I.num_cu)) : 0;
+    char* base = static_cast<char*>(I.workspace(off));
+
+    Work<double> w{};
+    w.res = reinterpret_cast<ResRec<double>*>(base + o_res);
+    w.counters = reinterpret_cast<uint32_t*>(base + o_cnt);
+    w.segments = reinterpret_cast<unsigned long long*>(base + o_seg);
+    w.acc = reinterpret_cast<double*>(base + o_acc);
+    w.pool = base + o_pool;
+    const double* res = reinterpret_cast<const double*>(w.res);
+    double* mom = reinterpret_cast<double*>(base + o_mom);
+    int32_t* count = reinterpret_cast<int32_t*>(base + o_count);
+    uint8_t* flag = reinterpret_cast<uint8_t*>(base + o_flag);
+    uint8_t* drgb = reinterpret_cast<uint8_t*>(base + o_rgb);
+    uint32_t* lists[2] = {reinterpret_cast<uint32_t*>(base + o_list) + 64, reinterpret_cast<uint32_t*>(base + o_list) + nt_list_stride(local_pix) + 64};
+    uint32_t* conv = reinterpret_cast<uint32_t*>(base + o_conv);
+
+    const bool prof = (p.flags & RT_PROFILE) != 0;
+    for (auto& e : I.ev)
+        if (!e) HIP_OK(hipEventCreate(&e));
+    std::vector<hipEvent_t> evs;  // RT_PROFILE: two per path launch (the number of rounds is not known beforehand)
+    struct EvGuard {
+        std::vector<hipEvent_t>& v;
+        ~EvGuard() { for (auto e : v) (void)hipEventDestroy(e); }
+    } ev_guard{evs};
+    auto mark = [&]() {
+        hipEvent_t e = nullptr;
+        HIP_OK(hipEventCreate(&e));
+        evs.push_back(e);
+        HIP_OK(hipEventRecord(e, stream));
+    };
+    int passes_run = 0;
+    uint64_t launches = 0;
+    // one pass of g (whole image or list) through the persistent kernel
+    auto paths = [&]() {
+        HIP_OK(hipMemsetAsync(w.counters, 0, 4u * kCounterStride, stream));
+        ++passes_run;
+        if (p.max_depth == 0) return;  // the records stay 0 (engine.h:451-452)
+        if (prof) mark();
+        g.chunk = path_chunk(g.P, I.num_cu);
+        if (variant == EXT_MEGA) {
+            launch_paths(I.num_cu, stream, ds.view, g, cam, w, counter(w, 0, 0, 0));
+            kid = KernelId{kFeatSpheres, 0, 3};
+        } else {
+            kid = launch_paths_g(ds.features, ds.tex_basic, ds.tex_bary, ds.codes16, ds.leaf_shift, I.num_cu, stream, ds.view, g, cam, w, counter(w, 0, 0, 0));
+        }
+        if (prof) mark();
+        ++launches;
+    };
+
+    HIP_OK(hipEventRecord(I.ev[0], stream));
+    HIP_OK(hipMemsetAsync(w.segments, 0, sizeof(unsigned long long), stream));
+    if (p.max_depth == 0) HIP_OK(hipMemsetAsync(w.res, 0, sizeof(ResRec<double>) * Pmax, stream));
+    HIP_OK(hipMemsetAsync(w.acc, 0, sizeof(double) * 3 * local_pix, stream));
+    HIP_OK(hipMemsetAsync(mom, 0, sizeof(double) * 2 * local_pix, stream));
+    HIP_OK(hipMemsetAsync(flag, 0, local_pix, stream));
+    HIP_OK(hipMemsetAsync(base + o_list, 0, list_bytes, stream));
+    HIP_OK(hipMemsetAsync(conv, 0, 4, stream));
+    // base pass: samples [0, min_spp) of every local pixel, tile-order slots
+    const uint32_t min_spp = static_cast<uint32_t>(np.min_spp), cap_spp = static_cast<uint32_t>(p.spp), step = static_cast<uint32_t>(np.step_spp);
+    for (uint32_t sb = 0; sb < min_spp; sb += k) {
+        g.sample_base = sb;
+        g.k = std::min<uint32_t>(k, min_spp - sb);
+        g.P = g.k * tile_pad;
+        g.live = g.k * npix;
+        paths();
+        nt_accum_base(stream, res, g.k, tile_pad, g.tiles_x, p.width, nrows, w.acc, mom);
+    }
+    // refinement rounds
+    uint64_t samples = static_cast<uint64_t>(local_pix) * min_spp;
+    uint32_t n_done = min_spp, n_active = npix;
+    const uint32_t* cur = nullptr;  // A_0: every local pixel
+    int rounds = 0;
+    g.list_mode = 1;
+    for (int side = 0;; side ^= 1) {
+        const uint32_t k_next = std::min<uint32_t>(step, cap_spp - n_done);
+        uint32_t* next = lists[side];
+        HIP_OK(hipMemsetAsync(next - 1, 0, 4, stream));
+        nt_select(stream, cur, n_active, mom, flag, p.width, nrows, static_cast<int>(n_done), static_cast<int>(k_next), np.dilate, np.rel_tol, np.lum_floor,
+                  next, count, conv);
+        if (k_next == 0) break;  // every active pixel is at the cap
+        HIP_OK(hipMemcpyAsync(&n_active, next - 1, 4, hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipStreamSynchronize(stream));
+        if (n_active == 0) break;
+        if (n_active > npix) throw std::runtime_error("internal: noise-target list longer than the image");
+        g.list = next;
+        g.nlist = n_active;
+        // sub-passes by sample range when the round's slots exceed the pass workspace (Pmax >= tile_pad >= n_active)
+        const uint32_t kk = std::min<uint32_t>(k_next, Pmax / n_active);
+        for (uint32_t sb = 0; sb < k_next; sb += kk) {
+            g.sample_base = n_done + sb;
+            g.k = std::min<uint32_t>(kk, k_next - sb);
+            g.npix_pad = g.k;
+            g.fd_npix = FastDiv::make(g.k);
+            g.P = n_active * g.k;
+            g.live = g.P;
+            paths();
+            nt_accum_list(stream, next, n_active, res, g.k, w.acc, mom);
+        }
+        samples += static_cast<uint64_t>(n_active) * k_next;
+        n_done += k_next;
+        cur = next;
+        ++rounds;
+    }
+    nt_finalize(stream, w.acc, count, drgb, npix);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(I.ev[1], stream));
+    const hipMemcpyKind kind = (p.flags & RT_OUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (out_rgb) HIP_OK(hipMemcpyAsync(out_rgb, drgb, 3 * local_pix, kind, stream));
+    if (out_acc) HIP_OK(hipMemcpyAsync(out_acc, w.acc, sizeof(double) * 3 * local_pix, kind, stream));
+    if (out_count) HIP_OK(hipMemcpyAsync(out_count, count, sizeof(int32_t) * local_pix, kind, stream));
+    if (out_moments) HIP_OK(hipMemcpyAsync(out_moments, mom, sizeof(double) * 2 * local_pix, kind, stream));
+    unsigned long long segs = 0;
+    uint32_t nconv = 0;
+    HIP_OK(hipMemcpyAsync(&segs, w.segments, sizeof segs, hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipMemcpyAsync(&nconv, conv, 4, hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    float ms = 0;
+    HIP_OK(hipEventElapsedTime(&ms, I.ev[0], I.ev[1]));
+    stats.ms = ms;
+    stats.passes = passes_run;
+    stats.samples_per_pass = static_cast<int>(k);
+    stats.segments = segs;
+    stats.extend_variant = variant;
+    stats.kernel_features = kid.f;
+    stats.kernel_textures = kid.tf;
+    stats.kernel_lds_mode = kid.lm;
+    stats.primary = samples;
+    if (prof) {
+        double ext_ms = 0;
+        for (size_t e = 0; e + 1 < evs.size(); e += 2) {
+            float a = 0;
+            HIP_OK(hipEventElapsedTime(&a, evs[e], evs[e + 1]));
+            ext_ms += a;
+        }
+        stats.extend_ms = ext_ms;
+        stats.extend_launches = launches;
+    }
+    result.rounds = rounds;
+    result.converged_pixels = nconv;
+    result.samples = samples;
+}
+
 #endif  // ART_SPLIT_PATHS <= 1
 }  // namespace art
 

@@ -5,6 +5,7 @@
 
 #include "art.h"
 #include "layout.h"
+#include "noise_target.h"
 #include "scene.h"
 
 namespace art {
@@ -50,6 +51,11 @@ public:
     // First-hit guide buffers of the local rows (k_guides): 10 doubles per pixel {albedo, normal, position, t} and,
     // when rays_out is non-NULL, the 7 doubles of every pixel-centre ray; host buffers, or device ones with RT_OUT_DEVICE.
     void render_guides(const CameraRec<double>& cam, const RenderParams& p, double* guides, double* rays_out);
+    // Noise-target rendering (rt_render_noise_target): p.spp is the per-pixel cap; every local pixel is traced until the
+    // test of noise_target.hip retires it.  out_acc (3 f64), out_count (int32) and out_moments ({S1, S2} f64) per local
+    // pixel are optional; host buffers, or device ones with RT_OUT_DEVICE.
+    void render_noise_target(const CameraRec<double>& cam, const RenderParams& p, const NoiseParams& np, uint8_t* out_rgb, double* out_acc,
+                             int32_t* out_count, double* out_moments, RenderStats& stats, NoiseResult& result);
     int device() const;
     size_t scene_bytes() const;
     const FlatScene& flat() const;

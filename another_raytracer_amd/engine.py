@@ -256,6 +256,66 @@ class engine:
         self.stats = st.as_dict()
         return int(round(st.ms))
 
+    def run_noise_target(self, output_image, accum=None, counts=None, moments=None, **noise_options):
+        """Noise-target render (rt_render_noise_target): every pixel is traced until the standard error of its mean
+        luminance is within rel_tol of the mean (+ lum_floor), up to samples_per_pixel samples (the per-pixel cap).
+        output_image (uint8, local_rows x W x 3) receives write_color of every pixel's sums with its own count;
+        optional: accum (float64 rows x W x 3 radiance sums), counts (int32 rows x W samples per pixel), moments
+        (float64 rows x W x 2: the luminance sums S1, S2).  numpy arrays, or torch tensors all on the device.
+        noise_options: min_spp, step_spp, dilate, rel_tol, lum_floor (0 / omitted = the defaults 32, 32, 0, 0.05, 0.01),
+        and band_rows, band_count, band_index, profile, stream as for run().  A pixel with n samples equals run() at
+        samples_per_pixel = n bit for bit.  Returns {"rounds", "converged_pixels", "samples", "ms"}, or None on an
+        empty world."""
+        from ._lib import rt_noise_params, rt_noise_result
+        if self._scene is None:
+            print("Invalid input scene!")
+            return None
+        if self.m in (engine_mode.adaptive, engine_mode.parallel_images) or self.split_shade or self.wavefront:
+            raise ValueError("run_noise_target traces engine_mode.single samples through the persistent-path kernels "
+                             "(no adaptive / parallel_images mode, split_shade or wavefront)")
+        opts = dict(noise_options)
+        flags = (RT_PROFILE if opts.pop("profile", False) else 0) | (RT_GLOBAL_SCENE if self.global_scene else 0)
+        p = self.params(opts.pop("band_rows", None), opts.pop("band_count", 1), opts.pop("band_index", 0), flags, opts.pop("stream", None))
+        n = rt_noise_params()
+        n.min_spp, n.step_spp, n.dilate = int(opts.pop("min_spp", 0)), int(opts.pop("step_spp", 0)), int(opts.pop("dilate", 0))
+        n.rel_tol, n.lum_floor = float(opts.pop("rel_tol", 0.0)), float(opts.pop("lum_floor", 0.0))
+        if opts:
+            raise TypeError(f"run_noise_target: unknown options {sorted(opts)}")
+        rows = check(lib.rt_local_rows(ctypes.byref(p), None), "rt_local_rows")
+        npix = rows * self.width
+        ptr, dev = _pointer(output_image, 3 * npix)
+        ptrs = []
+        for buf, per, what in ((accum, 3, "accum"), (moments, 2, "moments")):
+            if buf is None:
+                ptrs.append(None)
+                continue
+            a, d = _f64_pointer(buf, per * npix, what)
+            if d != dev:
+                raise ValueError(f"output_image and {what} must both live on the host or both on the device")
+            ptrs.append(ctypes.c_void_p(a))
+        cnt_ptr = None
+        if counts is not None:
+            if isinstance(counts, np.ndarray):
+                ok = counts.flags.c_contiguous and counts.dtype == np.int32 and counts.size >= npix
+                a, d = (counts.ctypes.data if ok else None), False
+            elif hasattr(counts, "data_ptr"):
+                ok = counts.is_contiguous() and str(counts.dtype) == "torch.int32" and counts.numel() >= npix
+                a, d = (counts.data_ptr() if ok else None), counts.device.type != "cpu"
+            else:
+                raise TypeError("counts must be a numpy array or a torch tensor")
+            if not ok:
+                raise ValueError(f"counts must be a contiguous int32 buffer of >= {npix} elements")
+            if d != dev:
+                raise ValueError("output_image and counts must both live on the host or both on the device")
+            cnt_ptr = ctypes.c_void_p(a)
+        if dev:
+            p.flags |= RT_OUT_DEVICE
+        st, res = rt_stats(), rt_noise_result()
+        check(lib.rt_render_noise_target(self._scene, ctypes.byref(self.cam.c), ctypes.byref(p), ctypes.byref(n), ctypes.c_void_p(ptr), ptrs[0],
+                                         cnt_ptr, ptrs[1], ctypes.byref(st), ctypes.byref(res)), "engine.run_noise_target")
+        self.stats = st.as_dict()
+        return dict(res.as_dict(), ms=st.ms)
+
     def run_progressive(self, output_image, callback, accum=None, samples_per_pass=0):
         """Progressive render (rt_render_progressive): the frame is traced in passes of samples_per_pass samples
         (0: spp / 8); after each pass callback(samples_done, spp) runs with output_image (and accum) holding the frame

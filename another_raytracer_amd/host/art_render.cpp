@@ -3,13 +3,16 @@
 //
 //   art_render SCENE W H SPP OUT.png [--mode single|stripes|images|adaptive] [--seed N] [--max-depth D] [--device I]
 //                                    [--assets DIR] [--gpus N] [--progressive K] [--save-scene FILE] [--option NAME=VALUE]
-//                                    [--denoise]
+//                                    [--denoise] [--noise-target TOL [--min-spp N] [--step-spp N]]
 //   art_render --info SCENE [--assets DIR]     scene_manager::build only (no GPU needed): prints the scene summary
 //
 // SCENE is a scene_manager alias, or file:PATH for a flat-scene file written by --save-scene.  --gpus N renders on
 // devices 0..N-1 through multi_engine (RCCL); --progressive K traces K samples per pass and prints one JSON line per
 // pass (the headless live preview); --denoise renders SPP (even) as two half-renders and filters the frame
 // (engine::run_denoised: first-hit guides + variance-guided a-trous filter; one GPU, single / stripes modes);
+// --noise-target TOL traces every pixel until the relative standard error of its mean luminance is within TOL, up to
+// SPP samples, with dilate = 1 (engine::run_noise_target; one GPU, single / stripes modes; not with --gpus, --progressive or --denoise)
+// and prints one more JSON line before the summary: {"noise_target", "rounds", "mean_spp", "converged_share", "ms"};
 // --option sets a library option (rt_option_set, include/art.h) before the scene is built, e.g. --option bvh.sah_ci=1.0 (repeatable).  Prints one JSON line: {"scene", "W", "H", "spp", "ms", "segments",
 // "msamples_per_s", "extend_variant"}.
 #include <cstdlib>
@@ -32,6 +35,7 @@ std::string default_assets(const char* argv0) {  // <repo>/assets next to <repo>
 int usage() {
     std::cerr << "usage: art_render SCENE W H SPP OUT.png [--mode single|stripes|images|adaptive] [--seed N] [--max-depth D]"
                  " [--device I] [--assets DIR] [--gpus N] [--progressive K] [--save-scene FILE] [--option NAME=VALUE] [--denoise]\n"
+                 "                  [--noise-target TOL [--min-spp N] [--step-spp N]]\n"
                  "       art_render --info SCENE [--assets DIR]\n";
     return 2;
 }
@@ -44,7 +48,8 @@ int main(int argc, char** argv) try {
     uint64_t seed = 0;
     int max_depth = 50, device = 0, gpus = 0, progressive = -1;
     std::string save_path;
-    bool info = false, denoise = false;
+    bool info = false, denoise = false, noise_target = false;
+    rt_noise_params noise{};
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> std::string {
@@ -53,6 +58,15 @@ int main(int argc, char** argv) try {
         };
         if (a == "--info") info = true;
         else if (a == "--denoise") denoise = true;
+        else if (a == "--noise-target") {
+            const std::string v = next();
+            char* stop = nullptr;
+            noise.rel_tol = std::strtod(v.c_str(), &stop);
+            if (stop == v.c_str() || *stop != '\0' || !(noise.rel_tol > 0)) throw std::invalid_argument("--noise-target wants a tolerance > 0, got '" + v + "'");
+            noise_target = true;
+            noise.dilate = 1;  // measured: without it pixels whose first samples are all black retire too early
+        } else if (a == "--min-spp") noise.min_spp = std::atoi(next().c_str());
+        else if (a == "--step-spp") noise.step_spp = std::atoi(next().c_str());
         else if (a == "--assets") assets = next();
         else if (a == "--mode") mode = next();
         else if (a == "--seed") seed = std::strtoull(next().c_str(), nullptr, 10);
@@ -98,6 +112,9 @@ int main(int argc, char** argv) try {
     std::vector<std::uint8_t> image(static_cast<size_t>(W) * H * 3);
     rt_stats st{};
     if (denoise && (gpus > 0 || progressive >= 0)) throw std::invalid_argument("--denoise renders on one GPU, not with --gpus or --progressive");
+    if (noise_target && (gpus > 0 || progressive >= 0 || denoise))
+        throw std::invalid_argument("--noise-target renders on one GPU, not with --gpus, --progressive or --denoise");
+    if (!noise_target && (noise.min_spp || noise.step_spp)) throw std::invalid_argument("--min-spp and --step-spp belong to --noise-target");
     if (gpus > 0) {  // engine.h:335-376's parallel drivers over GPUs
         if (from_file) throw std::invalid_argument("--gpus builds the scene on every device: give a scene alias");
         std::vector<int> devs;
@@ -117,6 +134,13 @@ int main(int argc, char** argv) try {
             }, progressive);
         } else if (denoise) {
             ms = eng.run_denoised(image.data());
+        } else if (noise_target) {
+            const rt_noise_result r = eng.run_noise_target(image.data(), noise);
+            if (r.rounds < 0) return 1;
+            ms = static_cast<int>(eng.stats().ms);
+            const double npix = static_cast<double>(W) * H;
+            std::cout << "{\"noise_target\":" << noise.rel_tol << ",\"rounds\":" << r.rounds << ",\"mean_spp\":" << r.samples / npix
+                      << ",\"converged_share\":" << r.converged_pixels / npix << ",\"ms\":" << eng.stats().ms << "}" << std::endl;
         } else {
             ms = eng.run(image.data());  // main.cpp:45
         }

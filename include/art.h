@@ -29,6 +29,8 @@
  *                                            mesh.h, bvh.cpp
  *   (none: engine_mode::adaptive interpolates     engine.h:96-333  rt_render_guides + rt_denoise, or rt_render_denoised
  *    untraced pixels; there is no denoiser)                          (first-hit guides, variance-guided a-trous filter)
+ *   (none: tracer_constants::samples_per_pixel is   tracer_constants.h:12  rt_render_noise_target (per-pixel sample counts:
+ *    one compile-time count for every pixel)                          every pixel is traced until its noise target, up to spp)
  *
  * RNG contract: the reference draws from one global std::mt19937 (tracer_utils.h:27-31).  Scene construction here
  * replays that generator exactly (seed 5489, same draw order), so scenes are bit-identical.  Rendering draws come
@@ -56,7 +58,7 @@ extern "C" {
  * ART_MULTI_TIMEOUT_MS); rt_stats.kernel_features / kernel_textures / kernel_lds_mode name the persistent kernel a
  * render ran; rt_multi_create uploads the scene to every device before it returns.
  * Additive since ABI 5 (the version stays 5): rt_render_guides, rt_denoise, rt_render_denoised, rt_denoise_params,
- * RT_GUIDE_DOUBLES, RT_DN_NO_DEMODULATE. */
+ * RT_GUIDE_DOUBLES, RT_DN_NO_DEMODULATE; rt_render_noise_target, rt_noise_params, rt_noise_result. */
 #define RT_ABI_VERSION 5
 
 /* return codes */
@@ -270,6 +272,46 @@ int rt_denoise(int device, const rt_denoise_params* p, const double* accum_a, co
  * the public calls, bit for bit. */
 int rt_render_denoised(rt_scene* scene, const rt_camera* cam, const rt_params* params, const rt_denoise_params* dn, uint8_t* out_rgb8,
                        double* out_color, rt_stats* stats);
+
+/* ---- noise-target rendering (additive since ABI 5; the reference gives every pixel the same sample count) ----
+ * rt_render_noise_target traces every local pixel until the standard error of its mean luminance is within a relative
+ * tolerance, up to params->spp samples (the per-pixel cap).
+ *   1. Base pass: samples [0, min_spp) of every pixel.  Beside the radiance sums two luminance sums are kept per pixel,
+ *      S1 += y and S2 += y*y with y = (0.2126*r + 0.7152*g) + 0.0722*b of each sample, f64, in sample order from +0.
+ *   2. Test after n samples: mean = S1/n; var = (S2 - S1*mean)/(n-1), negative values set to 0; se2 = var/n;
+ *      thr = rel_tol*(mean + lum_floor); converged iff se2 <= thr*thr (+ - * / and comparisons only).
+ *   3. Rounds: a pixel stays active while it was active, has fewer than spp samples and is unconverged -- with dilate = 1,
+ *      while any active pixel of its 3x3 neighbourhood (itself included) is unconverged.  Retirement is final.  Each
+ *      round adds min(step_spp, spp - n) samples to every active pixel, continuing its sums in sample order.
+ *   4. The render ends when no pixel is active or the active ones are at the cap; out_rgb8 is write_color of every
+ *      pixel's sums with its own count.
+ * A pixel that received n samples holds the out_accum and RGB8 that rt_render with spp = n and the same seed gives it,
+ * bit for bit (tests/nt_reference.py restates the test and the active-set rule).  All buffers cover the local rows,
+ * ordered as in rt_render; every one but out_rgb8 may be NULL: out_accum 3 f64 sums, out_count the samples, out_moments
+ * {S1, S2} per pixel; host pointers, or device pointers with RT_OUT_DEVICE.  Honours seed, max_depth, background, stream,
+ * samples_per_pass, the band fields, RT_OUT_DEVICE, RT_GLOBAL_SCENE and RT_PROFILE.  RT_E_INVALID, before any device
+ * work: RT_ADAPTIVE, RT_PARALLEL_IMAGES, RT_WAVEFRONT, RT_SPLIT_SHADE; min_spp < 2 or > spp; step_spp < 1; negative or
+ * non-finite tolerances; dilate outside 0 / 1, or dilate = 1 with band_count > 1 (the neighbourhood would depend on the
+ * partition).  stats as for rt_render: primary = the sum of out_count, segments from the device counter, the kernel
+ * identity of the persistent kernel, passes = path-kernel launches.  result (optional): the refinement rounds run, the
+ * pixels the test retired (a pixel whose test passes exactly when it reaches the cap counts; one stopped by the cap alone
+ * does not) and the samples traced.  Blocking. */
+typedef struct rt_noise_params {   /* zero-initialised = defaults */
+    int32_t min_spp;            /* 0 -> 32; every pixel gets this many (>= 2) */
+    int32_t step_spp;           /* 0 -> 32; samples a refinement round adds to every still-active pixel (>= 1) */
+    int32_t dilate;             /* 0 / 1: 1 also keeps the 3x3 neighbours of an unconverged pixel active (recommended for
+                                   whole frames: a pixel whose first min_spp samples are all equal, e.g. all black under a
+                                   small light, has var == 0 and would retire at once; measured in DESIGN.md 4.6) */
+    double rel_tol;             /* 0 -> 0.05; target relative standard error of the pixel's mean luminance */
+    double lum_floor;           /* 0 -> 0.01; added to the mean before the relative test (dark pixels) */
+} rt_noise_params;
+typedef struct rt_noise_result {
+    int32_t rounds;
+    int64_t converged_pixels;
+    uint64_t samples;
+} rt_noise_result;
+int rt_render_noise_target(rt_scene* scene, const rt_camera* cam, const rt_params* params, const rt_noise_params* noise, uint8_t* out_rgb8,
+                           double* out_accum, int32_t* out_count, double* out_moments, rt_stats* stats, rt_noise_result* result);
 
 /* ---- images (imageio::load_image, imageio.cpp:11-15: stbi_load(path, &w, &h, &c, 0) of stb_image v2.27) ----
  * Decodes a JPEG (baseline or progressive) or PNG file to 8-bit samples, native channel count, row 0 = top, the bytes

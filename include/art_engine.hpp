@@ -202,6 +202,23 @@ public:
         check(rt_render_denoised(world_.objects.get(), &cam_.raw(), &p, dn, out, color, &stats_), "engine::run_denoised");
         return static_cast<int>(stats_.ms);
     }
+    // Noise-target render (rt_render_noise_target; the reference gives every pixel samples_per_pixel samples): every
+    // pixel is traced until the standard error of its mean luminance is within noise.rel_tol, up to spp samples.  `out`
+    // receives write_color of every pixel's sums with its own count, `counts` (optional, W*H) the samples per pixel;
+    // `noise` zero-initialised = the defaults.  single / parallel_stripes only.  Returns the rounds, the converged pixels
+    // and the samples traced (rounds = -1 for an empty world); stats().ms holds the elapsed milliseconds.
+    rt_noise_result run_noise_target(std::uint8_t* out, const rt_noise_params& noise = rt_noise_params{}, std::int32_t* counts = nullptr) {
+        rt_noise_result res{};
+        if (!world_.objects || world_.info.objects == 0) {
+            std::fprintf(stderr, "Invalid input scene!\n");
+            res.rounds = -1;
+            return res;
+        }
+        const rt_params p = params();
+        if (p.flags & (RT_ADAPTIVE | RT_PARALLEL_IMAGES)) throw std::logic_error("engine::run_noise_target: adaptive and parallel_images frames have no noise target");
+        check(rt_render_noise_target(world_.objects.get(), &cam_.raw(), &p, &noise, out, nullptr, counts, nullptr, &stats_, &res), "engine::run_noise_target");
+        return res;
+    }
     const rt_stats& stats() const { return stats_; }
 
 private:
