@@ -21,7 +21,7 @@
 #include "scene.h"
 
 namespace art {
-int device_count();  // kernels.hip
+int device_count();  // renderer.hip
 }
 
 struct rt_scene {

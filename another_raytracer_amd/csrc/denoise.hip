@@ -8,23 +8,14 @@
 // The arithmetic is IEEE f64 + - * / and comparisons in one fixed order (the build's -ffp-contract=off keeps it
 // unfused), with no exp / pow / sqrt before the final write_color: tests/dn_reference.py restates it in numpy and the
 // GPU result equals it bit for bit.
-#include <hip/hip_runtime.h>
-
 #include <map>
 #include <memory>
 #include <mutex>
-#include <stdexcept>
-#include <string>
 #include <utility>
 
 #include "denoise.h"
+#include "hip_check.h"
 #include "options.h"
-
-#define HIP_OK(x)                                                                                         \
-    do {                                                                                                  \
-        hipError_t e_ = (x);                                                                              \
-        if (e_ != hipSuccess) throw std::runtime_error(std::string(#x) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 namespace art {
 namespace {

@@ -583,7 +583,7 @@ __device__ __forceinline__ bool hit_lds_slot(const uint8_t* lds, uint32_t slot, 
                                              double tmin, double tmax, double& t, uint32_t& prim, uint32_t& mt) {
     const double2 a = lds_d2(kLdsOffSph + slot * 16u), b = lds_d2(kLdsOffSph + (kLdsSlotCap + slot) * 16u);
 #if ART_LDS_LEAF_NOREF
-    // k_paths (its own object, kernels_paths.o): the hit is shaded by slot, and its material type is read once after
+    // k_paths (its own object, k_paths.hip): the hit is shaded by slot, and its material type is read once after
     // the trace, so the leaf test skips the per-slot code
     prim = 0;
     mt = kMatUnknown;
@@ -1176,7 +1176,7 @@ __device__ __forceinline__ bool hit_object(const DevScene<R>& S, const uint8_t* 
 
 // Out of line: measured +0.2 % (cow) to +1.8 % (Next-Week final) over the inlined body, which raised the register
 // pressure of the whole path loop for a function most segments do not reach.
-static __device__ __noinline__ double glibc_log_call(double x) { return glibc_log(x); }
+[[maybe_unused]] static __device__ __noinline__ double glibc_log_call(double x) { return glibc_log(x); }
 // get_sphere_uv out of line as well (glibc_trig.h's acos / atan2 are long and run only for image-textured spheres):
 // measured r4z2 the earth scene +3.1 % (its kernel: 166 -> 160 VGPRs, SGPR spills 28 -> 12), the Next-Week final +-0
 [[maybe_unused]] static __device__ __noinline__ UvPair sphere_uv_call(double x, double y, double z, const double* c, const double* t) {

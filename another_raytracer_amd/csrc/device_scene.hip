@@ -1,0 +1,417 @@
+// device_scene.hip — FlatScene -> DeviceScene: the layout.h LDS scene image, the leaf layouts the kernels read and
+// the upload.  Host code only.
+#include "device_scene.h"
+
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <unordered_map>
+
+#include "options.h"
+
+namespace art {
+
+template <class R, class D>
+static void cvt_sphere(const SphereRec<D>& s, SphereRec<R>& o) {
+    for (int a = 0; a < 3; ++a) { o.c[a] = R(s.c[a]); o.d[a] = R(s.d[a]); }
+    o.r = R(s.r); o.t0 = R(s.t0); o.dt = R(s.dt); o.mat = s.mat; o.flags = s.flags;
+}
+
+// Builds the layout.h LDS scene image when the f64 scene qualifies: spheres only, every BVH node and leaf slot within
+// the plane capacities, and image + stack within one CU's LDS.  Returns an empty vector otherwise.
+static std::vector<uint8_t> lds_scene_image(const FlatScene& f, uint32_t& nmov, bool& shade_ok) {
+    std::vector<uint8_t> img;
+    nmov = 0;
+    shade_ok = false;
+    if ((f.features & ~kFeatSpheres) != 0 || f.nodes.empty() || f.nodes.size() > kLdsNodeCap || f.primrefs.size() > kLdsSlotCap ||
+        f.world.size() > kPathsWorldCap || f.objs.size() > kPathsWorldCap ||
+        f.spheres.size() > kLdsRefIndexMask || std::max(extend_lds_bytes(true, stack_rows(f.max_stack)), paths_lds_bytes(stack_rows(f.max_stack))) > kLdsPerCu)
+        return img;
+    // k_paths shades a hit by its LDS leaf slot: every world object must be a BVH over the image's slots (a loose
+    // OBJ_PRIM object, e.g. with option compile.world_merge = 0 or from a flat-scene file, takes the HBM kernels)
+    for (int32_t w : f.world)
+        if (w < 0 || static_cast<size_t>(w) >= f.objs.size() || f.objs[w].kind != OBJ_BVH) return img;
+    for (uint32_t ref : f.primrefs) {
+        if (primref_type(ref) != PRIM_SPHERE) return img;
+        const SphereRec<double>& sp = f.spheres[primref_index(ref)];
+        if (sp.flags & SPH_MOVING) {
+            // the image's moving spheres span the unit shutter (every moving_sphere of the reference scenes,
+            // scene_manager.cpp:34-35, :201): their centre fraction is the ray time itself (hit_lds_slot); and they
+            // move along y only (scene_manager.cpp:33): the image keeps one dy per leaf slot (layout.h)
+            if (sp.t0 != 0.0 || sp.dt != 1.0 || sp.d[0] != 0.0 || sp.d[2] != 0.0) return img;
+            ++nmov;
+        }
+    }
+    if (nmov > kLdsMovCap) return img;
+    for (const BvhNode& b : f.nodes)
+        for (int c = 0; c < 4; ++c)
+            if (b.child[c] < 0 && b.child[c] != kNodeEmpty && leaf_count(b.child[c]) > kLdsLeafMaxCount) return img;
+    img.assign(kLdsImageBytes, 0);
+    auto put = [&](uint32_t off, const void* v, size_t n) { std::memcpy(img.data() + off, v, n); };
+    for (size_t n = 0; n < f.nodes.size(); ++n) {
+        const BvhNode& b = f.nodes[n];
+        float planes[6][4];
+        const float* src[6] = {b.lox, b.hix, b.loy, b.hiy, b.loz, b.hiz};
+        int32_t child[4];
+        for (int c = 0; c < 4; ++c) {
+            // an empty slot becomes an empty leaf behind a point box at (3e38, 3e38, 3e38): no slab test of it needs
+            // a child check, and the astronomically rare ray whose three slab times coincide there finds no primitives
+            const bool empty = b.child[c] == kNodeEmpty;
+            for (int j = 0; j < 6; ++j) planes[j][c] = empty ? kLdsEmptyBox : src[j][c];
+            // inner nodes by their byte offset in a plane (index * 16: device.h traverse), leaves as lds_leaf codes
+            child[c] = empty ? kLdsEmptyChild : b.child[c] >= 0 ? b.child[c] * 16 : lds_leaf(leaf_first(b.child[c]), leaf_count(b.child[c]));
+        }
+        // per axis: lo, hi, lo (layout.h kLdsNodePlanes), then the child codes as int16
+        const int order[9] = {0, 1, 0, 2, 3, 2, 4, 5, 4};
+        const uint32_t nn = static_cast<uint32_t>(n);
+        for (uint32_t j = 0; j < 9; ++j) put(kLdsOffNodes + (j * kLdsNodeCap + nn) * 16, planes[order[j]], 16);
+        const int16_t c16[8] = {static_cast<int16_t>(child[0]), static_cast<int16_t>(child[1]), static_cast<int16_t>(child[2]),
+                                static_cast<int16_t>(child[3]), 0, 0, 0, 0};
+        put(kLdsOffNodes + (kLdsNodePlaneChild * kLdsNodeCap + nn) * 16, c16, 16);
+    }
+    // shading table: one entry per material (two for a checker of solid colours); anything else keeps the scene off
+    // the fused variant (shade_ok = false), which shades from the global scene records instead
+    std::vector<int32_t> entry(f.mats.size(), -1);
+    uint32_t nent = 0;
+    shade_ok = true;
+    auto put_entry = [&](const double c[3], double param) {
+        const double v[4] = {c[0], c[1], c[2], param};
+        if (nent < kLdsMatCap) put(kLdsOffMat + nent * 32, v, 32);
+        return nent++;
+    };
+    auto solid = [&](int32_t t) { return t >= 0 && static_cast<size_t>(t) < f.texs.size() && f.texs[t].type == TEX_SOLID; };
+    uint32_t m = 0;
+    for (size_t slot = 0; slot < f.primrefs.size(); ++slot) {
+        const uint32_t idx = primref_index(f.primrefs[slot]);
+        const auto& sp = f.spheres[idx];
+        // a moving sphere's x and z at time tm are c + tm * (+-0) (moving_sphere.h:72-74) == c + d: the image stores
+        // that value (it differs from c only for c = -0 and d = +0), and the device adds tm * dy to y alone
+        const bool moving = (sp.flags & SPH_MOVING) != 0;
+        const double cx = moving ? sp.c[0] + sp.d[0] : sp.c[0], cz = moving ? sp.c[2] + sp.d[2] : sp.c[2];
+        const double p0[2] = {cx, sp.c[1]}, p1[2] = {cz, sp.r * sp.r}, inv_r = 1.0 / sp.r;
+        const uint32_t sl = static_cast<uint32_t>(slot);
+        put(kLdsOffSph + sl * 16, p0, 16);
+        put(kLdsOffSph + (kLdsSlotCap + sl) * 16, p1, 16);
+        put(kLdsOffInvR + sl * 8, &inv_r, 8);
+        uint32_t code = idx | (f.mats[sp.mat].type << kLdsRefMatShift);
+        const double dy = moving ? sp.d[1] : -0.0;
+        put(kLdsOffMov + sl * 8, &dy, 8);
+        if (moving) {
+            code |= (m + 1) << kLdsRefMovShift;
+            ++m;
+        }
+        put(kLdsOffRef + sl * 4, &code, 4);
+        const auto& mat = f.mats[sp.mat];
+        if (entry[sp.mat] < 0) {
+            if (mat.type == MAT_LAMBERTIAN || mat.type == MAT_LIGHT) {
+                const auto& t = f.texs[mat.tex];
+                if (t.type == TEX_SOLID) {
+                    entry[sp.mat] = static_cast<int32_t>(put_entry(t.c, 0.0));
+                } else if (t.type == TEX_CHECKER && solid(t.even) && solid(t.odd)) {
+                    entry[sp.mat] = static_cast<int32_t>(put_entry(f.texs[t.even].c, 0.0)) | static_cast<int32_t>(kLdsMatChecker);
+                    put_entry(f.texs[t.odd].c, 0.0);
+                } else {
+                    shade_ok = false;
+                }
+            } else if (mat.type == MAT_METAL) {
+                entry[sp.mat] = static_cast<int32_t>(put_entry(mat.albedo, mat.fuzz));
+            } else if (mat.type == MAT_DIELECTRIC) {
+                // dielectric (material.h:63-99): 1 / ir, and reflectance()'s r0 = ((1 - ratio) / (1 + ratio))^2 for
+                // both faces, in the device's IEEE double arithmetic (-ffp-contract=off), then ir
+                const double inv = 1.0 / mat.ir;
+                double r0f = (1.0 - inv) / (1.0 + inv), r0b = (1.0 - mat.ir) / (1.0 + mat.ir);
+                r0f = r0f * r0f;
+                r0b = r0b * r0b;
+                const double d3[3] = {inv, r0f, r0b};
+                entry[sp.mat] = static_cast<int32_t>(put_entry(d3, mat.ir));
+            } else {
+                shade_ok = false;
+            }
+        }
+        const uint16_t mi = static_cast<uint16_t>(entry[sp.mat] < 0 ? 0 : entry[sp.mat]);
+        put(kLdsOffMatIdx + sl * 2, &mi, 2);
+    }
+    if (nent > kLdsMatCap) shade_ok = false;
+    return img;
+}
+
+
+// The 16-bit child codes (layout.h make_leaf16) of a BVH whose leaves start past slot 8191 (more than 8192 primitive
+// references: the capsule's 10 200 triangles) do not fit; with every leaf moved to an even slot of a padded copy of
+// the primitive references they do, as first / 2 (F_LEAF2).  Rewrites the device copies of the leaf codes (nodes and
+// hoisted leaves) and returns the padded references (pad[i]: slot i belongs to no leaf, its records stay zero), or
+// an empty vector when the leaves overlap or the padded codes still do not fit.  A leaf tests the same primitives in
+// the same order, so every closest hit, and the image, is unchanged.
+static std::vector<uint32_t> pair_align_leaves(const std::vector<uint32_t>& primrefs, std::vector<BvhNode>& nodes,
+                                               std::vector<ObjRec<double>>& objs, std::vector<uint8_t>& pad) {
+    std::vector<std::pair<uint32_t, uint32_t>> leaves;  // (first, count)
+    for (const BvhNode& b : nodes)
+        for (int c = 0; c < 4; ++c)
+            if (b.child[c] < 0 && b.child[c] != kNodeEmpty) leaves.emplace_back(leaf_first(b.child[c]), leaf_count(b.child[c]));
+    for (const auto& o : objs)
+        if (o.kind == OBJ_BVH && o.b != kNodeEmpty) leaves.emplace_back(leaf_first(o.b), leaf_count(o.b));
+    std::sort(leaves.begin(), leaves.end());
+    leaves.erase(std::unique(leaves.begin(), leaves.end()), leaves.end());
+    std::unordered_map<uint32_t, uint32_t> moved;  // old first -> new first
+    std::vector<uint32_t> out;
+    pad.clear();
+    uint32_t next = 0;  // first old slot not yet copied
+    for (const auto& lf : leaves) {
+        if (lf.first < next || lf.second < 1 || lf.second > 4 || lf.first + lf.second > primrefs.size()) return {};
+        for (; next < lf.first; ++next) {  // slots outside every leaf keep their order
+            out.push_back(primrefs[next]);
+            pad.push_back(0);
+        }
+        if (out.size() & 1u) {
+            out.push_back(0u);
+            pad.push_back(1);
+        }
+        moved[lf.first] = static_cast<uint32_t>(out.size());
+        if (!leaf16_ok(static_cast<uint32_t>(out.size()) >> 1, lf.second)) return {};
+        for (uint32_t k = 0; k < lf.second; ++k) {
+            out.push_back(primrefs[lf.first + k]);
+            pad.push_back(0);
+        }
+        next = lf.first + lf.second;
+    }
+    for (; next < primrefs.size(); ++next) {
+        out.push_back(primrefs[next]);
+        pad.push_back(0);
+    }
+    auto remap = [&](int32_t c) { return make_leaf(moved.at(leaf_first(c)), leaf_count(c)); };
+    for (BvhNode& b : nodes)
+        for (int c = 0; c < 4; ++c)
+            if (b.child[c] < 0 && b.child[c] != kNodeEmpty) b.child[c] = remap(b.child[c]);
+    for (auto& o : objs)
+        if (o.kind == OBJ_BVH && o.b != kNodeEmpty) o.b = remap(o.b);
+    return out;
+}
+
+template <class R>
+void build_device_scene(const FlatScene& f0, DeviceScene<R>& ds) {
+    // the device copy of the BVH arrays, with leaves pair-aligned where 16-bit codes need it (pair_align_leaves)
+    FlatScene f = f0;
+    std::vector<uint8_t> slot_pad(f.primrefs.size(), 0);
+    {
+        bool fit = f.nodes.size() <= 32768u;
+        for (const BvhNode& b : f.nodes)
+            for (int c = 0; c < 4; ++c)
+                if (b.child[c] < 0 && b.child[c] != kNodeEmpty) fit = fit && leaf16_ok(leaf_first(b.child[c]), leaf_count(b.child[c]));
+        for (const auto& o : f.objs)
+            if (o.kind == OBJ_BVH && o.b != kNodeEmpty) fit = fit && leaf16_ok(leaf_first(o.b), leaf_count(o.b));
+        ds.leaf_shift = 0;
+        // only where an F_LEAF2 kernel exists (mesh feature sets with triangles: launch_paths_g); other kernels decode
+        // 16-bit leaves unshifted
+        const bool mesh = (f.features & ~kFeatMesh) == 0 && (f.features & F_TRI) != 0;
+        if (!fit && mesh && f.nodes.size() <= 32768u && opt(Opt::Leaf2) != 0) {
+            std::vector<BvhNode> nodes = f.nodes;
+            std::vector<ObjRec<double>> objs = f.objs;
+            std::vector<uint8_t> pad;
+            std::vector<uint32_t> refs = pair_align_leaves(f.primrefs, nodes, objs, pad);
+            if (!refs.empty()) {
+                f.primrefs = std::move(refs);
+                f.nodes = std::move(nodes);
+                f.objs = std::move(objs);
+                slot_pad = std::move(pad);
+                ds.leaf_shift = 1;
+            }
+        }
+    }
+    std::vector<SphereRec<R>> sph(f.spheres.size());
+    for (size_t i = 0; i < sph.size(); ++i) cvt_sphere(f.spheres[i], sph[i]);
+    std::vector<TriRec<R>> tri(f.tris.size());
+    for (size_t i = 0; i < tri.size(); ++i) {
+        for (int a = 0; a < 9; ++a) tri[i].p[a] = R(f.tris[i].p[a]);
+        tri[i].mat = f.tris[i].mat;
+        tri[i].pad = 0;
+    }
+    std::vector<RectRec<R>> rect(f.rects.size());
+    for (size_t i = 0; i < rect.size(); ++i) {
+        const auto& s = f.rects[i];
+        rect[i] = RectRec<R>{R(s.a0), R(s.a1), R(s.b0), R(s.b1), R(s.k), s.axis, s.mat};
+    }
+    std::vector<BoxRec<R>> box(f.boxes.size());
+    for (size_t i = 0; i < box.size(); ++i) {
+        for (int a = 0; a < 3; ++a) { box[i].mn[a] = R(f.boxes[i].mn[a]); box[i].mx[a] = R(f.boxes[i].mx[a]); }
+        box[i].mat = f.boxes[i].mat;
+        box[i].pad = 0;
+    }
+    std::vector<ObjRec<R>> objs(f.objs.size());
+    for (size_t i = 0; i < objs.size(); ++i) {
+        objs[i].kind = f.objs[i].kind; objs[i].a = f.objs[i].a; objs[i].b = f.objs[i].b; objs[i].pad = 0;
+        for (int a = 0; a < 4; ++a) objs[i].p[a] = R(f.objs[i].p[a]);
+    }
+    std::vector<MatRec<R>> mats(f.mats.size());
+    for (size_t i = 0; i < mats.size(); ++i) {
+        mats[i].type = f.mats[i].type; mats[i].tex = f.mats[i].tex; mats[i].flags = f.mats[i].flags; mats[i].pad = 0;
+        for (int a = 0; a < 3; ++a) mats[i].albedo[a] = R(f.mats[i].albedo[a]);
+        mats[i].fuzz = R(f.mats[i].fuzz); mats[i].ir = R(f.mats[i].ir);
+        mats[i].flags &= ~static_cast<uint32_t>(MATF_SOLID);
+        const int32_t t = f.mats[i].tex;
+        const uint32_t ty = f.mats[i].type;
+        if ((ty == MAT_LAMBERTIAN || ty == MAT_LIGHT || ty == MAT_ISOTROPIC) && t >= 0 && static_cast<size_t>(t) < f.texs.size() &&
+            f.texs[t].type == TEX_SOLID) {
+            // the solid colour itself: tex_value's ld3(t.c), the same doubles
+            for (int a = 0; a < 3; ++a) mats[i].albedo[a] = R(f.texs[t].c[a]);
+            mats[i].flags |= MATF_SOLID;
+        }
+    }
+    std::vector<TexRec<R>> texs(f.texs.size());
+    for (size_t i = 0; i < texs.size(); ++i) {
+        const auto& s = f.texs[i];
+        texs[i].type = s.type; texs[i].even = s.even; texs[i].odd = s.odd; texs[i].perlin = s.perlin; texs[i].image = s.image; texs[i].pad = 0;
+        for (int a = 0; a < 3; ++a) texs[i].c[a] = R(s.c[a]);
+        texs[i].scale = R(s.scale);
+        for (int a = 0; a < 6; ++a) texs[i].uv[a] = R(s.uv[a]);
+    }
+    std::vector<PerlinRec<R>> per(f.perlins.size());
+    for (size_t i = 0; i < per.size(); ++i) {
+        for (int v = 0; v < 256; ++v) for (int a = 0; a < 3; ++a) per[i].ranvec[v][a] = R(f.perlins[i].ranvec[v][a]);
+        std::memcpy(per[i].perm, f.perlins[i].perm, sizeof per[i].perm);
+    }
+    ds.view.spheres = ds.upload(sph);
+    ds.view.tris = ds.upload(tri);
+    ds.view.rects = ds.upload(rect);
+    ds.view.boxes = ds.upload(box);
+    ds.view.primrefs = ds.upload(f.primrefs);
+    {  // every scene with a BVH: any kernel instantiated with triangles reads it, whatever the scene holds
+        std::vector<TriRec<R>> lt(f.primrefs.size());
+        for (size_t i = 0; i < lt.size(); ++i)
+            if (!slot_pad[i] && primref_type(f.primrefs[i]) == PRIM_TRIANGLE) lt[i] = tri[primref_index(f.primrefs[i])];
+        ds.view.leaf_tris = ds.upload(lt);
+        if constexpr (std::is_same<R, double>::value) {
+            // TriRec112: the plane of each leaf triangle by the device's operations in its order (device.h cross, dot;
+            // -ffp-contract=off on both sides): n = cross(p2 - p1, p3 - p1), dd = -dot(n, p1), bit for bit
+            std::vector<TriRec112<R>> l112(lt.size());
+            for (size_t i = 0; i < lt.size(); ++i) {
+                const R* q = lt[i].p;
+                const R ux = q[3] - q[0], uy = q[4] - q[1], uz = q[5] - q[2];
+                const R vx = q[6] - q[0], vy = q[7] - q[1], vz = q[8] - q[2];
+                const R nx = uy * vz - uz * vy, ny = uz * vx - ux * vz, nz = ux * vy - uy * vx;
+                for (int k = 0; k < 9; ++k) l112[i].p[k] = q[k];
+                l112[i].n[0] = nx;
+                l112[i].n[1] = ny;
+                l112[i].n[2] = nz;
+                l112[i].dd = -(nx * q[0] + ny * q[1] + nz * q[2]);
+                l112[i].mat = lt[i].mat;
+                l112[i].pad = 0;
+            }
+            ds.view.leaf_tris112 = ds.upload(l112);
+        }
+        std::vector<PrimRec80> lp(f.primrefs.size());  // every primitive type in leaf order (triangle-free kernels)
+        for (size_t i = 0; i < lp.size(); ++i) {
+            if (slot_pad[i]) continue;
+            const uint32_t ref = f.primrefs[i], idx = primref_index(ref);
+            switch (primref_type(ref)) {
+                case PRIM_SPHERE: std::memcpy(lp[i].b, &sph[idx], sizeof(sph[idx])); break;
+                case PRIM_TRIANGLE: std::memcpy(lp[i].b, &tri[idx], sizeof(tri[idx])); break;
+                case PRIM_RECT: std::memcpy(lp[i].b, &rect[idx], sizeof(rect[idx])); break;
+                default: std::memcpy(lp[i].b, &box[idx], sizeof(box[idx])); break;
+            }
+        }
+        ds.view.leaf_prims = ds.upload(lp);
+    }
+    {  // BvhNode::pad: the 16-bit child codes (layout.h make_leaf16), derived here from the 32-bit ones (never read
+       // from a scene file); codes16 when every inner index, leaf and hoisted leaf fits them
+        std::vector<BvhNode> nodes = f.nodes;
+        bool ok = nodes.size() <= 32768u;
+        for (BvhNode& b : nodes) {
+            int32_t c16[4];
+            for (int c = 0; c < 4; ++c) {
+                const int32_t x = b.child[c];
+                if (x >= 0) {
+                    c16[c] = x;
+                } else if (x == kNodeEmpty) {
+                    c16[c] = kNodeEmpty;
+                } else {
+                    ok = ok && leaf16_ok(leaf_first(x) >> ds.leaf_shift, leaf_count(x));
+                    c16[c] = ok ? make_leaf16(leaf_first(x) >> ds.leaf_shift, leaf_count(x)) : kNodeEmpty;
+                }
+            }
+            b.pad[0] = static_cast<int32_t>((static_cast<uint32_t>(c16[1]) << 16) | (static_cast<uint32_t>(c16[0]) & 0xFFFFu));
+            b.pad[1] = static_cast<int32_t>((static_cast<uint32_t>(c16[3]) << 16) | (static_cast<uint32_t>(c16[2]) & 0xFFFFu));
+            b.pad[2] = b.pad[3] = 0;
+        }
+        for (const auto& o : f.objs)
+            if (o.kind == OBJ_BVH && o.b != kNodeEmpty) ok = ok && leaf16_ok(leaf_first(o.b) >> ds.leaf_shift, leaf_count(o.b));
+        // option render.codes16 = 0 (read per upload; tests): take the 32-bit-code kernels as a scene whose codes do
+        // not fit would (a parity probe of that path on scenes that fit)
+        if (opt(Opt::Codes16) == 0) ok = false;
+        ds.codes16 = ok;
+        if (!ok) ds.leaf_shift = 0;  // the 32-bit codes (child[]) address the padded slots directly
+        ds.view.nodes = ds.upload(nodes);
+    }
+    ds.view.objs = ds.upload(objs);
+    {  // obj_prims[o]: prim object o's primitive record (device.h hit_object)
+        std::vector<PrimRec80> op(objs.size());
+        for (size_t i = 0; i < objs.size(); ++i) {
+            if (objs[i].kind != OBJ_PRIM) continue;
+            const uint32_t ref = static_cast<uint32_t>(objs[i].a), idx = primref_index(ref);
+            switch (primref_type(ref)) {
+                case PRIM_SPHERE: std::memcpy(op[i].b, &sph[idx], sizeof(sph[idx])); break;
+                case PRIM_TRIANGLE: std::memcpy(op[i].b, &tri[idx], sizeof(tri[idx])); break;
+                case PRIM_RECT: std::memcpy(op[i].b, &rect[idx], sizeof(rect[idx])); break;
+                default: std::memcpy(op[i].b, &box[idx], sizeof(box[idx])); break;
+            }
+        }
+        static_assert(sizeof(SphereRec<R>) <= sizeof(PrimRec80) && sizeof(TriRec<R>) <= sizeof(PrimRec80) &&
+                      sizeof(RectRec<R>) <= sizeof(PrimRec80) && sizeof(BoxRec<R>) <= sizeof(PrimRec80), "PrimRec80 holds every record");
+        ds.view.obj_prims = ds.upload(op);
+    }
+    ds.view.world = ds.upload(f.world);
+    ds.view.mats = ds.upload(mats);
+    ds.view.texs = ds.upload(texs);
+    ds.view.perlins = ds.upload(per);
+    {  // [sphere_uv.h's table][image records]: device.h uv_table reads the table in front of DevScene::images
+        std::vector<uint8_t> ib(kUvTableBytes + sizeof(ImageRec) * f.images.size(), 0);
+        std::memcpy(ib.data(), glibc_trig_data::kTrigHost, sizeof(glibc_trig_data::kTrigHost));
+        if (!f.images.empty()) std::memcpy(ib.data() + kUvTableBytes, f.images.data(), sizeof(ImageRec) * f.images.size());
+        ds.view.images = reinterpret_cast<const ImageRec*>(ds.upload(ib) + kUvTableBytes);
+    }
+    ds.view.texels = ds.upload(f.texels);
+    if (std::is_same<R, double>::value) {
+        uint32_t nmov = 0;
+        bool shade_ok = false;
+        const std::vector<uint8_t> img = ds.leaf_shift ? std::vector<uint8_t>() : lds_scene_image(f, nmov, shade_ok);
+        if (!img.empty()) {
+            ds.view.lds_image = ds.upload(img);
+            ds.lds_scene = true;
+            ds.lds_shade = shade_ok;
+        }
+    }
+    ds.view.n_nodes = static_cast<uint32_t>(f.nodes.size());
+    ds.view.n_objs = static_cast<uint32_t>(f.objs.size());
+    ds.view.n_mats = static_cast<uint32_t>(f.mats.size());
+    ds.view.n_primrefs = static_cast<uint32_t>(f.primrefs.size());
+    ds.view.n_tris = static_cast<uint32_t>(f.tris.size());
+    ds.view.nworld = static_cast<int32_t>(f.world.size());
+    for (int a = 0; a < 3; ++a) ds.view.bg[a] = R(f.background[a]);
+    ds.media = f.has_media;
+    ds.features = f.features;
+    ds.max_stack = f.max_stack;
+    ds.tex_basic = true;
+    for (const auto& t : f.texs) ds.tex_basic = ds.tex_basic && (t.type == TEX_SOLID || t.type == TEX_CHECKER);
+    {  // TF_BARY: the texture trees the materials reach hold only solid, checker and barycentric-image nodes (a
+       // mesh's bary_image refers to its image texture, which no material samples directly), and no primitive but a
+       // triangle samples u, v
+        bool bary = !ds.tex_basic;
+        std::function<bool(int32_t, int)> tree_ok = [&](int32_t t, int depth) -> bool {
+            if (t < 0 || static_cast<size_t>(t) >= f.texs.size()) return true;
+            const uint32_t ty = f.texs[t].type;
+            if (ty == TEX_SOLID || ty == TEX_BARY_IMAGE) return true;
+            return ty == TEX_CHECKER && depth < 4 && tree_ok(f.texs[t].even, depth + 1) && tree_ok(f.texs[t].odd, depth + 1);
+        };
+        for (const auto& m : f.mats)
+            if (m.type == MAT_LAMBERTIAN || m.type == MAT_LIGHT || m.type == MAT_ISOTROPIC) bary = bary && tree_ok(m.tex, 0);
+        auto needs_uv = [&](uint32_t m) { return m < f.mats.size() && (f.mats[m].flags & MATF_NEEDS_UV) != 0; };
+        for (const auto& p : f.spheres) bary = bary && !needs_uv(p.mat);
+        for (const auto& p : f.rects) bary = bary && !needs_uv(p.mat);
+        for (const auto& p : f.boxes) bary = bary && !needs_uv(p.mat);
+        ds.tex_bary = bary && opt(Opt::TexBary) != 0;
+    }
+    ds.mat_types = 0;
+    for (const auto& m : f.mats) ds.mat_types |= 1u << m.type;
+}
+template void build_device_scene<double>(const FlatScene&, DeviceScene<double>&);
+
+}  // namespace art

@@ -1,0 +1,46 @@
+// launch.h — the host launchers the objects share.  The library is built without relocatable device code: a kernel
+// lives in one object, and so does every host function that takes its address (hipLaunchKernelGGL, blocks_per_cu,
+// static_lds_is_zero).  renderer.hip has no kernel of its own and launches through these.
+#pragma once
+#include <functional>
+
+#include "device_scene.h"
+#include "path_work.h"
+
+namespace art {
+
+// Extend variant: 0 = HBM scene, 1 = LDS scene, 2 = LDS scene with fused shading (no k_shade launches), 3 = persistent
+// paths (k_paths: the fused LDS bounce loop in registers, one launch per pass), 4 = persistent paths over the HBM scene (k_paths_g).
+enum ExtendVariant { EXT_GLOBAL = 0, EXT_LDS = 1, EXT_FUSED = 2, EXT_MEGA = 3, EXT_MEGA_G = 4 };
+// The variant for this scene and these flags (RT_GLOBAL_SCENE / RT_SPLIT_SHADE / RT_WAVEFRONT force the general kernels).
+int extend_variant(const DeviceScene<double>& ds, int flags);
+// Which persistent-path kernel a render ran (rt_stats.kernel_*): k_paths_g<F, TF, LM>, or k_paths as LM 3
+struct KernelId {
+    uint32_t f = 0, tf = 0;
+    int lm = -1;
+};
+
+// kernels.hip
+bool static_lds_is_zero(const void* kernel);
+int blocks_per_cu(const void* kernel, int block, size_t lds);
+KernelId launch_paths_g(uint32_t feat, bool tex_basic, bool tex_bary, bool codes16, uint32_t leaf_shift, int num_cu, hipStream_t st,
+                        const DevScene<double>& S, const PassGeom& g, const CameraRec<double>& cam, const Work<double>& w, uint32_t* next_slot);
+void bounce(const DeviceScene<double>& ds, int variant, int num_cu, hipStream_t st, const PassGeom& g, const CameraRec<double>& cam,
+            const Work<double>& w, int d, const std::function<void()>& mark);
+void launch_accum(hipStream_t st, const PassGeom& g, const Work<double>& w, double* qsum, uint32_t m);  // qsum: k_accum_images, or null
+void launch_finalize(hipStream_t st, const double* acc, uint8_t* rgb, uint32_t n, int spp);
+void launch_adapt_corners(hipStream_t st, uint32_t* list, int W, int sqx, uint32_t nsq);
+void launch_adapt_store(hipStream_t st, const uint32_t* list, uint32_t n, const double* acc, int spp, int32_t* work);
+void launch_adapt_accum(hipStream_t st, const uint32_t* list, uint32_t cap, const ResRec<double>* res, uint32_t k, int spp, int32_t* work);
+void launch_adapt_level(hipStream_t st, int level, int32_t* work, int W, int sqx, uint32_t nsq, uint8_t* f0, uint8_t* f1, uint8_t* f2, uint32_t* list,
+                        uint32_t* count);
+void launch_adapt_fill(hipStream_t st, int32_t* work, uint8_t* rgb, int W, int rows, int sqx, const uint8_t* f0, const uint8_t* f1, const uint8_t* f2);
+void launch_trace_rays(const DeviceScene<double>& ds, bool global_scene, hipStream_t st, const double* rays, uint32_t n, double* t_out, double* n_out);
+void launch_guides(const DeviceScene<double>& ds, int flags, hipStream_t st, const GuideGeom& g, const CameraRec<double>& cam, double* guides,
+                   double* rays);
+// k_paths.hip
+void launch_paths(int num_cu, hipStream_t st, const DevScene<double>& S, const PassGeom& g, const CameraRec<double>& cam, const Work<double>& w,
+                  uint32_t* next_slot);
+size_t pool_bytes(int variant, int num_cu);  // the camera-ray pool of `variant` (k_paths' rings; 0 for every other)
+
+}  // namespace art

@@ -244,7 +244,7 @@ struct CameraRec {       // camera.h: precomputed on the host in f64 exactly as 
 // Row-interleaved bands (the multi-GPU split; ancestor: _run_parallel_stripes' 4 contiguous stripes, engine.h:335-376):
 // global row y belongs to band y / band_rows, rendered by band set (y / band_rows) % n.  Local row ly of band set r
 // is global row band_global_row(ly, ...); band set r owns band_local_rows(H, ...) rows.  One rule for the kernels
-// (kernels.hip global_row), rt_local_rows, the RCCL gather's block size and the unpack (multi.hip).
+// (path_work.h global_row), rt_local_rows, the RCCL gather's block size and the unpack (multi.hip).
 ART_HD int band_global_row(int ly, int band_rows, int n, int r) {
     return (ly / band_rows) * (band_rows * n) + r * band_rows + (ly % band_rows);
 }

@@ -14,16 +14,12 @@
 #include <thread>
 #include <vector>
 
+#include "hip_check.h"
 #include "multi.h"
 #include "options.h"
 
 namespace art {
 
-#define HIP_CHECK(x)                                                                                      \
-    do {                                                                                                  \
-        hipError_t e_ = (x);                                                                              \
-        if (e_ != hipSuccess) throw std::runtime_error(std::string(#x) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 #define RCCL_CHECK(x)                                                                                        \
     do {                                                                                                     \
         ncclResult_t r_ = (x);                                                                               \
@@ -55,7 +51,7 @@ static void launch_unpack(const uint8_t* recv, uint8_t* frame, int W, int H, int
     const int wide = (row_bytes % 16 == 0 && reinterpret_cast<uintptr_t>(recv) % 16 == 0 && reinterpret_cast<uintptr_t>(frame) % 16 == 0);
     hipLaunchKernelGGL(k_unpack_bands, dim3(static_cast<unsigned>(n * max_rows)), dim3(256), 0, stream, recv, frame, W, H, band_rows, n,
                        max_rows, wide);
-    HIP_CHECK(hipGetLastError());
+    HIP_OK(hipGetLastError());
 }
 
 void unpack_bands(const uint8_t* recv, uint8_t* frame, int W, int H, int band_rows, int n, bool device, void* stream) {
@@ -79,15 +75,15 @@ struct DeviceBuf {
     size_t bytes = 0;
     void ensure(size_t want) {
         if (want <= bytes) return;
-        HIP_CHECK(hipSetDevice(device));
+        HIP_OK(hipSetDevice(device));
         if (p) {
             void* old = p;
             p = nullptr;
             bytes = 0;
-            HIP_CHECK(hipFree(old));
+            HIP_OK(hipFree(old));
         }
         void* q = nullptr;
-        HIP_CHECK(hipMalloc(&q, want));
+        HIP_OK(hipMalloc(&q, want));
         p = q;
         bytes = want;
     }
@@ -215,7 +211,7 @@ struct MultiRenderer::Impl {
             bool all = true;
             for (size_t k = 0; k < streams.size(); ++k) {
                 if (done[k]) continue;
-                HIP_CHECK(hipSetDevice(devices[k]));
+                HIP_OK(hipSetDevice(devices[k]));
                 const hipError_t q = hipStreamQuery(streams[k]);
                 if (q == hipSuccess) {
                     done[k] = true;
@@ -238,7 +234,7 @@ MultiRenderer::MultiRenderer(const FlatScene& flat, const std::vector<int>& devi
     std::unique_ptr<Impl> guard(impl_);
     if (devices.empty()) throw std::runtime_error("rt_multi needs at least one device");
     int count = 0;
-    HIP_CHECK(hipGetDeviceCount(&count));
+    HIP_OK(hipGetDeviceCount(&count));
     for (size_t a = 0; a < devices.size(); ++a) {
         if (devices[a] < 0 || devices[a] >= count) throw std::runtime_error("device " + std::to_string(devices[a]) + " does not exist");
         for (size_t b = 0; b < a; ++b)
@@ -255,12 +251,12 @@ MultiRenderer::MultiRenderer(const FlatScene& flat, const std::vector<int>& devi
     impl_->streams.assign(n, nullptr);
     impl_->send.resize(n);
     for (int k = 0; k < n; ++k) {
-        HIP_CHECK(hipSetDevice(devices[k]));
-        HIP_CHECK(hipStreamCreateWithFlags(&impl_->streams[k], hipStreamNonBlocking));
+        HIP_OK(hipSetDevice(devices[k]));
+        HIP_OK(hipStreamCreateWithFlags(&impl_->streams[k], hipStreamNonBlocking));
         impl_->send[k].device = devices[k];
     }
-    HIP_CHECK(hipSetDevice(devices[0]));
-    for (auto& e : impl_->ev) HIP_CHECK(hipEventCreate(&e));
+    HIP_OK(hipSetDevice(devices[0]));
+    for (auto& e : impl_->ev) HIP_OK(hipEventCreate(&e));
     impl_->recv.device = impl_->frame.device = devices[0];
     // one communicator per device, rank k = devices[k], created as one group (what ncclCommInitAll does) but
     // non-blocking, so that a stuck bootstrap ends at the deadline instead of hanging the caller
@@ -273,7 +269,7 @@ MultiRenderer::MultiRenderer(const FlatScene& flat, const std::vector<int>& devi
     try {
         RcclGroup group;
         for (int k = 0; k < n; ++k) {
-            HIP_CHECK(hipSetDevice(devices[k]));
+            HIP_OK(hipSetDevice(devices[k]));
             RCCL_ISSUE(ncclCommInitRankConfig(&impl_->comms[k], n, id, k, &cfg));
             if (k == n - 1 && opt(Opt::FaultRcclGroup) == 1)  // fault point (tests): an error inside the init group
                 throw std::runtime_error("ncclCommInitRankConfig: injected failure (test.fault_rccl_group = 1)");
@@ -352,12 +348,12 @@ void MultiRenderer::render(const CameraRec<double>& cam, const RenderParams& p, 
     }
     // phase 2: one gather of the equal-sized packed blocks to devices[0] (rows past a band's end are padding)
     const auto deadline = deadline_from_now();
-    HIP_CHECK(hipSetDevice(I.devices[0]));
-    HIP_CHECK(hipEventRecord(I.ev[0], I.streams[0]));
+    HIP_OK(hipSetDevice(I.devices[0]));
+    HIP_OK(hipEventRecord(I.ev[0], I.streams[0]));
     try {
         RcclGroup group;
         for (int k = 0; k < n; ++k) {
-            HIP_CHECK(hipSetDevice(I.devices[k]));
+            HIP_OK(hipSetDevice(I.devices[k]));
             RCCL_ISSUE(ncclGather(I.send[k].p, k == 0 ? I.recv.p : nullptr, block, ncclUint8, 0, I.comms[k], I.streams[k]));
             if (k == n - 1 && opt(Opt::FaultRcclGroup) == 2)  // fault point (tests): an error inside the gather group
                 throw std::runtime_error("ncclGather: injected failure inside the group (test.fault_rccl_group = 2)");
@@ -375,21 +371,21 @@ void MultiRenderer::render(const CameraRec<double>& cam, const RenderParams& p, 
     if (opt(Opt::FaultGatherAbort) != 0) I.abort_all("ncclGather: injected failure (test.fault_gather_abort)");
     const auto tw = clock::now();
     I.wait_comms("ncclGather launch", deadline);  // non-blocking group: the gathers are enqueued once this returns
-    HIP_CHECK(hipSetDevice(I.devices[0]));
-    HIP_CHECK(hipEventRecord(I.ev[1], I.streams[0]));
+    HIP_OK(hipSetDevice(I.devices[0]));
+    HIP_OK(hipEventRecord(I.ev[1], I.streams[0]));
     I.wait_streams("ncclGather", deadline);
     tm.wait_ms = std::chrono::duration<double, std::milli>(clock::now() - tw).count();
     // phase 3: the root places every row and hands the frame over
-    HIP_CHECK(hipSetDevice(I.devices[0]));
+    HIP_OK(hipSetDevice(I.devices[0]));
     uint8_t* dst = out_device ? out_rgb : static_cast<uint8_t*>(I.frame.p);
     launch_unpack(static_cast<const uint8_t*>(I.recv.p), dst, W, H, band_rows, n, max_rows, I.streams[0]);
-    if (!out_device) HIP_CHECK(hipMemcpyAsync(out_rgb, I.frame.p, row_bytes * H, hipMemcpyDeviceToHost, I.streams[0]));
-    HIP_CHECK(hipEventRecord(I.ev[2], I.streams[0]));
-    HIP_CHECK(hipStreamSynchronize(I.streams[0]));
+    if (!out_device) HIP_OK(hipMemcpyAsync(out_rgb, I.frame.p, row_bytes * H, hipMemcpyDeviceToHost, I.streams[0]));
+    HIP_OK(hipEventRecord(I.ev[2], I.streams[0]));
+    HIP_OK(hipStreamSynchronize(I.streams[0]));
     const auto t1 = clock::now();
     float g_ms = 0.f, u_ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&g_ms, I.ev[0], I.ev[1]));
-    HIP_CHECK(hipEventElapsedTime(&u_ms, I.ev[1], I.ev[2]));
+    HIP_OK(hipEventElapsedTime(&g_ms, I.ev[0], I.ev[1]));
+    HIP_OK(hipEventElapsedTime(&u_ms, I.ev[1], I.ev[2]));
     tm.gather_ms = g_ms;
     tm.unpack_ms = u_ms;
 

@@ -1,5 +1,5 @@
 // noise_target.h — noise-target rendering (rt_render_noise_target): the per-pixel bookkeeping kernels of
-// noise_target.hip, launched by Renderer::render_noise_target (kernels.hip).  No HIP types in this header.
+// noise_target.hip, launched by Renderer::render_noise_target (renderer.hip).  No HIP types in this header.
 #pragma once
 #include <cstddef>
 #include <cstdint>

@@ -1,26 +1,16 @@
 // noise_target.hip — the bookkeeping kernels of noise-target rendering (rt_render_noise_target): every
 // pixel is traced until the standard error of its mean luminance is below a relative tolerance, up to a cap.  The paths
-// themselves are traced by the persistent kernels of kernels.hip (whole-image passes, then pixel-list passes with
+// themselves are traced by the persistent kernels k_paths / k_paths_g (whole-image passes, then pixel-list passes with
 // entry-major slots); the kernels here add the radiance records onto the per-pixel sums, evaluate the test, build the
 // next round's pixel list and write the frame.
 //
 // Exactness: a pixel that received n samples holds the sums and the RGB8 of rt_render with spp = n.  Every accumulator
 // (acc[3], S1, S2) is continued from its stored value one sample at a time in sample order, as k_accum adds them; the
 // test uses + - * / and comparisons only, compiled without contraction, and tests/nt_reference.py restates it.
-#include <hip/hip_runtime.h>
-
-#include <stdexcept>
-#include <string>
-
+#include "hip_check.h"
 #include "noise_target.h"
 
 namespace art {
-
-#define NT_HIP_OK(expr)                                                                                                   \
-    do {                                                                                                                  \
-        hipError_t e_ = (expr);                                                                                           \
-        if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " #expr); \
-    } while (0)
 
 // luminance of a radiance record (Rec. 709 weights), in this order
 __device__ __forceinline__ double nt_luminance(double r, double g, double b) { return (0.2126 * r + 0.7152 * g) + 0.0722 * b; }
@@ -113,7 +103,7 @@ __global__ __launch_bounds__(256) void k_nt_flag(const uint32_t* __restrict__ cu
     flag[p] = nt_unconverged(mom[2 * p], mom[2 * p + 1], n_done, rel_tol, lum_floor) ? 1 : 0;
 }
 
-// Wave-aggregated append (kernels.hip wave_append): one atomic per wave on the list's count word.  List order across
+// Wave-aggregated append (path_work.h wave_append): one atomic per wave on the list's count word.  List order across
 // waves varies from run to run; nothing downstream depends on it (every per-pixel sum is addressed by pixel).
 template <bool DILATE>
 __global__ __launch_bounds__(256) void k_nt_select(const uint32_t* __restrict__ cur, uint32_t n, const double* __restrict__ mom,
@@ -171,13 +161,13 @@ __global__ __launch_bounds__(256) void k_nt_finalize(const double* __restrict__ 
 void nt_accum_base(void* stream, const double* res, uint32_t k, uint32_t npix_pad, uint32_t tiles_x, int W, int rows, double* acc, double* mom) {
     hipLaunchKernelGGL(k_nt_accum_base, dim3((npix_pad + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), res, k, npix_pad, tiles_x, W, rows,
                        acc, mom);
-    NT_HIP_OK(hipGetLastError());
+    HIP_OK(hipGetLastError());
 }
 void nt_accum_list(void* stream, const uint32_t* list, uint32_t n, const double* res, uint32_t k, double* acc, double* mom) {
     if (n == 0) return;
     hipLaunchKernelGGL(k_nt_accum_list, dim3((n + kNtAccumWaves - 1) / kNtAccumWaves), dim3(64 * kNtAccumWaves), 0, static_cast<hipStream_t>(stream), list,
                        res, k, acc, mom);
-    NT_HIP_OK(hipGetLastError());
+    HIP_OK(hipGetLastError());
 }
 void nt_select(void* stream, const uint32_t* cur, uint32_t n, const double* mom, uint8_t* flag, int W, int rows, int n_done, int k_next, bool dilate,
                double rel_tol, double lum_floor, uint32_t* next, int32_t* count, uint32_t* converged) {
@@ -190,11 +180,11 @@ void nt_select(void* stream, const uint32_t* cur, uint32_t n, const double* mom,
     } else {
         hipLaunchKernelGGL(k_nt_select<false>, grid, block, 0, st, cur, n, mom, flag, W, rows, n_done, k_next, rel_tol, lum_floor, next, count, converged);
     }
-    NT_HIP_OK(hipGetLastError());
+    HIP_OK(hipGetLastError());
 }
 void nt_finalize(void* stream, const double* acc, const int32_t* count, uint8_t* rgb, uint32_t npix) {
     hipLaunchKernelGGL(k_nt_finalize, dim3((npix + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), acc, count, rgb, npix);
-    NT_HIP_OK(hipGetLastError());
+    HIP_OK(hipGetLastError());
 }
 
 }  // namespace art

@@ -1,4 +1,4 @@
-// renderer.h — host-side device renderer (implemented in kernels.hip; no HIP types in this header).
+// renderer.h — host-side device renderer (implemented in renderer.hip; no HIP types in this header).
 #pragma once
 #include <cstdint>
 #include <functional>

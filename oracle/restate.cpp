@@ -915,7 +915,7 @@ V3 ray_color_rec(const Scene& s, const Ray& r, int depth, Rng& rng, long long& s
 
 // The same integrator flattened into the product's iterative form (pcg mode): L += T*e; T *= a.
 // Path tracing diagnostics: ORC_TRACE="pixel:sample" prints every segment of that one path (orc_render_rows) as bit
-// patterns, in the format of the product's ART_TRACE build (kernels.hip k_paths_g), so the two can be diffed.
+// patterns, in the format of the product's ART_TRACE build (k_paths_g.h k_paths_g), so the two can be diffed.
 static thread_local bool g_tracing = false;
 static uint64_t bits(double x) {
     uint64_t b;

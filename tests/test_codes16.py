@@ -1,6 +1,6 @@
 """layout.h's 16-bit child codes (the packed-key traversal of the k_paths_g F_CODE16 kernels, BvhNode::pad): round trip
 and ordering against kNodeEmpty, on the host (tests/native/codes16_check.cpp, g++).  The device derives the codes from
-the 32-bit ones at upload (kernels.hip build_device_scene) and the GPU parity suite renders every scene through them."""
+the 32-bit ones at upload (device_scene.hip build_device_scene) and the GPU parity suite renders every scene through them."""
 import os
 import shutil
 import subprocess

@@ -70,7 +70,7 @@ def test_reflectance_branch_is_unchanged_by_one_ulp():
     assert flips == 0
 
 
-def fastdiv_make(d: int):  # csrc/kernels.hip FastDiv::make
+def fastdiv_make(d: int):  # csrc/path_work.h FastDiv::make
     l = 0
     while l < 32 and (1 << l) < d:
         l += 1

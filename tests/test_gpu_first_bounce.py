@@ -1,4 +1,4 @@
-"""k_paths' first-bounce rounds (csrc/kernels.hip, RayRing): a wave starts 64 paths at a time, traces and shades their
+"""k_paths' first-bounce rounds (csrc/k_paths.hip, RayRing): a wave starts 64 paths at a time, traces and shades their
 first segment together, writes the radiance of the paths that end there and appends the others, compacted, to its ring.
 
 Every render here runs k_paths (extend_variant 3) and is bit-exact in the f64 sums, the RGB8 frame and the segment

@@ -152,7 +152,7 @@ def test_persistent_paths_small_and_ragged_frames(gpu, W, H, spp):
 @pytest.mark.parametrize("scene", ["7", "3"])
 def test_lds_ring_kernels_small_ragged_split_and_banded(gpu, scene):
     # the triangle-free LM 1 kernels take their camera rays from a per-wave LDS ring filled 64 slots at a time
-    # (kernels.hip ring_fill_g / ring_take_g): passes shorter than one batch, batches of padding slots of partial 8x8
+    # (k_paths_g.h ring_fill_g / ring_take_g): passes shorter than one batch, batches of padding slots of partial 8x8
     # tiles, passes that end inside a batch, several passes, and band partitions must all trace exactly the oracle's
     # paths
     from tests.test_kernel_resources import SCENE_KERNELS

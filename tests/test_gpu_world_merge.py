@@ -1,7 +1,7 @@
 """Scene-compile restructurings switched off (options compile.world_merge = 0 / 1, compile.hoist = 0, which apply to
 scenes compiled after they are set): the world stays the reference's hittable_list of loose primitives, which must (a)
 not take the LDS k_paths kernel -- it shades hits by LDS leaf slot, so a loose OBJ_PRIM object would be shaded with
-another object's material (kernels.hip lds_scene_image) -- and (b) still equal the oracle bit for bit, as it
+another object's material (device_scene.hip lds_scene_image) -- and (b) still equal the oracle bit for bit, as it
 does with the restructurings on (tests/test_gpu_parity.py)."""
 import numpy as np
 import pytest

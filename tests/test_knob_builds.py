@@ -1,6 +1,6 @@
 """Every compile-time knob that survives in the kernel sources (another_raytracer_amd/csrc) still compiles for gfx950
 with a non-default value, device code only (no GPU needed): the diagnostic builds (ART_STATS divergence counters,
-ART_TRACE path dumps), the one-object build (ART_SPLIT_PATHS=0), the k_paths leaf test with the per-slot code
+ART_TRACE path dumps: the one-object build, kernels_unity.hip), the k_paths leaf test with the per-slot code
 (ART_LDS_LEAF_NOREF=0) and the tuning parameters DESIGN.md §4 measured (suspend threshold, waves per SIMD, ring size,
 LDS node capacity, k_extend occupancy, k_paths_g's LDS camera-ray ring for A/B).  Dropped experiments are deleted from the sources, not compiled out, so no
 other switch exists to rot."""
@@ -15,20 +15,21 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "another_raytracer_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc"
 
-# knob sets, each compiled once (sets combine knobs that do not interact, to keep the CPU suite short)
+# knob sets (source file, flags), each compiled once (sets combine knobs that do not interact, to keep the CPU suite short)
 VARIANTS = {
-    "stats": ["-DART_SPLIT_PATHS=0", "-DART_STATS", "-DART_SUSPEND_LANES=0", "-DART_POOL_RING=128", "-DART_LDS_NODE_CAP=320"],
-    "trace": ["-DART_SPLIT_PATHS=0", "-DART_TRACE", "-DART_PATHS_G_WAVES=2", "-DART_EXTEND_MIN_WAVES=2", "-DART_LDS_LEAF_NOREF=1"],
-    "paths_ref": ["-DART_SPLIT_PATHS=2", "-DART_LDS_LEAF_NOREF=0", "-DART_SUSPEND_LANES=16"],
-    "no_ring": ["-DART_SPLIT_PATHS=1", "-DART_LDS_RING_G=0"],
+    "stats": ("kernels_unity.hip", ["-DART_STATS", "-DART_SUSPEND_LANES=0", "-DART_POOL_RING=128", "-DART_LDS_NODE_CAP=320"]),
+    "trace": ("kernels_unity.hip", ["-DART_TRACE", "-DART_PATHS_G_WAVES=2", "-DART_EXTEND_MIN_WAVES=2", "-DART_LDS_LEAF_NOREF=1"]),
+    "paths_ref": ("k_paths.hip", ["-DART_LDS_LEAF_NOREF=0", "-DART_SUSPEND_LANES=16"]),
+    "no_ring": ("kernels.hip", ["-DART_LDS_RING_G=0"]),
 }
-SURVIVING = {"ART_STATS", "ART_TRACE", "ART_SPLIT_PATHS", "ART_SPLIT_MESH", "ART_LDS_LEAF_NOREF", "ART_SUSPEND_LANES", "ART_PATHS_G_WAVES",
+SURVIVING = {"ART_STATS", "ART_TRACE", "ART_LDS_LEAF_NOREF", "ART_SUSPEND_LANES", "ART_PATHS_G_WAVES",
              "ART_POOL_RING", "ART_LDS_NODE_CAP", "ART_EXTEND_MIN_WAVES", "ART_LDS_BLOCK", "ART_LDS_RING_G"}
 
 
-def _compile(args, out):
+def _compile(variant, out):
+    src, args = variant
     cmd = [HIPCC, "-std=c++17", "-O1", "--offload-arch=gfx950", "--cuda-device-only", "-ffp-contract=off", "-w", "-I" + os.path.join(ROOT, "include"),
-           "-I" + CSRC, *args, "-c", os.path.join(CSRC, "kernels.hip"), "-o", out]
+           "-I" + CSRC, *args, "-c", os.path.join(CSRC, src), "-o", out]
     return subprocess.run(cmd, capture_output=True, text=True, timeout=1200)
 
 

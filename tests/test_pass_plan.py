@@ -1,5 +1,5 @@
 """pass_plan.h's path_chunk -- how many path slots a persistent kernel's wave claims per atomic on the pass counter
-(kernels.hip k_paths / k_paths_g; r4r_ab_path_chunk.txt) -- built with g++ and checked on the host: its values at the
+(k_paths.hip k_paths / k_paths_g.h k_paths_g; r4r_ab_path_chunk.txt) -- built with g++ and checked on the host: its values at the
 BASELINE configs' pass sizes and its invariants (a power of two in [64, 2048], monotone in the pass size, at least 64
 claims per wave of a full CU above the minimum)."""
 import os

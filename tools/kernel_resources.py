@@ -6,6 +6,7 @@
 
 tests/test_kernel_resources.py uses it to guard the occupancy DESIGN.md §4 relies on (k_paths: <= 128 VGPRs and no
 scratch, i.e. 4 waves per SIMD)."""
+import hashlib
 import struct
 import sys
 
@@ -74,11 +75,35 @@ def kernel_metadata(elf):
     return []
 
 
+def function_code(elf):
+    """{function symbol: its code bytes} of one code object (the STT_FUNC entries of its symbol table)."""
+    shoff, = struct.unpack_from("<Q", elf, 0x28)
+    shentsize, shnum, _ = struct.unpack_from("<HHH", elf, 0x3A)
+    hdrs = [struct.unpack_from("<IIQQQQI", elf, shoff + i * shentsize) for i in range(shnum)]
+    out = {}
+    for _name, typ, _flags, _addr, off, size, link in hdrs:
+        if typ != 2:  # SHT_SYMTAB
+            continue
+        stroff = hdrs[link][4]
+        for at in range(off, off + size, 24):
+            name, info, _other, shndx, value, sz = struct.unpack_from("<IBBHQQ", elf, at)
+            if info & 15 == 2 and 0 < shndx < shnum:
+                start = hdrs[shndx][4] + value - hdrs[shndx][3]
+                out[elf[stroff + name:elf.index(b"\0", stroff + name)].decode()] = elf[start:start + sz]
+    return out
+
+
 def kernels(path):
-    """{kernel symbol: metadata dict} over every gfx950 code object in the library."""
+    """{kernel symbol: metadata dict} over every gfx950 code object in the library, plus .code_size and .code_sha1
+    (the function symbol's bytes)."""
     out = {}
     for co in code_objects(fatbin(path)):
+        code = function_code(co)
         for k in kernel_metadata(co):
+            if k[".name"] in out:
+                raise ValueError("kernel in two code objects: " + k[".name"])
+            k[".code_size"] = len(code[k[".name"]])
+            k[".code_sha1"] = hashlib.sha1(code[k[".name"]]).hexdigest()[:12]
             out[k[".name"]] = k
     return out
 
@@ -90,7 +115,7 @@ def main():
         if sub in name:
             print(f"{name}: vgpr {k.get('.vgpr_count')} agpr {k.get('.agpr_count', 0)} sgpr {k.get('.sgpr_count')} "
                   f"spill {k.get('.vgpr_spill_count', 0)} scratch {k.get('.private_segment_fixed_size')} "
-                  f"lds {k.get('.group_segment_fixed_size')}")
+                  f"lds {k.get('.group_segment_fixed_size')} code {k['.code_size']} B {k['.code_sha1']}")
 
 
 if __name__ == "__main__":

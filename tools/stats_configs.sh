@@ -1,5 +1,5 @@
 #!/bin/bash
-# Traversal statistics and the per-phase cycle split of the path kernels (libart_stats.so: SPLIT=0 EXTRA=-DART_STATS)
+# Traversal statistics and the per-phase cycle split of the path kernels (libart_stats.so: UNITY=1 EXTRA=-DART_STATS)
 # over the general-scene configs.  Usage (GPU box): bash tools/stats_configs.sh
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 export TMPDIR=/tmp

@@ -4,7 +4,7 @@
     python tools/trace_path.py oracle SCENE W H PIXEL SAMPLE
 
 The GPU side needs the ART_TRACE build (make -C another_raytracer_amd/csrc OUT=../libart_trace.so
-OBJDIR=../../build/trace EXTRA=-DART_TRACE ../libart_trace.so); both sides print lines starting with TRACE in one
+OBJDIR=../../build/trace UNITY=1 EXTRA=-DART_TRACE ../libart_trace.so); both sides print lines starting with TRACE in one
 format (bit patterns of the ray, hit point, normal), so `diff` finds the first operation where they part.
 """
 import os
