@@ -15,6 +15,8 @@ Scenes can also be assembled object by object with the reference's constructors 
 xy_rect, xz_rect, yz_rect, box, hittable_list, bvh_node, translate, rotate_y, constant_medium; lambertian, metal,
 dielectric, diffuse_light; solid_color, checker_texture, noise_texture, image_texture, barycentric_image_texture) and
 OBJ/MTL meshes (mesh().parse(path) / .build(), mesh.h) — see scene.py.
+Ray queries against a compiled scene -- closest hits with the whole hit_record, or any-hit occlusion with a per-ray
+t_max, on numpy arrays or device tensors: query_rays(world.objects, rays, ...) -- see rays.py.
 All compute runs in libart.so (HIP, gfx950) behind include/art.h.
 """
 from ._lib import RTError, get_option, lib, set_option  # noqa: F401  (fails loudly when libart.so is missing)
@@ -22,13 +24,14 @@ from .engine import camera, denoise, engine, engine_mode, tracer_constants  # no
 from .scene import (  # noqa: F401
     barycentric_image_texture, box, bvh_node, checker_texture, constant_medium, dielectric, diffuse_light, hittable_list, image_texture,
     lambertian, mesh, metal, moving_sphere, noise_texture, random_double, rotate_y, scene, scene_alias, scene_manager,
-    solid_color, sphere, translate, triangle, xy_rect, xz_rect, yz_rect, reset_scene_rng, save_scene,
+    solid_color, sphere, translate, triangle, xy_rect, xz_rect, yz_rect, reset_scene_rng, save_scene, compile_world,
 )
+from .rays import HitRecords, query_rays  # noqa: F401
 from . import imageio  # noqa: F401
 
 __all__ = [
     "RTError", "set_option", "get_option", "camera", "denoise", "engine", "engine_mode", "tracer_constants", "scene", "scene_alias", "scene_manager",
-    "hittable_list", "bvh_node", "sphere", "moving_sphere", "triangle", "xy_rect", "xz_rect", "yz_rect", "box",
+    "query_rays", "HitRecords", "compile_world", "hittable_list", "bvh_node", "sphere", "moving_sphere", "triangle", "xy_rect", "xz_rect", "yz_rect", "box",
     "translate", "rotate_y", "constant_medium", "lambertian", "metal", "dielectric", "diffuse_light", "solid_color",
     "checker_texture", "noise_texture", "image_texture", "barycentric_image_texture", "mesh", "random_double", "reset_scene_rng", "imageio", "save_scene",
 ]

@@ -23,6 +23,8 @@ RT_ABI_VERSION = 5
 RT_OUT_DEVICE, RT_PROFILE, RT_GLOBAL_SCENE, RT_SPLIT_SHADE, RT_ADAPTIVE, RT_WAVEFRONT, RT_PARALLEL_IMAGES = 1, 2, 4, 8, 16, 32, 64
 RT_GUIDE_DOUBLES = 10  # rt_render_guides: albedo[3], normal[3], position[3], t per pixel
 RT_DN_NO_DEMODULATE = 256
+RT_Q_ANY_HIT, RT_Q_NO_MEDIA = 512, 1024  # rt_query_params.flags
+RT_HIT_DOUBLES = 12  # rt_query_rays: t, normal[3], point[3], u, v, front_face, prim, mat per ray
 ERRORS = {-1: "RT_E_INVALID", -2: "RT_E_SCENE", -3: "RT_E_DEVICE", -4: "RT_E_INTERNAL"}
 
 
@@ -79,6 +81,10 @@ class rt_noise_result(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class rt_query_params(ctypes.Structure):  # zero-initialised = closest hit, host buffers, the scene's stream
+    _fields_ = [("flags", ctypes.c_int32), ("reserved", ctypes.c_int32), ("stream", ctypes.c_void_p)]
+
+
 class rt_multi_times(ctypes.Structure):
     _fields_ = [("total_ms", ctypes.c_double), ("render_ms_max", ctypes.c_double), ("render_ms_min", ctypes.c_double),
                 ("gather_ms", ctypes.c_double), ("unpack_ms", ctypes.c_double), ("wait_ms", ctypes.c_double),
@@ -111,6 +117,7 @@ SIGNATURES = {
     "rt_render_progressive": (_I, [_P, ctypes.POINTER(rt_camera), ctypes.POINTER(rt_params), _P, _P, rt_progress_fn, _P,
                                    ctypes.POINTER(rt_stats)]),
     "rt_trace_rays": (_I, [_P, _P, ctypes.c_int64, ctypes.c_int32, _P, _P]),
+    "rt_query_rays": (_I, [_P, ctypes.POINTER(rt_query_params), _P, _P, ctypes.c_int64, _P, _P]),
     "rt_render_guides": (_I, [_P, ctypes.POINTER(rt_camera), ctypes.POINTER(rt_params), _P, _P]),
     "rt_denoise": (_I, [_I, ctypes.POINTER(rt_denoise_params), _P, _P, ctypes.c_int32, _P, _P, _P, _DP]),
     "rt_render_denoised": (_I, [_P, ctypes.POINTER(rt_camera), ctypes.POINTER(rt_params), ctypes.POINTER(rt_denoise_params), _P, _P,

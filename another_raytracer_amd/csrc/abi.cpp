@@ -332,6 +332,26 @@ int rt_trace_rays(rt_scene* s, const double* rays, int64_t n, int32_t flags, dou
     });
 }
 
+int rt_query_rays(rt_scene* s, const rt_query_params* q, const double* rays, const double* t_max, int64_t n, double* hits, uint8_t* occluded) {
+    if (!s || !q) return fail(RT_E_INVALID, "rt_query_rays: scene and params must be non-NULL");
+    if (n < 0 || n > (int64_t(1) << 30)) return fail(RT_E_INVALID, "rt_query_rays: n must be in [0, 2^30]");
+    if (q->flags & ~(RT_OUT_DEVICE | RT_GLOBAL_SCENE | RT_Q_ANY_HIT | RT_Q_NO_MEDIA))
+        return fail(RT_E_INVALID, "rt_query_rays takes RT_OUT_DEVICE, RT_GLOBAL_SCENE, RT_Q_ANY_HIT and RT_Q_NO_MEDIA only");
+    if ((hits != nullptr) == (occluded != nullptr))
+        return fail(RT_E_INVALID, "rt_query_rays: give exactly one of hits (closest mode) and occluded (RT_Q_ANY_HIT)");
+    const bool any_hit = (q->flags & RT_Q_ANY_HIT) != 0;
+    if (any_hit != (occluded != nullptr))
+        return fail(RT_E_INVALID, any_hit ? "rt_query_rays: RT_Q_ANY_HIT writes occluded, not hits" : "rt_query_rays: occluded needs RT_Q_ANY_HIT");
+    if (n == 0) return RT_OK;
+    if (!rays) return fail(RT_E_INVALID, "rt_query_rays: rays is NULL");
+    return guard(RT_E_DEVICE, [&] {
+        if (!s->renderer) s->renderer = std::make_unique<art::Renderer>(s->flat, s->device);
+        s->renderer->query_rays(rays, t_max, static_cast<size_t>(n), (q->flags & RT_OUT_DEVICE) != 0, (q->flags & RT_GLOBAL_SCENE) != 0, any_hit,
+                                (q->flags & RT_Q_NO_MEDIA) != 0, q->stream, hits, occluded);
+        return RT_OK;
+    });
+}
+
 int rt_render_guides(rt_scene* s, const rt_camera* cam, const rt_params* p, double* guides, double* rays_out) {
     std::string why;
     if (!s || !cam || !guides) return fail(RT_E_INVALID, "scene, camera and guides must be non-NULL");

@@ -402,7 +402,8 @@ __device__ __forceinline__ void box_face(const BoxRec<R>& b, int f, int& axis, R
     else if (pair == 1) { a0 = b.mn[0]; a1 = b.mx[0]; b0 = b.mn[2]; b1 = b.mx[2]; k = hi ? b.mx[1] : b.mn[1]; }
     else { a0 = b.mn[1]; a1 = b.mx[1]; b0 = b.mn[2]; b1 = b.mx[2]; k = hi ? b.mx[0] : b.mn[0]; }
 }
-template <class R>
+// ANY (occlusion queries): true at the first side accepted in [tmin, tmax]; t and face are not set.
+template <class R, bool ANY = false>
 __device__ __forceinline__ bool hit_box(const BoxRec<R>& b, const Ray<R>& r, R tmin, R tmax, R& t, uint32_t& face) {
     bool any = false;  // hittable_list semantics over the six sides: closest wins, a later equal t replaces
     R closest = tmax;
@@ -411,6 +412,10 @@ __device__ __forceinline__ bool hit_box(const BoxRec<R>& b, const Ray<R>& r, R t
         R a0, a1, b0, b1, k, tt;
         box_face(b, f, axis, a0, a1, b0, b1, k);
         const bool h = hit_rect(axis, a0, a1, b0, b1, k, r, tmin, closest, tt);
+        if constexpr (ANY) {
+            if (h) return true;
+            continue;
+        }
         if (h) {
             any = true;
             closest = tt;
@@ -422,7 +427,7 @@ __device__ __forceinline__ bool hit_box(const BoxRec<R>& b, const Ray<R>& r, R t
 }
 
 // The test of a primitive given its record (a prim object's copy, DevScene::obj_prims): the same arithmetic as hit_prim.
-template <class R, uint32_t F>
+template <class R, uint32_t F, bool ANY = false>
 __device__ __forceinline__ bool hit_prim_rec(uint32_t type, const PrimRec80& rec, const Ray<R>& r, R tmin, R tmax, R& t, uint32_t& face) {
     if ((F & F_SPHERE) && (fbase(F) == F_SPHERE || type == PRIM_SPHERE)) return hit_sphere(reinterpret_cast<const SphereRec<R>&>(rec), r, tmin, tmax, t);
     if ((F & F_TRI) && (fbase(F) == F_TRI || type == PRIM_TRIANGLE)) return hit_tri(reinterpret_cast<const TriRec<R>&>(rec), r, tmin, tmax, t);
@@ -430,12 +435,12 @@ __device__ __forceinline__ bool hit_prim_rec(uint32_t type, const PrimRec80& rec
         const RectRec<R>& q = reinterpret_cast<const RectRec<R>&>(rec);
         return hit_rect(static_cast<int>(q.axis), q.a0, q.a1, q.b0, q.b1, q.k, r, tmin, tmax, t);
     }
-    if ((F & F_BOX) && type == PRIM_BOX) return hit_box(reinterpret_cast<const BoxRec<R>&>(rec), r, tmin, tmax, t, face);
+    if ((F & F_BOX) && type == PRIM_BOX) return hit_box<R, ANY>(reinterpret_cast<const BoxRec<R>&>(rec), r, tmin, tmax, t, face);
     return false;
 }
 // F (layout.h Feature bits) prunes the primitive kinds a scene cannot contain, so a kernel instantiated for a
 // spheres-only scene carries no triangle/box/transform/medium code and needs far fewer registers.
-template <class R, uint32_t F>
+template <class R, uint32_t F, bool ANY = false>
 __device__ __forceinline__ bool hit_prim(const DevScene<R>& S, uint32_t ref, const Ray<R>& r, R tmin, R tmax, R& t, uint32_t& face) {
     const uint32_t idx = primref_index(ref);
     const uint32_t type = primref_type(ref);
@@ -445,7 +450,7 @@ __device__ __forceinline__ bool hit_prim(const DevScene<R>& S, uint32_t ref, con
         const RectRec<R>& q = S.rects[idx];
         return hit_rect(static_cast<int>(q.axis), q.a0, q.a1, q.b0, q.b1, q.k, r, tmin, tmax, t);
     }
-    if ((F & F_BOX) && type == PRIM_BOX) return hit_box(S.boxes[idx], r, tmin, tmax, t, face);
+    if ((F & F_BOX) && type == PRIM_BOX) return hit_box<R, ANY>(S.boxes[idx], r, tmin, tmax, t, face);
     return false;
 }
 
@@ -718,12 +723,18 @@ struct TravResume {
 };
 // B: lanes per block (LDS stack stride).  L: nodes and leaf spheres come from the LDS scene image at `lds`.
 // RES: resumable (rs non-null), HBM-scene variant only.
-template <class R, uint32_t F, int B, bool L, int PL = 0, bool RES = false>
+// ANY (occlusion queries, k_occlude_rays): 0 = the closest hit; 1, 2 = any hit: the walk returns true at the first leaf
+// test accepted in [tmin, tmax] and sets none of t, prim, face, mt.  tmax -- and so the f32 interval of the box tests --
+// is then constant over the walk, so no visit is stale and the child order only decides how soon an occluder is met:
+// 1 keeps the nearest-first sorting network, 2 pushes the entered children in node order without it.
+template <class R, uint32_t F, int B, bool L, int PL = 0, bool RES = false, int ANY = 0>
 __device__ __forceinline__ bool traverse(const DevScene<R>& S, const uint8_t* lds, int32_t root, const Ray<R>& r, R tmin, R tmax,
                                          StackF<L, F>* stk, R& t, uint32_t& prim, uint32_t& face, uint32_t& mt, TravResume* rs = nullptr,
                                          int32_t hoisted = kNodeEmpty) {
     static_assert(!(L && (F & F_MEDIA)), "packed LDS keys need tmin > 0: no medium boundary tests in the LDS variant");
     static_assert(!RES || !L, "resumable traversal: HBM-scene variant only");
+    static_assert(ANY == 0 || !RES, "any-hit walks are never suspended");
+    constexpr bool kSort = ANY != 2;
     const float ox = static_cast<float>(r.o.x), oy = static_cast<float>(r.o.y), oz = static_cast<float>(r.o.z);
     // hardware reciprocal (1 ulp): the box test is conservative by its 2e-6 relative padding, far above that
     // A direction component that is 0 (or tiny) would give 1/d = inf, and the plane distances fma(plane, 1/d, -o/d)
@@ -916,11 +927,13 @@ __device__ __forceinline__ bool traverse(const DevScene<R>& S, const uint8_t* ld
                 // min/max pairs and each code comes back with one bit-field extract
                 uint32_t q0, q1, q2, q3;
                 slab4_packed(lx, hx, ly, hy, lz, hz, ch, ix, iy, iz, oix, oiy, oiz, tminf, tmaxf, q0, q1, q2, q3);
-                ucas(q0, q1);
-                ucas(q2, q3);
-                ucas(q0, q2);
-                ucas(q1, q3);
-                ucas(q1, q2);
+                if constexpr (kSort) {
+                    ucas(q0, q1);
+                    ucas(q2, q3);
+                    ucas(q0, q2);
+                    ucas(q1, q3);
+                    ucas(q1, q2);
+                }
                 if (q0 >= kKeyMiss) ART_STAT_LANE(12);  // a dead visit: no child box is entered before tmax
                 st.push(static_cast<int32_t>(q3), q3 < kKeyMiss);
                 st.push(static_cast<int32_t>(q2), q2 < kKeyMiss);
@@ -937,11 +950,13 @@ __device__ __forceinline__ bool traverse(const DevScene<R>& S, const uint8_t* ld
                 // as the LDS variant: 5 integer min/max pairs; each pushed code sign-extended from its key's low half
                 uint32_t q0, q1, q2, q3;
                 slab4_packed_nf(lx, hx, ly, hy, lz, hz, ch, ix, iy, iz, oix, oiy, oiz, tminf, tmaxf, q0, q1, q2, q3);
-                ucas(q0, q1);
-                ucas(q2, q3);
-                ucas(q0, q2);
-                ucas(q1, q3);
-                ucas(q1, q2);
+                if constexpr (kSort) {
+                    ucas(q0, q1);
+                    ucas(q2, q3);
+                    ucas(q0, q2);
+                    ucas(q1, q3);
+                    ucas(q1, q2);
+                }
                 st.push(static_cast<int16_t>(q3), q3 < kKeyMiss);
                 st.push(static_cast<int16_t>(q2), q2 < kKeyMiss);
                 st.push(static_cast<int16_t>(q1), q1 < kKeyMiss);
@@ -951,11 +966,13 @@ __device__ __forceinline__ bool traverse(const DevScene<R>& S, const uint8_t* ld
                 float k0, k1, k2, k3;
                 slab4_nf(lx, hx, ly, hy, lz, hz, ix, iy, iz, oix, oiy, oiz, tminf, tmaxf, k0, k1, k2, k3);
                 int32_t c0 = ch.x, c1 = ch.y, c2 = ch.z, c3 = ch.w;
-                cas(k0, c0, k1, c1);
-                cas(k2, c2, k3, c3);
-                cas(k0, c0, k2, c2);
-                cas(k1, c1, k3, c3);
-                cas(k1, c1, k2, c2);
+                if constexpr (kSort) {
+                    cas(k0, c0, k1, c1);
+                    cas(k2, c2, k3, c3);
+                    cas(k0, c0, k2, c2);
+                    cas(k1, c1, k3, c3);
+                    cas(k1, c1, k2, c2);
+                }
                 const float inf = __builtin_inff();
                 st.push(c3, k3 < inf);
                 st.push(c2, k2 < inf);
@@ -1056,7 +1073,7 @@ __device__ __forceinline__ bool traverse(const DevScene<R>& S, const uint8_t* ld
                     __asm__ volatile("" : "+v"(p1.x), "+v"(p1.y), "+v"(p1.z), "+v"(p2.x), "+v"(p2.y), "+v"(p2.z), "+v"(p3.x), "+v"(p3.y), "+v"(p3.z));
                     __asm__ volatile("" : "+v"(nn.x), "+v"(nn.y), "+v"(nn.z), "+v"(pdd));
                     if (fbase(F) == F_TRI || primref_type(ref) == PRIM_TRIANGLE) h = hit_tri_pre(p1, p2, p3, nn, pdd, r, tmin, tmax, tt);
-                    else h = hit_prim<R, F & ~F_TRI>(S, ref, r, tmin, tmax, tt, fc);
+                    else h = hit_prim<R, F & ~F_TRI, ANY != 0>(S, ref, r, tmin, tmax, tt, fc);
                 } else if constexpr ((F & F_TRI) != 0) {
                     // the leaf-ordered triangle copy: its address depends on the slot alone, so its loads go out
                     // beside the primref's instead of behind it (one L2 round trip per test instead of two); the
@@ -1066,7 +1083,7 @@ __device__ __forceinline__ bool traverse(const DevScene<R>& S, const uint8_t* ld
                     ref = S.primrefs[slot];
                     __asm__ volatile("" : "+v"(p1.x), "+v"(p1.y), "+v"(p1.z), "+v"(p2.x), "+v"(p2.y), "+v"(p2.z), "+v"(p3.x), "+v"(p3.y), "+v"(p3.z));
                     if (fbase(F) == F_TRI || primref_type(ref) == PRIM_TRIANGLE) h = hit_tri_v(p1, p2, p3, r, tmin, tmax, tt);
-                    else h = hit_prim<R, F & ~F_TRI>(S, ref, r, tmin, tmax, tt, fc);
+                    else h = hit_prim<R, F & ~F_TRI, ANY != 0>(S, ref, r, tmin, tmax, tt, fc);
                 } else {
                     // the leaf-ordered record copy: its loads go out beside the primref's instead of behind it
                     const uint4* lp = reinterpret_cast<const uint4*>(S.leaf_prims + slot);
@@ -1087,10 +1104,10 @@ __device__ __forceinline__ bool traverse(const DevScene<R>& S, const uint8_t* ld
                             if constexpr (kSphLazy) h = sphere_root_lazy<R>(center, sr.r * sr.r, r, d_a, d_inv_a, tmin, tmax, tt);
                             else h = sphere_root<R, true>(center, sr.r * sr.r, r, d_a, d_inv_a, tmin, tmax, tt);
                         } else {
-                            h = hit_prim_rec<R, F & ~F_SPHERE>(primref_type(ref), rec, r, tmin, tmax, tt, fc);
+                            h = hit_prim_rec<R, F & ~F_SPHERE, ANY != 0>(primref_type(ref), rec, r, tmin, tmax, tt, fc);
                         }
                     } else {
-                        h = hit_prim_rec<R, F>(primref_type(ref), rec, r, tmin, tmax, tt, fc);
+                        h = hit_prim_rec<R, F, ANY != 0>(primref_type(ref), rec, r, tmin, tmax, tt, fc);
                     }
                     // the record's material index (sphere / box / rect: dword 18 / 12 / 11) and a rect's axis (dword 10,
                     // in the face field): the hit's surface then needs no reload of a box or rect record (prim_surface)
@@ -1107,6 +1124,10 @@ __device__ __forceinline__ bool traverse(const DevScene<R>& S, const uint8_t* ld
                     else { ART_STAT_WAVE(22); ART_STAT_LANE(21); }
                 }
 #endif
+            }
+            if constexpr (ANY != 0) {
+                if (h) return true;  // the lane idles until its wave's walk ends
+                continue;
             }
             if (h) {
                 ART_STAT_LANE(13);
@@ -1140,7 +1161,7 @@ __device__ __forceinline__ Ray<R> xform_in(const ObjRec<R>& o, const Ray<R>& r) 
 }
 
 // Any non-medium object: prim, BVH, or a translate/rotate_y chain (<= kMaxXformChain) over one of them.
-template <class R, uint32_t F, int B, bool L, int PL = 0, bool RES = false>
+template <class R, uint32_t F, int B, bool L, int PL = 0, bool RES = false, int ANY = 0>
 __device__ __forceinline__ bool hit_object(const DevScene<R>& S, const uint8_t* lds, int32_t oi, Ray<R> r, R tmin, R tmax, StackF<L, F>* stk,
                                            R& t, uint32_t& prim, uint32_t& face, uint32_t& mt, TravResume* rs = nullptr) {
     if (F & F_XFORM) {
@@ -1160,7 +1181,7 @@ __device__ __forceinline__ bool hit_object(const DevScene<R>& S, const uint8_t* 
         if constexpr (!L) {
             const PrimRec80& rec = S.obj_prims[oi];
             const uint32_t ty = primref_type(prim);
-            const bool h = hit_prim_rec<R, F>(ty, rec, r, tmin, tmax, t, face);
+            const bool h = hit_prim_rec<R, F, ANY != 0>(ty, rec, r, tmin, tmax, t, face);
             if constexpr ((F & F_TRI) == 0) {  // as the leaf records: the material index, a rect's axis in `face`
                 const uint32_t* wd = reinterpret_cast<const uint32_t*>(rec.b);
                 mt = ty == PRIM_SPHERE ? wd[18] : ty == PRIM_BOX ? wd[12] : wd[11];
@@ -1168,10 +1189,10 @@ __device__ __forceinline__ bool hit_object(const DevScene<R>& S, const uint8_t* 
             }
             return h;
         } else {
-            return hit_prim<R, F>(S, prim, r, tmin, tmax, t, face);
+            return hit_prim<R, F, ANY != 0>(S, prim, r, tmin, tmax, t, face);
         }
     }
-    return traverse<R, F, B, L, PL, RES>(S, lds, o.a, r, tmin, tmax, stk, t, prim, face, mt, rs, o.b);
+    return traverse<R, F, B, L, PL, RES, ANY>(S, lds, o.a, r, tmin, tmax, stk, t, prim, face, mt, rs, o.b);
 }
 
 // Out of line: measured +0.2 % (cow) to +1.8 % (Next-Week final) over the inlined body, which raised the register
@@ -1249,16 +1270,19 @@ struct HitOut {
     uint32_t mt;         // LDS scene image: the material type; HBM-scene triangle-free kernels: the material index of a
                          // primitive hit (a rect's axis then rides in obj >> 16); else kMatUnknown
 };
+// t_max: the search interval is [0.001, t_max] (rt_query_rays; every renderer call site searches to +inf).
+// no_media (RT_Q_NO_MEDIA): constant_medium objects are skipped and draw nothing from rng.
 template <class R, uint32_t F, int B, bool L, int PL = 0>
 __device__ __forceinline__ bool trace_world(const DevScene<R>& S, const uint8_t* lds, const Ray<R>& r, StackF<L, F>* stk, uint64_t& rng, R& t,
-                                            HitOut& h) {
-    R closest = R(__builtin_inf());
+                                            HitOut& h, R t_max = R(__builtin_inf()), bool no_media = false) {
+    R closest = t_max;
     bool any = false;
     for (int w = 0; w < S.nworld; ++w) {
         const int32_t oi = S.world[w];
         const ObjRec<R>& o = S.objs[oi];
         R tt;
         if ((F & F_MEDIA) && o.kind == OBJ_MEDIUM) {
+            if (no_media) continue;
             if (hit_medium<R, F, B, L, PL>(S, lds, o, r, R(0.001), closest, stk, rng, tt)) {
                 closest = tt;
                 any = true;
@@ -1279,6 +1303,23 @@ __device__ __forceinline__ bool trace_world(const DevScene<R>& S, const uint8_t*
     }
     t = closest;
     return any;
+}
+
+// Occlusion query (rt_query_rays with RT_Q_ANY_HIT): true iff some non-medium primitive of the world is accepted by its
+// own hit test in [0.001, t_max].  The list walk stops at the first occluder; constant_medium objects never occlude.
+// Every primitive whose test accepts is inside a leaf whose padded f32 box the constant interval enters, so the answer
+// depends on neither the tree nor the order of the walk.  F carries no media bits.  ANY: traverse's 1 or 2.
+template <class R, uint32_t F, int B, bool L, int ANY>
+__device__ __forceinline__ bool occlude_world(const DevScene<R>& S, const uint8_t* lds, const Ray<R>& r, StackF<L, F>* stk, R t_max) {
+    static_assert((F & (F_MEDIA | F_MEDIA_G)) == 0 && ANY != 0, "any-hit walks test no medium");
+    for (int w = 0; w < S.nworld; ++w) {
+        const int32_t oi = S.world[w];
+        if (S.objs[oi].kind == OBJ_MEDIUM) continue;
+        R tt;
+        uint32_t prim = 0, face = 0, mt = kMatUnknown;
+        if (hit_object<R, F, B, L, 0, false, ANY>(S, lds, oi, r, R(0.001), t_max, stk, tt, prim, face, mt)) return true;
+    }
+    return false;
 }
 
 // trace_world with suspendable BVH traversals (ART_SUSPEND_LANES): the world list walk of one segment, resumed at
@@ -1375,7 +1416,9 @@ __device__ __forceinline__ void rect_surface(V3<R>& p, V3<R>& n, bool& ff, R& su
 // uvc: glibc_trig.h's constants (uv_table(S) or k_paths_g's LDS copy of its head; read only when UV); the tables
 // behind them are read from uv_table(S)
 // TUV: triangle u, v (barycentric image textures); UV: u, v of every primitive (TF_IMAGE kernels)
-template <class R, uint32_t F, bool UV = true, bool TUV = UV>
+// ALLUV (k_query_rays' hit record): u, v whatever the material samples -- of static spheres, triangles, rects and box
+// sides, the primitives whose hit() sets them in the reference; a moving sphere's stay 0 (moving_sphere.h sets none)
+template <class R, uint32_t F, bool UV = true, bool TUV = UV, bool ALLUV = false>
 __device__ __forceinline__ void prim_surface(const DevScene<R>& S, uint32_t ref, uint32_t face, const Ray<R>& r, R t, Surf<R>& s,
                                              uint32_t mat_hint, const double* uvc) {
     const uint32_t idx = primref_index(ref);
@@ -1396,7 +1439,7 @@ __device__ __forceinline__ void prim_surface(const DevScene<R>& S, uint32_t ref,
             const V3<R> outward = divs(sp_p - center, sp.r);
             face_normal(r, outward, ff, sp_n);
             // u,v only feed image textures: acos/atan2 are skipped for materials that never sample them
-            if (UV && !moving && (S.mats[sp.mat].flags & MATF_NEEDS_UV)) {
+            if (UV && !moving && (ALLUV || (S.mats[sp.mat].flags & MATF_NEEDS_UV))) {
                 ART_STAT_WAVE(32);
                 ART_STAT_LANE(33);
                 // get_sphere_uv (sphere.h:24-37) with glibc's acos / atan2 restated (sphere_uv.h; their constants are
@@ -1417,7 +1460,7 @@ __device__ __forceinline__ void prim_surface(const DevScene<R>& S, uint32_t ref,
             const V3<R> p = r.o + t * r.d;
             sp_p = p;
             face_normal(r, N, ff, sp_n);
-            if (TUV && (S.mats[tr.mat].flags & MATF_NEEDS_UV)) {  // barycentric u, v feed image textures only (texture.h:135-154)
+            if (TUV && (ALLUV || (S.mats[tr.mat].flags & MATF_NEEDS_UV))) {  // barycentric u, v feed image textures only (texture.h:135-154)
                 const R u = dot(N, cross(p3 - p2, p - p2));
                 const R v = dot(N, cross(p1 - p3, p - p3));
                 su = u / len2(N);
@@ -1428,7 +1471,7 @@ __device__ __forceinline__ void prim_surface(const DevScene<R>& S, uint32_t ref,
         }
         case PRIM_RECT: {
             if (!(F & F_RECT)) break;
-            if (mat_hint != kMatUnknown && !(UV && (S.mats[mat_hint].flags & MATF_NEEDS_UV))) {
+            if (mat_hint != kMatUnknown && !(UV && (ALLUV || (S.mats[mat_hint].flags & MATF_NEEDS_UV)))) {
                 ART_STAT_WAVE(42);
                 ART_STAT_LANE(43);
                 rect_surface<R, false>(sp_p, sp_n, ff, su, sv, static_cast<int>(face), R(0), R(0), R(0), R(0), r, t);
@@ -1438,13 +1481,13 @@ __device__ __forceinline__ void prim_surface(const DevScene<R>& S, uint32_t ref,
             ART_STAT_WAVE(38);
             ART_STAT_LANE(39);
             const RectRec<R>& q = S.rects[idx];
-            rect_surface<R, UV>(sp_p, sp_n, ff, su, sv, static_cast<int>(q.axis), q.a0, q.a1, q.b0, q.b1, r, t, (S.mats[q.mat].flags & MATF_NEEDS_UV) != 0);
+            rect_surface<R, UV>(sp_p, sp_n, ff, su, sv, static_cast<int>(q.axis), q.a0, q.a1, q.b0, q.b1, r, t, ALLUV || (S.mats[q.mat].flags & MATF_NEEDS_UV) != 0);
             mat = q.mat;
             break;
         }
         default: {
             if (!(F & F_BOX)) break;
-            if (mat_hint != kMatUnknown && !(UV && (S.mats[mat_hint].flags & MATF_NEEDS_UV))) {
+            if (mat_hint != kMatUnknown && !(UV && (ALLUV || (S.mats[mat_hint].flags & MATF_NEEDS_UV)))) {
                 ART_STAT_WAVE(42);
                 ART_STAT_LANE(43);
                 rect_surface<R, false>(sp_p, sp_n, ff, su, sv, static_cast<int>(face >> 1), R(0), R(0), R(0), R(0), r, t);  // box_face: axis = f >> 1
@@ -1457,7 +1500,7 @@ __device__ __forceinline__ void prim_surface(const DevScene<R>& S, uint32_t ref,
             int axis;
             R a0, a1, b0, b1, k;
             box_face(b, static_cast<int>(face), axis, a0, a1, b0, b1, k);
-            rect_surface<R, UV>(sp_p, sp_n, ff, su, sv, axis, a0, a1, b0, b1, r, t, (S.mats[b.mat].flags & MATF_NEEDS_UV) != 0);
+            rect_surface<R, UV>(sp_p, sp_n, ff, su, sv, axis, a0, a1, b0, b1, r, t, ALLUV || (S.mats[b.mat].flags & MATF_NEEDS_UV) != 0);
             mat = b.mat;
             break;
         }
@@ -1472,7 +1515,7 @@ __device__ __forceinline__ void prim_surface(const DevScene<R>& S, uint32_t ref,
 
 // Rebuilds the hit_record of the world object that won (transform chain unwound as translate::hit / rotate_y::hit
 // do it: hittable.cpp:7-11, :72-84, including set_face_normal against the transformed ray).
-template <class R, uint32_t F, bool UV = true, bool TUV = UV>
+template <class R, uint32_t F, bool UV = true, bool TUV = UV, bool ALLUV = false>
 __device__ __forceinline__ void world_surface(const DevScene<R>& S, const HitOut& h, const Ray<R>& r, R t, Surf<R>& s, const double* uvc = nullptr) {
     const int32_t w = static_cast<int32_t>(h.obj & 0xFFFFu);
     int32_t oi = S.world[w];
@@ -1508,7 +1551,7 @@ __device__ __forceinline__ void world_surface(const DevScene<R>& S, const HitOut
             }
         }
     }
-    prim_surface<R, F, UV, TUV>(S, h.prim, h.obj >> 16, r2, t, s, (F & F_TRI) == 0 ? h.mt : kMatUnknown, uvc);
+    prim_surface<R, F, UV, TUV, ALLUV>(S, h.prim, h.obj >> 16, r2, t, s, (F & F_TRI) == 0 ? h.mt : kMatUnknown, uvc);
     if (!(F & F_XFORM)) return;
 #ifdef ART_STATS
     if (o0 >= 0) {

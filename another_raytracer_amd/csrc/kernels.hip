@@ -294,6 +294,84 @@ __global__ __launch_bounds__(L ? kBlockL : kBlock) void k_trace_rays(DevScene<do
     }
 }
 
+// Ray queries with the hit record (rt_query_rays, closest mode): k_trace_rays' search over [0.001, t_max[i]] (t_max null:
+// +inf), constant_medium objects skipped when no_media, and the whole hit_record as world_surface rebuilds it.  Record per
+// ray (RT_HIT_DOUBLES = 12): t, normal[3], point[3], u, v, front_face, prim, mat.  u, v: get_sphere_uv / the rect and
+// triangle formulas for every material (prim_surface ALLUV; the trig table is uploaded with every scene); 0 where the
+// reference's hit() sets none (moving spheres, media).  prim: the compiled primitive reference (type:2 | index:30), -2 for
+// a medium scattering event; mat: the material index.  A miss: t = point = +inf, prim = mat = -1, everything else 0.
+// With t_max null and no_media 0 the traversal is k_trace_rays' own: the same t and normal.
+template <uint32_t F, bool L>
+__global__ __launch_bounds__(L ? kBlockL : kBlock) void k_query_rays(DevScene<double> S, const double* rays, const double* t_max, uint32_t n,
+                                                                       uint32_t no_media, double* hits) {
+    using R = double;
+    constexpr int B = L ? kBlockL : kBlock;
+    extern __shared__ __align__(16) uint8_t smem[];
+    StackT<L>* stk = reinterpret_cast<StackT<L>*>(smem + (L ? kLdsImageBytes : 0u)) + B + stack_column<L>(threadIdx.x);
+    stk[-B] = static_cast<StackT<L>>(kNodeEmpty);
+    if constexpr (L) {
+        load_lds_image<B>(S.lds_image, smem);
+        __syncthreads();
+    }
+    const uint32_t i = blockIdx.x * B + threadIdx.x;
+    if (i >= n) return;
+    const double* q = rays + 7 * static_cast<size_t>(i);
+    Ray<R> r;
+    r.o = mk(q[0], q[1], q[2]);
+    r.d = mk(q[3], q[4], q[5]);
+    r.tm = q[6];
+    const R inf = __builtin_inf();
+    const R tm = t_max ? t_max[i] : inf;
+    uint64_t rng = pcg_seed(0, i, 0);
+    R t = R(0);
+    HitOut h{0, 0, kMatUnknown};
+    double* o = hits + 12 * static_cast<size_t>(i);
+    if (trace_world<R, F, B, L>(S, L ? smem : nullptr, r, stk, rng, t, h, tm, no_media != 0)) {
+        Surf<R> s;
+        world_surface<R, F, true, true, true>(S, h, r, t, s, uv_table(S));
+        o[0] = t;
+        o[1] = s.n.x; o[2] = s.n.y; o[3] = s.n.z;
+        o[4] = s.p.x; o[5] = s.p.y; o[6] = s.p.z;
+        o[7] = s.u; o[8] = s.v;
+        o[9] = s.ff ? 1.0 : 0.0;
+        o[10] = h.prim == kMediumHit ? -2.0 : static_cast<double>(h.prim);
+        o[11] = static_cast<double>(s.mat);
+    } else {
+        o[0] = inf;
+        o[1] = o[2] = o[3] = 0.0;
+        o[4] = o[5] = o[6] = inf;
+        o[7] = o[8] = o[9] = 0.0;
+        o[10] = o[11] = -1.0;
+    }
+}
+
+// Occlusion queries (rt_query_rays with RT_Q_ANY_HIT): occluded[i] = 1 iff some non-medium primitive is accepted by its own
+// hit test in [0.001, t_max[i]] (occlude_world: the any-hit traversal, the world walk stopping at the first occluder).  F
+// carries no media bits; no RNG.  ANY: traverse's child order (1 sorted, 2 node order: option query.any_sorted; the node
+// order is the default, DESIGN.md 4.7 measured both).
+template <uint32_t F, bool L, int ANY>
+__global__ __launch_bounds__(L ? kBlockL : kBlock) void k_occlude_rays(DevScene<double> S, const double* rays, const double* t_max, uint32_t n,
+                                                                         uint8_t* occluded) {
+    using R = double;
+    constexpr int B = L ? kBlockL : kBlock;
+    extern __shared__ __align__(16) uint8_t smem[];
+    StackT<L>* stk = reinterpret_cast<StackT<L>*>(smem + (L ? kLdsImageBytes : 0u)) + B + stack_column<L>(threadIdx.x);
+    stk[-B] = static_cast<StackT<L>>(kNodeEmpty);
+    if constexpr (L) {
+        load_lds_image<B>(S.lds_image, smem);
+        __syncthreads();
+    }
+    const uint32_t i = blockIdx.x * B + threadIdx.x;
+    if (i >= n) return;
+    const double* q = rays + 7 * static_cast<size_t>(i);
+    Ray<R> r;
+    r.o = mk(q[0], q[1], q[2]);
+    r.d = mk(q[3], q[4], q[5]);
+    r.tm = q[6];
+    const R tm = t_max ? t_max[i] : R(__builtin_inf());
+    occluded[i] = occlude_world<R, F, B, L, ANY>(S, L ? smem : nullptr, r, stk, tm) ? 1 : 0;
+}
+
 // First-hit guide buffers (rt_render_guides): one ray per local pixel through the pixel centre -- no render RNG draw,
 // no lens offset, time0 -- traced exactly as k_trace_rays traces it (ray index = global pixel gy * W + i, so a whole
 // frame's t and normal equal rt_trace_rays of rays_out), plus the hit point (Surf::p) and the first hit's albedo:
@@ -806,6 +884,58 @@ void launch_adapt_level(hipStream_t st, int level, int32_t* work, int W, int sqx
 }
 void launch_adapt_fill(hipStream_t st, int32_t* work, uint8_t* rgb, int W, int rows, int sqx, const uint8_t* f0, const uint8_t* f1, const uint8_t* f2) {
     hipLaunchKernelGGL(k_adapt_fill, grid256(static_cast<uint32_t>(rows) * static_cast<uint32_t>(W)), dim3(256), 0, st, work, rgb, W, rows, sqx, f0, f1, f2);
+}
+
+// The rt_query_rays launchers close the file: they instantiate k_query_rays and k_occlude_rays, and the compiler emits
+// device functions in instantiation order, so every earlier kernel and the out-of-line helpers it calls keep their
+// relative places -- and with them their code bytes (DESIGN.md 4.7 compares them with the build before these kernels).
+// rt_query_rays, closest mode: launch_trace_rays' instantiation choice (the LDS image, else the smallest HBM-scene feature set)
+template <uint32_t F, bool L>
+static void launch_query_fl(const DeviceScene<double>& ds, hipStream_t st, const double* d_rays, const double* d_tmax, uint32_t nn, bool no_media,
+                            double* d_hits) {
+    const uint32_t stack = stack_rows(ds.max_stack);
+    constexpr int B = L ? kBlockL : kBlock;
+    const size_t lds = L ? kLdsImageBytes + paths_stack_bytes(stack) : sizeof(int32_t) * stack * kBlock;
+    if constexpr (L) {
+        static const bool checked = static_lds_is_zero(reinterpret_cast<const void*>(k_query_rays<F, L>));
+        (void)checked;
+        (void)blocks_per_cu(reinterpret_cast<const void*>(k_query_rays<F, L>), B, lds);  // the > 64 KiB dynamic-LDS attribute
+    }
+    hipLaunchKernelGGL((k_query_rays<F, L>), dim3((nn + B - 1) / B), dim3(B), lds, st, ds.view, d_rays, d_tmax, nn, no_media ? 1u : 0u, d_hits);
+}
+void launch_query_rays(const DeviceScene<double>& ds, bool global_scene, hipStream_t st, const double* d_rays, const double* d_tmax, uint32_t nn,
+                       bool no_media, double* d_hits) {
+    const uint32_t feat = ds.features;
+    if (ds.lds_scene && !global_scene && (feat & ~kFeatSpheres) == 0) launch_query_fl<kFeatSpheres, true>(ds, st, d_rays, d_tmax, nn, no_media, d_hits);
+    else if ((feat & ~kFeatSpheres) == 0) launch_query_fl<kFeatSpheres, false>(ds, st, d_rays, d_tmax, nn, no_media, d_hits);
+    else if ((feat & ~kFeatMesh) == 0) launch_query_fl<kFeatMesh, false>(ds, st, d_rays, d_tmax, nn, no_media, d_hits);
+    else launch_query_fl<F_ALL, false>(ds, st, d_rays, d_tmax, nn, no_media, d_hits);
+}
+// the any-hit kernels: the same choice with the media bits removed; the child order from option query.any_sorted
+template <uint32_t F, bool L>
+static void launch_occlude_fl(const DeviceScene<double>& ds, hipStream_t st, const double* d_rays, const double* d_tmax, uint32_t nn, uint8_t* d_occ) {
+    const uint32_t stack = stack_rows(ds.max_stack);
+    constexpr int B = L ? kBlockL : kBlock;
+    const size_t lds = L ? kLdsImageBytes + paths_stack_bytes(stack) : sizeof(int32_t) * stack * kBlock;
+    auto go = [&](auto kernel) {
+        if constexpr (L) {
+            static const bool checked = static_lds_is_zero(reinterpret_cast<const void*>(kernel));
+            (void)checked;
+            (void)blocks_per_cu(reinterpret_cast<const void*>(kernel), B, lds);
+        }
+        hipLaunchKernelGGL(kernel, dim3((nn + B - 1) / B), dim3(B), lds, st, ds.view, d_rays, d_tmax, nn, d_occ);
+    };
+    if (opt(Opt::QueryAnySorted) != 0) go(k_occlude_rays<F, L, 1>);
+    else go(k_occlude_rays<F, L, 2>);
+}
+void launch_occlude_rays(const DeviceScene<double>& ds, bool global_scene, hipStream_t st, const double* d_rays, const double* d_tmax, uint32_t nn,
+                         uint8_t* d_occ) {
+    constexpr uint32_t kNoMedia = ~(F_MEDIA | F_MEDIA_G);
+    const uint32_t feat = ds.features & kNoMedia;
+    if (ds.lds_scene && !global_scene && (ds.features & ~kFeatSpheres) == 0) launch_occlude_fl<kFeatSpheres, true>(ds, st, d_rays, d_tmax, nn, d_occ);
+    else if ((feat & ~kFeatSpheres) == 0) launch_occlude_fl<kFeatSpheres, false>(ds, st, d_rays, d_tmax, nn, d_occ);
+    else if ((feat & ~kFeatMesh) == 0) launch_occlude_fl<kFeatMesh & kNoMedia, false>(ds, st, d_rays, d_tmax, nn, d_occ);
+    else launch_occlude_fl<F_ALL & kNoMedia, false>(ds, st, d_rays, d_tmax, nn, d_occ);
 }
 
 }  // namespace art

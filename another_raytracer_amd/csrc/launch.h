@@ -36,6 +36,11 @@ void launch_adapt_level(hipStream_t st, int level, int32_t* work, int W, int sqx
                         uint32_t* count);
 void launch_adapt_fill(hipStream_t st, int32_t* work, uint8_t* rgb, int W, int rows, int sqx, const uint8_t* f0, const uint8_t* f1, const uint8_t* f2);
 void launch_trace_rays(const DeviceScene<double>& ds, bool global_scene, hipStream_t st, const double* rays, uint32_t n, double* t_out, double* n_out);
+// rt_query_rays: closest hits with the record (hits: n x 12) / occlusion bytes; t_max may be null (+inf)
+void launch_query_rays(const DeviceScene<double>& ds, bool global_scene, hipStream_t st, const double* rays, const double* t_max, uint32_t n,
+                       bool no_media, double* hits);
+void launch_occlude_rays(const DeviceScene<double>& ds, bool global_scene, hipStream_t st, const double* rays, const double* t_max, uint32_t n,
+                         uint8_t* occluded);
 void launch_guides(const DeviceScene<double>& ds, int flags, hipStream_t st, const GuideGeom& g, const CameraRec<double>& cam, double* guides,
                    double* rays);
 // k_paths.hip

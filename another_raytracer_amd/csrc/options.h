@@ -28,6 +28,8 @@ enum class Opt : int {
     TexBary,       // render.tex_bary: 1 (default) the TF_BARY kernels for meshes whose only images are barycentric, 0 off
     DenoiseLdsIterations,  // denoise.lds_iterations: how many of rt_denoise's first iterations (tap spacings 1, 2) run the
                            // LDS-tile kernel instead of the direct-load one (0..2; same result either way, A/B)
+    QueryAnySorted,  // query.any_sorted: rt_query_rays' any-hit walk visits a node's children in node order without the
+                     // sorting network (0, default: measured faster) or nearest first (1); the same answers either way (A/B)
     // multi-GPU
     MultiTimeoutMs,  // multi.timeout_ms: deadline of RCCL init / gather waits (unset: ART_MULTI_TIMEOUT_MS, else 120000;
                      // inf, or anything beyond ~292 years, means no deadline)

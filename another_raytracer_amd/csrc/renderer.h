@@ -48,6 +48,12 @@ public:
     // Closest hit of n rays (rays: n x {ox, oy, oz, dx, dy, dz, tm}) through the renderer's traversal: t (inf on a
     // miss) and the face normal (n x 3), host buffers; global_scene forces the HBM traversal on an LDS-image scene.
     void trace_rays(const double* rays, size_t n, bool global_scene, double* t_out, double* n_out);
+    // rt_query_rays: closest hits with the record (hits: n x RT_HIT_DOUBLES) or, with any_hit, occlusion bytes, over
+    // [0.001, t_max[i]] (t_max null: +inf).  device: every buffer is a device pointer and nothing is copied; the launch
+    // goes to `stream` and the call returns without waiting for it, or to the scene's own stream (null) and waits.
+    // Host buffers: workspace, copies and a wait, as trace_rays.
+    void query_rays(const double* rays, const double* t_max, size_t n, bool device, bool global_scene, bool any_hit, bool no_media, void* stream,
+                    double* hits, uint8_t* occluded);
     // First-hit guide buffers of the local rows (k_guides): 10 doubles per pixel {albedo, normal, position, t} and,
     // when rays_out is non-NULL, the 7 doubles of every pixel-centre ray; host buffers, or device ones with RT_OUT_DEVICE.
     void render_guides(const CameraRec<double>& cam, const RenderParams& p, double* guides, double* rays_out);

@@ -457,6 +457,38 @@ void Renderer::trace_rays(const double* rays, size_t n, bool global_scene, doubl
     HIP_OK(hipStreamSynchronize(st));
 }
 
+void Renderer::query_rays(const double* rays, const double* t_max, size_t n, bool device, bool global_scene, bool any_hit, bool no_media,
+                          void* stream, double* hits, uint8_t* occluded) {
+    upload();
+    Impl& I = *impl_;
+    const DeviceScene<double>& ds = I.s64;
+    if (n == 0) return;
+    if (n > (1u << 30)) throw std::runtime_error("too many rays");
+    hipStream_t st = (device && stream) ? static_cast<hipStream_t>(stream) : I.own_stream;
+    const uint32_t nn = static_cast<uint32_t>(n);
+    if (device) {  // the caller's buffers as they are: no workspace, no copy
+        if (any_hit) launch_occlude_rays(ds, global_scene, st, rays, t_max, nn, occluded);
+        else launch_query_rays(ds, global_scene, st, rays, t_max, nn, no_media, hits);
+        HIP_OK(hipGetLastError());
+        if (!stream) HIP_OK(hipStreamSynchronize(st));  // the scene's own stream: nobody else can wait on it
+        return;
+    }
+    // host buffers: [rays][t_max][hits or occluded] in the workspace (each part 8-byte aligned)
+    const size_t in_b = sizeof(double) * 7 * n, tm_b = t_max ? sizeof(double) * n : 0;
+    const size_t out_b = any_hit ? n : sizeof(double) * RT_HIT_DOUBLES * n;
+    char* base = static_cast<char*>(I.workspace(in_b + tm_b + out_b));
+    double* d_rays = reinterpret_cast<double*>(base);
+    double* d_tm = t_max ? reinterpret_cast<double*>(base + in_b) : nullptr;
+    char* d_out = base + in_b + tm_b;
+    HIP_OK(hipMemcpyAsync(d_rays, rays, in_b, hipMemcpyHostToDevice, st));
+    if (t_max) HIP_OK(hipMemcpyAsync(d_tm, t_max, tm_b, hipMemcpyHostToDevice, st));
+    if (any_hit) launch_occlude_rays(ds, global_scene, st, d_rays, d_tm, nn, reinterpret_cast<uint8_t*>(d_out));
+    else launch_query_rays(ds, global_scene, st, d_rays, d_tm, nn, no_media, reinterpret_cast<double*>(d_out));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(any_hit ? static_cast<void*>(occluded) : static_cast<void*>(hits), d_out, out_b, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+}
+
 void Renderer::render_guides(const CameraRec<double>& cam, const RenderParams& p, double* guides, double* rays_out) {
     upload();
     Impl& I = *impl_;

@@ -25,6 +25,8 @@
  *   dynamic_gui refresh per row / square     gui.cpp:25-58,      rt_render_progressive(..., callback, user, ...)
  *                                            engine.h:88,307,353
  *   hittable_list::hit(r, 0.001, inf, rec)   hittable_list.cpp:5 rt_trace_rays(scene, rays, n, flags, t, normals)
+ *   hittable_list::hit(r, t_min, t_max, rec)  hittable_list.cpp:5 rt_query_rays(scene, &q, rays, t_max, n, hits, occluded): the
+ *     with the full hit_record                hittable.h:9-23       whole record per ray (t_min = 0.001), or any-hit occlusion
  *   (scene construction every run)           scene_manager.cpp,  rt_scene_save / rt_scene_load (flat-scene files)
  *                                            mesh.h, bvh.cpp
  *   (none: engine_mode::adaptive interpolates     engine.h:96-333  rt_render_guides + rt_denoise, or rt_render_denoised
@@ -58,7 +60,9 @@ extern "C" {
  * ART_MULTI_TIMEOUT_MS); rt_stats.kernel_features / kernel_textures / kernel_lds_mode name the persistent kernel a
  * render ran; rt_multi_create uploads the scene to every device before it returns.
  * Additive since ABI 5 (the version stays 5): rt_render_guides, rt_denoise, rt_render_denoised, rt_denoise_params,
- * RT_GUIDE_DOUBLES, RT_DN_NO_DEMODULATE; rt_render_noise_target, rt_noise_params, rt_noise_result. */
+ * RT_GUIDE_DOUBLES, RT_DN_NO_DEMODULATE; rt_render_noise_target, rt_noise_params, rt_noise_result; rt_query_rays,
+ * rt_query_params, RT_Q_ANY_HIT, RT_Q_NO_MEDIA, RT_HIT_DOUBLES (ray queries with the hit record, a per-ray t_max, occlusion
+ * queries, device buffers and a caller's stream), option query.any_sorted. */
 #define RT_ABI_VERSION 5
 
 /* return codes */
@@ -163,6 +167,8 @@ int rt_device_count(void);
  *   renders after the call (kernel-selection switches for A/B; images are identical either way);
  *   denoise.lds_iterations (2; how many of rt_denoise's first iterations -- tap spacings 1, 2 -- read their taps from an
  *   LDS tile instead of loading each directly; 0..2, the result is identical either way);
+ *   query.any_sorted (0; rt_query_rays' any-hit walk takes a node's children in node order, without the closest search's
+ *   sorting network; 1 = nearest first; the answers are identical either way, DESIGN.md 4.7 measured both);
  *   multi.timeout_ms (the RCCL deadline; inf = none), multi.rccl_blocking (0; 1 = blocking communicators, diagnosis:
  *   gives up the deadline and the error-path protection);
  *   test.fault_workspace_bytes (0 = off; N refuses workspace growth beyond N bytes), test.fault_gather_abort (0; 1 = the
@@ -211,6 +217,46 @@ int rt_render_progressive(rt_scene* scene, const rt_camera* cam, const rt_params
  * NULL): n x 3 face normals as hit_record holds them (set_face_normal, hittable.h:18-22), 0 on a miss.  Ray i draws
  * its constant_medium uniforms from the PCG stream keyed (seed 0, pixel i, sample 0).  Host buffers; blocking. */
 int rt_trace_rays(rt_scene* scene, const double* rays, int64_t n, int32_t flags, double* t_out, double* normal_out);
+/* rt_query_rays (additive since ABI 5): hittable_list::hit(r, 0.001, t_max[i], rec) of n rays (rays as rt_trace_rays takes
+ * them; t_max: n doubles, or NULL for +inf) with the whole hit_record, or as an occlusion query.  t_min is always 0.001
+ * (the traversal's packed sort keys need a positive t_min).  A t_max below 0.001 finds nothing; a NaN t_max is undefined.
+ * Closest mode (hits non-NULL, occluded NULL, no RT_Q_ANY_HIT): hits receives RT_HIT_DOUBLES per ray:
+ *   [0]     t          hit distance; with t_max NULL and no RT_Q_NO_MEDIA, t and normal equal rt_trace_rays' bit for bit
+ *   [1..3]  normal     hit_record::normal (set_face_normal, hittable.h:18-22: against the ray)
+ *   [4..6]  point      hit_record::p
+ *   [7, 8]  u, v       as the primitive's hit() sets them: a static sphere (get_sphere_uv, sphere.h:24-37, with glibc's
+ *                      acos / atan2 restated), a triangle (barycentric, triangle.h:83-84), an aarect and each side of a
+ *                      box (aarect.cpp:11-12, :29-30, :47-48) -- for every material, image-textured or not.  0 where the
+ *                      reference sets none: a moving sphere (moving_sphere.h) and a constant_medium event
+ *   [9]     front_face 1.0 or 0.0
+ *   [10]    prim       the compiled primitive reference (type:2 | index:30) as an exact double: opaque, stable for one
+ *                      rt_scene, equal for two rays iff they hit the same primitive; -2 for a constant_medium event
+ *   [11]    mat        the compiled material index in [0, rt_scene_info.materials) (a medium event: its isotropic one)
+ *   A miss: t = +inf, normal 0, point +inf, u = v = 0, front_face 0, prim = mat = -1.
+ *   Ray i draws its constant_medium uniforms from the PCG stream keyed (seed 0, pixel i, sample 0), as rt_trace_rays.
+ *   RT_Q_NO_MEDIA: constant_medium objects are skipped (and draw nothing): the closest surface.
+ * Any-hit mode (RT_Q_ANY_HIT, occluded non-NULL, hits NULL): occluded[i] = 1 iff some non-medium primitive is accepted by
+ *   its own hit test in [0.001, t_max[i]], else 0 -- shadow, visibility and ambient-occlusion rays.  Media never occlude.
+ *   The walk stops at the first accepted primitive; which one that is depends on the tree, the byte does not.
+ * Buffers: host pointers, and the call blocks (workspace and copies, as rt_trace_rays).  With RT_OUT_DEVICE rays, t_max,
+ *   hits and occluded are device pointers on the scene's device, used in place (no workspace, no copy), and the kernel
+ *   is enqueued on q->stream: the call returns once it is enqueued, WITHOUT waiting -- the results are ready when that
+ *   stream reaches the point, and the buffers must stay alive until then.  With q->stream NULL it runs on the scene's own
+ *   stream and the call waits for it; that stream is ordered after no other, so rays and t_max must be complete when
+ *   the call is made.  The first call on a scene uploads it (blocking) in either case.
+ * RT_GLOBAL_SCENE: never the LDS scene image (A/B and parity tests).  RT_E_INVALID, before any device work: scene or q
+ * NULL; n < 0 or n > 2^30; rays NULL with n > 0; flag bits other than the four named; both of hits / occluded given, or
+ * neither; RT_Q_ANY_HIT without occluded, or occluded without RT_Q_ANY_HIT.  n = 0 is RT_OK and touches nothing. */
+#define RT_Q_ANY_HIT 512    /* occlusion query: stop at the first accepted hit */
+#define RT_Q_NO_MEDIA 1024  /* constant_medium objects are skipped (implied by RT_Q_ANY_HIT) */
+#define RT_HIT_DOUBLES 12   /* t, normal[3], point[3], u, v, front_face, prim, mat */
+typedef struct rt_query_params { /* zero-initialised = closest hit, host buffers, scene's stream */
+    int32_t flags;              /* RT_OUT_DEVICE | RT_GLOBAL_SCENE | RT_Q_ANY_HIT | RT_Q_NO_MEDIA */
+    int32_t reserved;
+    void* stream;               /* hipStream_t (RT_OUT_DEVICE only), or NULL for the scene's own stream */
+} rt_query_params;
+int rt_query_rays(rt_scene* scene, const rt_query_params* q, const double* rays, const double* t_max, int64_t n, double* hits,
+                  uint8_t* occluded);
 /* Number of rows a band partition owns, and optionally their global indices (rows_out may be NULL).  Global row y
  * belongs to band set (y / band_rows) % band_count; local row ly of set r is global row
  * (ly / band_rows) * band_rows * band_count + r * band_rows + ly % band_rows. */

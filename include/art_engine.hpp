@@ -129,6 +129,26 @@ inline double get_option(const std::string& name) {
 }
 inline void save_scene(const scene& world, const std::string& path) { check(rt_scene_save(world.objects.get(), path.c_str()), "save_scene"); }
 
+// Ray queries (rt_query_rays): hittable_list::hit(r, 0.001, t_max[i], rec) of n rays {ox, oy, oz, dx, dy, dz, time}
+// against a compiled world.  query_rays fills n * RT_HIT_DOUBLES doubles (t, normal, point, u, v, front_face, prim, mat;
+// include/art.h); occluded_rays n bytes, 1 where some non-medium primitive lies in [0.001, t_max[i]].  t_max may be
+// nullptr (+inf).  flags: RT_GLOBAL_SCENE, RT_Q_NO_MEDIA (closest mode), and RT_OUT_DEVICE with `stream` for device
+// buffers -- the call then returns once the kernel is enqueued on a non-null stream.
+inline void query_rays(const scene& world, const double* rays, const double* t_max, std::int64_t n, double* hits, std::int32_t flags = 0,
+                       void* stream = nullptr) {
+    rt_query_params q{};
+    q.flags = flags & ~RT_Q_ANY_HIT;
+    q.stream = stream;
+    check(rt_query_rays(world.objects.get(), &q, rays, t_max, n, hits, nullptr), "query_rays");
+}
+inline void occluded_rays(const scene& world, const double* rays, const double* t_max, std::int64_t n, std::uint8_t* occluded,
+                          std::int32_t flags = 0, void* stream = nullptr) {
+    rt_query_params q{};
+    q.flags = flags | RT_Q_ANY_HIT;
+    q.stream = stream;
+    check(rt_query_rays(world.objects.get(), &q, rays, t_max, n, nullptr, occluded), "occluded_rays");
+}
+
 // The engine with a runtime image size (the reference fixes W, H, C at compile time: engine<W,H,C> below); samples
 // per pixel and max depth are the reference's tracer_constants (tracer_constants.h:12-13) as arguments with the same
 // defaults.
