@@ -611,8 +611,8 @@ __device__ __forceinline__ bool hit_lds_slot(const uint8_t* lds, uint32_t slot, 
 // [6] traversals, [7] hit_sphere tests with disc >= 0; [32..45] k_paths_g's surface branches (wave iterations, lanes):
 // sphere u,v, transform unwinds, medium hits, box/rect record reloads, spheres, box/rect from the carried material,
 // world_surface calls; [46] leaf phases (wave), [47] the wave iterations a wave-cooperative leaf test would need
-// (sum over leaf phases of ceil(the phase's leaf tests / the lanes still traversing)); [48..51] k_paths' first-bounce
-// rounds: cycles, batches, lanes that traced a camera ray, ring entries appended.
+// (sum over leaf phases of ceil(the phase's leaf tests / the lanes still traversing)); [48..51] k_paths' batches:
+// cycles, batches, lanes that traced a camera ray, pool entries pushed.
 constexpr int kArtStats = 52;
 __device__ unsigned long long g_art_stats[kArtStats];
 __device__ __forceinline__ void stat_wave(int k) {

@@ -1,65 +1,58 @@
 // k_paths.hip — k_paths, the persistent-path kernel of the LDS scene (the benchmark kernel), and its launcher, in
 // their own object: the Makefile compiles it under PATHS_SCHED with ART_LDS_LEAF_NOREF=$(PATHS_NOREF).
 #include "launch.h"
+#include "path_pool.h"
 #include "path_work.h"
 
 namespace art {
 
 // Persistent-path variant of the fused LDS scene (EXT_MEGA): one launch traces a whole pass.  Every lane owns one
-// path at a time and keeps it in registers from its camera ray to its end (engine.h:447-466 flattened: trace,
-// shade_hit_lds, repeat until a miss, an absorption, a light or max_depth), then writes the slot's radiance and takes
-// the next slot -- no path records, queues or per-depth launches, and the deep bounces of old paths share the waves
+// path at a time and keeps it in registers to its end (engine.h:447-466 flattened: trace, shade_hit_lds, repeat until
+// a miss, an absorption, a light or max_depth; a path that a batch displaces waits in the wave's pool, below), then
+// writes the slot's radiance -- no path records, queues or per-depth launches, and the deep bounces of old paths share the waves
 // with the first bounces of new ones instead of running as a tail of nearly empty launches.  Slots are claimed in
 // increasing order in wave chunks of PassGeom::chunk from one counter (one atomic per chunk).  The bounce arithmetic
 // and the RNG draws are those of the fused k_extend, so images are bit-identical to the wavefront variants.
 // The slots a wave claims per atomic on the pass counter: PassGeom::chunk = path_chunk (pass_plan.h).
-// First-bounce pool: a path start is run by the whole wave for however few lanes start a path (~a third of them per
-// round), so paths are started 64 at a time -- one per lane, converged -- in a round of their own: the wave claims 64
+// Path start: a path start is run by the whole wave for however few lanes start a path (~a third of them per round),
+// so paths are started 64 at a time -- one per lane, converged -- in a round of their own, a batch: the wave claims 64
 // consecutive slots, generates their camera rays and traces and shades their first segment with the loop's own trace
 // and shading code while the 64 rays are still together (sample-major slots: one 8x8-pixel patch; entry-major: one
 // pixel -- nearly identical traversals, instead of one lane each in waves of unrelated secondary rays).  A path that
-// ends there (miss, light, absorbed, max_depth 1) writes its radiance; one that continues is appended, compacted, to
-// a per-wave ring in global memory as it stands after the bounce (scattered ray, throughput, RNG state, slot), and a
-// lane that falls idle loads the next ring entry and goes on at depth 1.  The paths the lanes hold meanwhile are
-// parked in a per-lane area behind the wave's ring for the round (plain vector stores and loads; their registers are
-// the batch's), so the kernel keeps one trace and one shading site and its register count.
-// ART_POOL_RING: ring entries per wave.  A batch runs whenever 64 entries are free (a batch may append fewer, a sky
-// tile none); a round with more takers than entries leaves the rest idle for that round.  Measured for the camera-ray
-// ring this one replaces (r3m, scene 1, PMC per segment; XCD-contiguous rings): HBM reads 3.50 B (128 entries) ->
-// 0.10 B (96), writes 33.5 -> 27.9 B, Msamples/s +0.4 % (within the run-to-run spread).
-#ifndef ART_POOL_RING
-#define ART_POOL_RING 96
-#endif
-constexpr uint32_t kPoolRing = ART_POOL_RING;
-static_assert(kPoolRing >= 96 && kPoolRing <= 128, "a ring holds the unread part of one batch and a whole new one");
-struct __align__(16) PoolRay {  // a path after its first bounce: six 16-B pieces
+// ends there (miss, light, absorbed, max_depth 1) writes its radiance; one that continues stays in its lane, in
+// registers, and goes on at depth 1 in the next round.  The paths the lanes held before the batch are pushed,
+// compacted, onto a per-wave LIFO pool in global memory (ray, throughput, RNG state, slot, depth), and a lane that falls
+// idle in an ordinary round pops one.  A batch is due when kBatchIdle idle lanes would find the pool empty
+// (path_pool.h), so the pool holds at most kPoolBound entries and its hot part is the few on top.  One trace and one
+// shading site, and the register count of the loop without batches.
+struct __align__(16) PoolRay {  // a displaced path: six 16-B pieces
     double2 a, b, c;  // (ox,oy) (oz,dx) (dy,dz)
     double2 d, e;     // (tm,Tr) (Tg,Tb)
     uint64_t rng;
-    uint32_t slot, pad;
+    uint32_t slot, depth;
 };
-static_assert(sizeof(PoolRay) == 96, "ring entries and parked lanes are six 16-B pieces");
-constexpr uint32_t kPoolPark = 64;  // PoolRay-sized records behind a wave's ring: the parked path of each lane
-// A wave's ring.  Fields other than the pointer are wave-uniform.  batch(), append(), park() and unpark() are called
-// by the whole wave in a first-bounce round; take() by the idle lanes of an ordinary round.  An entry is read at least
-// one round after its stores: a first-bounce round ends with s_waitcnt vmcnt(0).
-struct RayRing {
-    PoolRay* ring;
-    uint32_t head, tail;    // positions consumed / produced
+static_assert(sizeof(PoolRay) == 96, "pool entries are six 16-B pieces");
+// A wave's pool.  Fields other than the pointer are wave-uniform.  batch() and push() are called by the whole wave in
+// a batch round, pop() by the idle lanes of an ordinary round.  Memory ordering rests on the s_waitcnt vmcnt(0) that
+// follows the trace of every round: a round's pushes and pops are issued before its trace, so (1) an entry is loaded
+// at least one round after its stores completed, and (2) a slot is overwritten only in a round after the one whose
+// load read it, when that load has completed.  Nothing after the trace touches the pool, so a round needs no wait
+// at its end.
+struct PathPool {
+    PoolRay* base;
+    uint32_t count;         // entries held
     uint32_t cur, end;      // the wave's claimed slot chunk [cur, end)
     bool exhausted;         // every slot of the pass is in a batch
-    // wave w of block b: the rings of one XCD's blocks are contiguous (blocks go to the 8 XCDs round
-    // robin, block b to XCD b % 8), so each XCD's rings spread over all of its L2's sets instead of every block's
-    // chunk landing on the same sets (block-major rings of one XCD lie 8 chunks apart: a power-of-two stride)
+    // wave w of block b: the pools of one XCD's blocks are contiguous (blocks go to the 8 XCDs round
+    // robin, block b to XCD b % 8), so each XCD's pools spread over all of its L2's sets instead of every block's
+    // chunk landing on the same sets (block-major pools of one XCD lie 8 chunks apart: a power-of-two stride)
     __device__ __forceinline__ void init(void* pool, uint32_t block, uint32_t nblocks, uint32_t waves_per_block, uint32_t w) {
         const uint32_t per_xcd = (nblocks + kXcds - 1) / kXcds;
         const uint32_t wave = ((block % kXcds) * per_xcd + block / kXcds) * waves_per_block + w;
-        ring = static_cast<PoolRay*>(pool) + static_cast<size_t>(wave) * (kPoolRing + kPoolPark);
-        head = tail = cur = end = 0;
+        base = static_cast<PoolRay*>(pool) + static_cast<size_t>(wave) * kPoolCap;
+        count = cur = end = 0;
         exhausted = false;
     }
-    // a first-bounce round is due: the ring has room for a whole batch's paths
-    __device__ __forceinline__ bool room() const { return !exhausted && tail - head <= kPoolRing - 64u; }
     // Claims the next 64 slots and generates their camera rays: true for a lane whose slot is a pixel of the pass
     // (st: the new path, q: its slot); a padding slot of a partial tile or a slot >= P does nothing.
     __device__ __forceinline__ bool batch(const PassGeom& sg, const CameraRec<double>& sc, uint32_t* next_slot, uint32_t lane, PathState<double>& st,
@@ -85,11 +78,10 @@ struct RayRing {
         st.T = mk(1.0, 1.0, 1.0);
         return true;
     }
-    // The batch's continuing paths, compacted: position = tail + the lane's rank among them.
-    __device__ __forceinline__ void append(bool cont, uint64_t below, const PathState<double>& st, uint32_t q) {
-        const uint64_t m = __ballot(cont);
-        if (cont) {
-            PoolRay& e = ring[(tail + static_cast<uint32_t>(__popcll(m & below))) % kPoolRing];
+    // The paths a batch displaces, compacted: the busy lane of rank r among `m` stores at pool_push_pos(count, r).
+    __device__ __forceinline__ void push(uint64_t m, uint32_t rank, bool busy, const PathState<double>& st, uint32_t q, int depth) {
+        if (busy) {
+            PoolRay& e = base[pool_push_pos(count, rank)];
             e.a = make_double2(st.ray.o.x, st.ray.o.y);
             e.b = make_double2(st.ray.o.z, st.ray.d.x);
             e.c = make_double2(st.ray.d.y, st.ray.d.z);
@@ -97,15 +89,14 @@ struct RayRing {
             e.e = make_double2(st.T.y, st.T.z);
             e.rng = st.rng;
             e.slot = q;
+            e.depth = static_cast<uint32_t>(depth);
         }
-        tail += static_cast<uint32_t>(__popcll(m));
+        count += static_cast<uint32_t>(__popcll(m));
+        __asm__ volatile("" ::: "memory");  // the stores are issued before the batch's camera rays and trace
     }
-    // The idle lane of rank `rank`: 1 = a path goes on after its first bounce (st, q), 0 = the ring ran dry this round
-    // (the lane idles a round), 2 = the pass is drained.
-    __device__ __forceinline__ int take(uint32_t rank, PathState<double>& st, uint32_t& q) const {
-        const uint32_t pos = head + rank;
-        if (pos >= tail) return exhausted ? 2 : 0;
-        const PoolRay& e = ring[pos % kPoolRing];
+    // The idle lane of rank `rank` < npop takes the entry pool_pop_pos(count, rank); the caller lowers count by npop.
+    __device__ __forceinline__ void pop(uint32_t rank, PathState<double>& st, uint32_t& q, int& depth) const {
+        const PoolRay& e = base[pool_pop_pos(count, rank)];
         const double2 a = e.a, b = e.b, c = e.c, d = e.d, f = e.e;
         st.ray.o = mk(a.x, a.y, b.x);
         st.ray.d = mk(b.y, c.x, c.y);
@@ -113,34 +104,7 @@ struct RayRing {
         st.T = mk(d.y, f.x, f.y);
         st.rng = e.rng;
         q = e.slot;
-        return 1;
-    }
-    // after the round's take(): n entries consumed
-    __device__ __forceinline__ void advance(uint32_t n) { head = min(head + n, tail); }
-    // The lane's path for the length of a first-bounce round, piece-major behind the ring (each piece of the wave is
-    // 1 KiB contiguous).  The compiler barriers keep the values dead between the stores and the loads.
-    __device__ __forceinline__ void park(uint32_t lane, const PathState<double>& st, uint32_t q, int depth) const {
-        double2* p = reinterpret_cast<double2*>(ring + kPoolRing) + lane;
-        p[0 * 64] = make_double2(st.ray.o.x, st.ray.o.y);
-        p[1 * 64] = make_double2(st.ray.o.z, st.ray.d.x);
-        p[2 * 64] = make_double2(st.ray.d.y, st.ray.d.z);
-        p[3 * 64] = make_double2(st.ray.tm, st.T.x);
-        p[4 * 64] = make_double2(st.T.y, st.T.z);
-        p[5 * 64] = make_double2(__longlong_as_double(static_cast<long long>(st.rng)),
-                                 __hiloint2double(depth, static_cast<int>(q)));
-        __asm__ volatile("" ::: "memory");
-    }
-    __device__ __forceinline__ void unpark(uint32_t lane, PathState<double>& st, uint32_t& q, int& depth) const {
-        __asm__ volatile("" ::: "memory");
-        const double2* p = reinterpret_cast<const double2*>(ring + kPoolRing) + lane;
-        const double2 a = p[0 * 64], b = p[1 * 64], c = p[2 * 64], d = p[3 * 64], e = p[4 * 64], f = p[5 * 64];
-        st.ray.o = mk(a.x, a.y, b.x);
-        st.ray.d = mk(b.y, c.x, c.y);
-        st.ray.tm = d.x;
-        st.T = mk(d.y, e.x, e.y);
-        st.rng = static_cast<uint64_t>(__double_as_longlong(f.x));
-        q = static_cast<uint32_t>(__double2loint(f.y));
-        depth = __double2hiint(f.y);
+        depth = static_cast<int>(e.depth);
     }
 };
 __global__ __launch_bounds__(kBlockL, 1) void k_paths(DevScene<double> S0, PassGeom g, CameraRec<double> cam, Work<double> w, uint32_t* next_slot) {
@@ -182,7 +146,7 @@ __global__ __launch_bounds__(kBlockL, 1) void k_paths(DevScene<double> S0, PassG
     const uint32_t lane = __lane_id();
     const uint64_t below = (1ull << lane) - 1ull;
     const V3<R> bg = mk(S.bg[0], S.bg[1], S.bg[2]);
-    bool busy = false, drained = false;
+    bool busy = false;
     uint32_t q = 0;
     int depth = 0;
     PathState<R> st;
@@ -190,38 +154,37 @@ __global__ __launch_bounds__(kBlockL, 1) void k_paths(DevScene<double> S0, PassG
 #ifdef ART_STATS
     unsigned long long tm_load = 0, tm_trace = 0, tm_shade = 0, tm_app = 0, tm_fb = 0, tm_prev = __builtin_amdgcn_s_memtime();
 #endif
-    RayRing rr;
-    rr.init(w.pool, blockIdx.x, gridDim.x, B / 64, threadIdx.x / 64);
+    PathPool pp;
+    pp.init(w.pool, blockIdx.x, gridDim.x, B / 64, threadIdx.x / 64);
     for (;;) {
-        // A round is either a first-bounce round (the ring has room for a batch: all 64 lanes start a path, the paths
-        // they hold are parked) or an ordinary one (idle lanes take ring entries, busy lanes trace their segment).
-        // `act`: the lane traces and shades this round.  The ring and the area are private to the wave and no lane or
-        // wave waits on another; every first-bounce round consumes 64 slots, so their number is bounded by the pass.
-        const bool fb = rr.room();
-        const bool held = __ballot(busy) != 0;
+        // A round is either a batch (enough idle lanes would find the pool empty: the busy lanes push their paths and
+        // all 64 lanes start a new one) or an ordinary one (idle lanes pop entries, busy lanes trace their segment).
+        // The entries a batch leaves in the pool stay there: popping them would only push them again.
+        // `act`: the lane traces and shades this round.  The pool is private to the wave and no lane or wave waits on
+        // another; every batch consumes 64 slots, so their number is bounded by the pass.
+        const uint64_t m_busy = __ballot(busy);
+        const uint32_t n_idle = 64u - static_cast<uint32_t>(__popcll(m_busy));
+        const bool fb = pool_batch_due(pp.exhausted, pp.count, n_idle);
         bool act;
         if (fb) {
-            if (held) rr.park(lane, st, q, depth);
-            act = rr.batch(s_g, s_cam, next_slot, lane, st, q);
+#ifdef ART_STATS
+            if (lane == 0) atomicAdd(&g_art_stats[51], static_cast<unsigned long long>(__popcll(m_busy)));
+#endif
+            if (m_busy) pp.push(m_busy, static_cast<uint32_t>(__popcll(m_busy & below)), busy, st, q, depth);
+            act = pp.batch(s_g, s_cam, next_slot, lane, st, q);
             depth = 0;
         } else {
-            // every idle lane takes the next ring entry (more takers than entries: the rest idle a round)
-            const uint64_t idle = __ballot(!busy && !drained);
-            if (idle) {
-                const uint32_t n = static_cast<uint32_t>(__popcll(idle));
-                const uint32_t rank = static_cast<uint32_t>(__popcll(idle & below));
-                if (!busy && !drained) {
-                    const int got = rr.take(rank, st, q);
-                    drained = got == 2;
-                    busy = got == 1;
-                    depth = 1;
+            const uint32_t npop = pool_pop_count(pp.count, n_idle);
+            if (npop) {
+                const uint32_t rank = static_cast<uint32_t>(__popcll(~m_busy & below));
+                if (!busy && rank < npop) {
+                    pp.pop(rank, st, q, depth);
+                    busy = true;
                 }
-                rr.advance(n);
-            }
-            if (__ballot(busy) == 0) {
+                pp.count -= npop;
+            } else if (m_busy == 0) {  // the pass is exhausted, the pool is empty and no lane holds a path
                 ART_TICK(tm_load);
-                if (__ballot(!drained) == 0) break;
-                continue;
+                break;
             }
             act = busy;
         }
@@ -236,7 +199,7 @@ __global__ __launch_bounds__(kBlockL, 1) void k_paths(DevScene<double> S0, PassG
             if (hitw) h.mt = reinterpret_cast<const uint32_t*>(lds + kLdsOffRef)[h.obj >> 16] >> kLdsRefMatShift;
 #endif
         }
-        // an ordinary round's ring loads are complete
+        // the round's pool stores and loads are complete (PathPool: both ordering rules rest on this wait)
         __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
         ART_TICK((fb ? tm_fb : tm_trace));
         // the whole wave draws random_in_unit_sphere for its lambertian and metal hits (material.h:33, :55), which
@@ -255,22 +218,19 @@ __global__ __launch_bounds__(kBlockL, 1) void k_paths(DevScene<double> S0, PassG
             if (!cont) store_res(w.res, q, st.L);
         }
         ART_TICK((fb ? tm_fb : tm_shade));
-        if (fb) {
 #ifdef ART_STATS
-            const uint64_t m_act = __ballot(act), m_cont = __ballot(cont);
+        if (fb) {
+            const uint64_t m_act = __ballot(act);
             if (lane == 0) {
                 atomicAdd(&g_art_stats[49], 1ull);
                 atomicAdd(&g_art_stats[50], static_cast<unsigned long long>(__popcll(m_act)));
-                atomicAdd(&g_art_stats[51], static_cast<unsigned long long>(__popcll(m_cont)));
             }
+        }
 #endif
-            rr.append(cont, below, st, q);
-            if (held) rr.unpark(lane, st, q, depth);
-            // the ring entries are stored before a later round loads them, and the parked paths are back
-            __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else if (act) {
-            if (cont) ++depth;
-            else busy = false;
+        // a batch's lanes all hold a new path or none; an ordinary round's idle lanes stay idle
+        if (fb || act) {
+            busy = cont;
+            ++depth;
         }
         ART_TICK((fb ? tm_fb : tm_app));
     }
@@ -296,7 +256,7 @@ void launch_paths(int num_cu, hipStream_t st, const DevScene<double>& S, const P
     hipLaunchKernelGGL(k_paths, dim3(num_cu), dim3(kBlockL), lds, st, S, g, cam, w, next_slot);
 }
 size_t pool_bytes(int variant, int num_cu) {
-    return variant == EXT_MEGA ? sizeof(PoolRay) * (kPoolRing + kPoolPark) * kPoolWavesPerCu * static_cast<size_t>(num_cu) : 0;
+    return variant == EXT_MEGA ? sizeof(PoolRay) * kPoolCap * kPoolWavesPerCu * static_cast<size_t>(num_cu) : 0;
 }
 
 }  // namespace art

@@ -703,7 +703,7 @@ int extend_variant(const DeviceScene<double>& ds, int flags) {
 }
 // The persistent kernels' waves index the camera-ray rings (kPoolWavesPerCu per CU allocated)
 static void check_ring_waves(int blocks, int block, int num_cu) {
-    const size_t padded = (static_cast<size_t>(blocks) + kXcds - 1) / kXcds * kXcds;  // RayRing::init's XCD-major index
+    const size_t padded = (static_cast<size_t>(blocks) + kXcds - 1) / kXcds * kXcds;  // the XCD-major wave index (PathPool::init)
     if (padded * static_cast<size_t>(block / 64) > static_cast<size_t>(num_cu) * kPoolWavesPerCu)
         throw std::runtime_error("internal: persistent grid larger than the camera-ray rings");
 }

@@ -46,6 +46,6 @@ void launch_guides(const DeviceScene<double>& ds, int flags, hipStream_t st, con
 // k_paths.hip
 void launch_paths(int num_cu, hipStream_t st, const DevScene<double>& S, const PassGeom& g, const CameraRec<double>& cam, const Work<double>& w,
                   uint32_t* next_slot);
-size_t pool_bytes(int variant, int num_cu);  // the camera-ray pool of `variant` (k_paths' rings; 0 for every other)
+size_t pool_bytes(int variant, int num_cu);  // the path pools of `variant` (k_paths' PathPool, kPoolCap entries per wave; 0 for every other)
 
 }  // namespace art

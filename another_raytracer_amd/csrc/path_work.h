@@ -182,7 +182,7 @@ struct Work {
     uint32_t* counters;         // [(depth * kQueueKinds + kind) * kShards + shard] * kCounterStride
     unsigned long long* segments;
     double* acc;                // local pixels * 3
-    void* pool;                 // k_paths first-bounce rings: kPoolRing + kPoolPark PoolRays per wave
+    void* pool;                 // k_paths path pools: the paths a batch displaces, kPoolCap PoolRays per wave (path_pool.h)
 };
 template <class R>
 __host__ __device__ __forceinline__ uint32_t* counter(const Work<R>& w, int d, int kind, int s) {
@@ -482,10 +482,10 @@ __device__ __forceinline__ void load_lds_image(const uint8_t* image, uint8_t* ld
 #define ART_TICK(acc)
 #endif
 
-// k_paths' camera-ray rings (k_paths.hip), sized per CU by the host.  XCD-contiguous rings: measured (r3m, 128-entry rings) HBM reads 11.3 -> 3.5 B per segment against the
-// block-major layout, Msamples/s unchanged
+// k_paths' path pools (k_paths.hip) and k_paths_g's camera-ray rings, sized per CU by the host.  XCD-contiguous: measured (r3m, 128-entry camera-ray rings in k_paths)
+// HBM reads 11.3 -> 3.5 B per segment against the block-major layout, Msamples/s unchanged
 constexpr uint32_t kXcds = 8;  // MI355X
-constexpr uint32_t kPoolWavesPerCu = 32;  // rings allocated per CU: the most waves a CU holds
+constexpr uint32_t kPoolWavesPerCu = 32;  // pools / rings allocated per CU: the most waves a CU holds
 __host__ __device__ constexpr size_t paths_stack_bytes(uint32_t stack) { return (sizeof(int16_t) * stack * kBlockL + 15u) & ~size_t(15); }
 constexpr size_t kJumpBytes = sizeof(JumpEntry) * kJumpEntries;
 // The world list and object records, copied into LDS by every k_paths block: each trace walks them, and from global

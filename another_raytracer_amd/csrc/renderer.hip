@@ -389,7 +389,7 @@ static void render_impl(Renderer::Impl& I, DeviceScene<double>& ds, const Camera
                          "coop-sphere %.3f texture+unit %.3f scatter %.3f)\n",
                          st[8] / tt, st[9] / tt, (st[10] + st[24] + st[25] + st[26]) / tt, st[11] / tt, st[24] / tt, st[25] / tt, st[26] / tt, st[10] / tt);
         if (st[49] > 0)
-            std::fprintf(stderr, "ART_STATS first bounce: cycles %.3f batches %llu camera rays %llu (util %.3f) entries appended %llu (%.2f per batch)\n",
+            std::fprintf(stderr, "ART_STATS batches: cycles %.3f batches %llu camera rays %llu (util %.3f) entries pushed %llu (%.2f per batch)\n",
                          st[48] / tt, st[49], st[50], st[50] / (64.0 * st[49]), st[51], double(st[51]) / st[49]);
         if (st[28] + st[30] > 0)
             std::fprintf(stderr, "ART_STATS texture evaluations (wave iterations, lanes): noise %llu %llu image %llu %llu\n", st[28], st[29], st[30], st[31]);
