@@ -109,7 +109,7 @@ void fill_stats(const art::RenderStats& st, rt_stats* stats) {
     stats->kernel_textures = st.kernel_textures;
     stats->kernel_lds_mode = st.kernel_lds_mode;
 }
-art::CameraRec<double> camera_of(const rt_camera* cam) {
+art::CameraRec camera_of(const rt_camera* cam) {
     return art::make_camera(cam->lookfrom, cam->lookat, cam->vup, cam->vfov, cam->aspect, cam->aperture, cam->focus_dist, cam->time0, cam->time1);
 }
 int multi_from_graph(art::SceneGraph graph, const int* devices, int ngpus, rt_multi** out) {

@@ -1,8 +1,8 @@
-// device.h — device-side math, RNG, intersection and shading routines (templated on the real type R).
+// device.h — device-side math, RNG, intersection and shading routines, in f64 (the only arithmetic).
 //
 // Every routine restates the reference function it cites with the SAME operation order (v/t == (1/t)*v, dot summed
-// left to right, ...), so that the f64 instantiation reproduces the CPU restatement (oracle/restate.cpp, pcg mode)
-// to the last bit up to libm-vs-OCML transcendental ulps.  The f32 instantiation runs the identical code in float.
+// left to right, ...), so that it reproduces the CPU restatement (oracle/restate.cpp, pcg mode) to the last bit up to
+// libm-vs-OCML transcendental ulps.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,16 +17,15 @@
 namespace art {
 
 // ------------------------------------------------------------------------------------------------ vec3 (core/vec3.h)
-template <class R>
 struct V3 {
-    R x, y, z;
+    double x, y, z;
 };
-template <class R> __device__ __forceinline__ V3<R> mk(R a, R b, R c) { return V3<R>{a, b, c}; }
-template <class R> __device__ __forceinline__ V3<R> operator+(V3<R> u, V3<R> v) { return {u.x + v.x, u.y + v.y, u.z + v.z}; }
-template <class R> __device__ __forceinline__ V3<R> operator-(V3<R> u, V3<R> v) { return {u.x - v.x, u.y - v.y, u.z - v.z}; }
-template <class R> __device__ __forceinline__ V3<R> operator-(V3<R> u) { return {-u.x, -u.y, -u.z}; }
-template <class R> __device__ __forceinline__ V3<R> operator*(V3<R> u, V3<R> v) { return {u.x * v.x, u.y * v.y, u.z * v.z}; }
-template <class R> __device__ __forceinline__ V3<R> operator*(R t, V3<R> v) { return {t * v.x, t * v.y, t * v.z}; }
+__device__ __forceinline__ V3 mk(double a, double b, double c) { return V3{a, b, c}; }
+__device__ __forceinline__ V3 operator+(V3 u, V3 v) { return {u.x + v.x, u.y + v.y, u.z + v.z}; }
+__device__ __forceinline__ V3 operator-(V3 u, V3 v) { return {u.x - v.x, u.y - v.y, u.z - v.z}; }
+__device__ __forceinline__ V3 operator-(V3 u) { return {-u.x, -u.y, -u.z}; }
+__device__ __forceinline__ V3 operator*(V3 u, V3 v) { return {u.x * v.x, u.y * v.y, u.z * v.z}; }
+__device__ __forceinline__ V3 operator*(double t, V3 v) { return {t * v.x, t * v.y, t * v.z}; }
 // std::sqrt, correctly rounded (sphere.h:47, vec3.h:42 length, vec3.h:152 refract, material.h:75 and
 // constant_medium.h:61).  For x >= 2^-767 this is the compiler's own f64 sqrt expansion (hardware rsq, then two
 // Goldschmidt and two Newton fma steps) without its denormal-range scaling and its zero/inf select, which never apply
@@ -42,33 +41,31 @@ __device__ __forceinline__ double sqrt_rn(double x) {
     s = fma(fma(-s, s, x), h, s);
     return fma(fma(-s, s, x), h, s);
 }
-__device__ __forceinline__ float sqrt_rn(float x) { return sqrtf(x); }
 
-template <class R> __device__ __forceinline__ R dot(V3<R> u, V3<R> v) { return u.x * v.x + u.y * v.y + u.z * v.z; }
-template <class R> __device__ __forceinline__ R len2(V3<R> v) { return v.x * v.x + v.y * v.y + v.z * v.z; }
-template <class R> __device__ __forceinline__ V3<R> cross(V3<R> u, V3<R> v) {
+__device__ __forceinline__ double dot(V3 u, V3 v) { return u.x * v.x + u.y * v.y + u.z * v.z; }
+__device__ __forceinline__ double len2(V3 v) { return v.x * v.x + v.y * v.y + v.z * v.z; }
+__device__ __forceinline__ V3 cross(V3 u, V3 v) {
     return {u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x};
 }
-template <class R> __device__ __forceinline__ V3<R> divs(V3<R> v, R t) { return (R(1) / t) * v; }  // vec3.h:97-99: (1/t) * v
-template <class R> __device__ __forceinline__ V3<R> unit(V3<R> v) { return divs(v, sqrt_rn(len2(v))); }
-template <class R> __device__ __forceinline__ bool near_zero(V3<R> v) {  // vec3.h:49-53
-    const R s = R(1e-8);
+__device__ __forceinline__ V3 divs(V3 v, double t) { return (1.0 / t) * v; }  // vec3.h:97-99: (1/t) * v
+__device__ __forceinline__ V3 unit(V3 v) { return divs(v, sqrt_rn(len2(v))); }
+__device__ __forceinline__ bool near_zero(V3 v) {  // vec3.h:49-53
+    const double s = 1e-8;
     return fabs(v.x) < s && fabs(v.y) < s && fabs(v.z) < s;
 }
-template <class R> __device__ __forceinline__ V3<R> reflect(V3<R> v, V3<R> n) { return v - (R(2) * dot(v, n)) * n; }
-template <class R> __device__ __forceinline__ V3<R> refract(V3<R> uv, V3<R> n, R eta) {  // vec3.h:149-154
-    R cos_theta = fmin(dot(-uv, n), R(1));
-    V3<R> perp = eta * (uv + cos_theta * n);
-    V3<R> par = (-sqrt_rn(fabs(R(1) - len2(perp)))) * n;
+__device__ __forceinline__ V3 reflect(V3 v, V3 n) { return v - (2.0 * dot(v, n)) * n; }
+__device__ __forceinline__ V3 refract(V3 uv, V3 n, double eta) {  // vec3.h:149-154
+    double cos_theta = fmin(dot(-uv, n), 1.0);
+    V3 perp = eta * (uv + cos_theta * n);
+    V3 par = (-sqrt_rn(fabs(1.0 - len2(perp)))) * n;
     return perp + par;
 }
-template <class R> __device__ __forceinline__ V3<R> ld3(const R* p) { return {p[0], p[1], p[2]}; }
+__device__ __forceinline__ V3 ld3(const double* p) { return {p[0], p[1], p[2]}; }
 
-template <class R>
 struct Ray {
-    V3<R> o, d;
-    R tm;
-    __device__ __forceinline__ V3<R> at(R t) const { return o + t * d; }
+    V3 o, d;
+    double tm;
+    __device__ __forceinline__ V3 at(double t) const { return o + t * d; }
 };
 
 // ------------------------------------------------------------------------------------------------ RNG contract
@@ -83,43 +80,26 @@ __host__ __device__ inline uint64_t splitmix64(uint64_t x) {
 __host__ __device__ inline uint64_t pcg_seed(uint64_t seed, uint32_t pixel, uint32_t sample) {
     return splitmix64(((static_cast<uint64_t>(pixel) << 32) | sample) ^ splitmix64(seed));
 }
-template <class R>
-__device__ __forceinline__ R uniform(uint64_t& s) {
-    const uint64_t old = s;
-    s = old * 6364136223846793005ull + 1442695040888963407ull;
-    const uint32_t xs = static_cast<uint32_t>(((old >> 18u) ^ old) >> 27u);
-    const uint32_t rot = static_cast<uint32_t>(old >> 59u);
-    const uint32_t x = (xs >> rot) | (xs << ((32u - rot) & 31u));
-    return static_cast<R>(x >> 8) * static_cast<R>(1.0 / 16777216.0);
-}
-template <class R> __device__ __forceinline__ R uniform(uint64_t& s, R lo, R hi) { return lo + (hi - lo) * uniform<R>(s); }
-// The 24-bit integer k of the next uniform (uniform<R> == k * 2^-24): the argument of glibc_log in hit_medium.
-__device__ __forceinline__ uint32_t uniform_k(uint64_t& s) {
+// One PCG32 step: advances the state and returns the 24-bit integer k of the draw (the top 24 of its 32 output bits).
+__device__ __forceinline__ uint32_t uniform_k(uint64_t& s) {  // also the argument of glibc_log in hit_medium
     const uint64_t old = s;
     s = old * 6364136223846793005ull + 1442695040888963407ull;
     const uint32_t xs = static_cast<uint32_t>(((old >> 18u) ^ old) >> 27u);
     const uint32_t rot = static_cast<uint32_t>(old >> 59u);
     return ((xs >> rot) | (xs << ((32u - rot) & 31u))) >> 8;
 }
+__device__ __forceinline__ double uniform(uint64_t& s) { return static_cast<double>(uniform_k(s)) * (1.0 / 16777216.0); }  // k * 2^-24
+__device__ __forceinline__ double uniform(uint64_t& s, double lo, double hi) { return lo + (hi - lo) * uniform(s); }
 // uniform(s, -1, 1) = -1 + 2 * (k * 2^-24) with k < 2^24: every step is exact, so the single fma k * 2^-23 - 1 is the
 // same value
-template <class R>
-__device__ __forceinline__ R uniform_pm1(uint64_t& s) {
-    const uint64_t old = s;
-    s = old * 6364136223846793005ull + 1442695040888963407ull;
-    const uint32_t xs = static_cast<uint32_t>(((old >> 18u) ^ old) >> 27u);
-    const uint32_t rot = static_cast<uint32_t>(old >> 59u);
-    const uint32_t x = (xs >> rot) | (xs << ((32u - rot) & 31u));
-    return fma(static_cast<R>(x >> 8), static_cast<R>(1.0 / 8388608.0), R(-1));
-}
-template <class R>
-__device__ __forceinline__ V3<R> in_unit_sphere(uint64_t& s) {  // vec3.h:117-123, draws x, y, z
+__device__ __forceinline__ double uniform_pm1(uint64_t& s) { return fma(static_cast<double>(uniform_k(s)), 1.0 / 8388608.0, -1.0); }
+__device__ __forceinline__ V3 in_unit_sphere(uint64_t& s) {  // vec3.h:117-123, draws x, y, z
     for (;;) {
-        V3<R> p;
-        p.x = uniform_pm1<R>(s);
-        p.y = uniform_pm1<R>(s);
-        p.z = uniform_pm1<R>(s);
-        if (len2(p) >= R(1)) continue;
+        V3 p;
+        p.x = uniform_pm1(s);
+        p.y = uniform_pm1(s);
+        p.z = uniform_pm1(s);
+        if (len2(p) >= 1.0) continue;
         return p;
     }
 }
@@ -148,17 +128,16 @@ __host__ __device__ inline JumpEntry pcg_jump(uint32_t steps) {
 // takes the first accepted one.  A wave needs ~2 rounds instead of the ~6 serial iterations of its unluckiest lane.
 // Must be called by the whole wave (the helpers are every lane, active or not in the path loop).  jt: the jump table
 // in LDS (kJumpEntries JumpEntry).
-template <class R>
-__device__ __forceinline__ V3<R> coop_unit_sphere(bool need, uint64_t& rng, const JumpEntry* jt) {
+__device__ __forceinline__ V3 coop_unit_sphere(bool need, uint64_t& rng, const JumpEntry* jt) {
     const uint32_t lane = __lane_id();
-    V3<R> p = mk(R(0), R(0), R(0));
+    V3 p = mk(0.0, 0.0, 0.0);
     uint64_t s = rng;  // pending lanes: the state at the next untested candidate
     bool pending = false;
     if (need) {
-        p.x = uniform_pm1<R>(s);
-        p.y = uniform_pm1<R>(s);
-        p.z = uniform_pm1<R>(s);
-        if (len2(p) >= R(1)) pending = true;
+        p.x = uniform_pm1(s);
+        p.y = uniform_pm1(s);
+        p.z = uniform_pm1(s);
+        if (len2(p) >= 1.0) pending = true;
         else rng = s;
     }
     uint64_t mask = __ballot(pending);
@@ -180,11 +159,11 @@ __device__ __forceinline__ V3<R> coop_unit_sphere(bool need, uint64_t& rng, cons
         const uint32_t shi = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(owner_lane * 4, static_cast<int>(static_cast<uint32_t>(s >> 32))));
         const JumpEntry e = jt[j];
         uint64_t hs = e.a * ((static_cast<uint64_t>(shi) << 32) | slo) + e.c;
-        V3<R> c;
-        c.x = uniform_pm1<R>(hs);
-        c.y = uniform_pm1<R>(hs);
-        c.z = uniform_pm1<R>(hs);
-        const uint64_t acc = __ballot(helper && len2(c) < R(1));
+        V3 c;
+        c.x = uniform_pm1(hs);
+        c.y = uniform_pm1(hs);
+        c.z = uniform_pm1(hs);
+        const uint64_t acc = __ballot(helper && len2(c) < 1.0);
         // owners: the first accepted candidate of their k; its helper's state (hs) is the state right after it.
         // With none accepted, the state after the last helper's candidate is where the next round starts.
         const uint64_t mine = k == 64u ? acc : (acc >> (rank * k)) & ((1ull << k) - 1ull);
@@ -192,7 +171,7 @@ __device__ __forceinline__ V3<R> coop_unit_sphere(bool need, uint64_t& rng, cons
         const int src = static_cast<int>(pending ? rank * k + jstar : lane) * 4;
         const uint32_t nlo = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(src, static_cast<int>(static_cast<uint32_t>(hs))));
         const uint32_t nhi = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(src, static_cast<int>(static_cast<uint32_t>(hs >> 32))));
-        V3<R> got;
+        V3 got;
         got.x = __hiloint2double(__builtin_amdgcn_ds_bpermute(src, __double2hiint(c.x)), __builtin_amdgcn_ds_bpermute(src, __double2loint(c.x)));
         got.y = __hiloint2double(__builtin_amdgcn_ds_bpermute(src, __double2hiint(c.y)), __builtin_amdgcn_ds_bpermute(src, __double2loint(c.y)));
         got.z = __hiloint2double(__builtin_amdgcn_ds_bpermute(src, __double2hiint(c.z)), __builtin_amdgcn_ds_bpermute(src, __double2loint(c.z)));
@@ -212,23 +191,22 @@ __device__ __forceinline__ V3<R> coop_unit_sphere(bool need, uint64_t& rng, cons
 }
 
 // ------------------------------------------------------------------------------------------------ device scene view
-template <class R>
 struct DevScene {
-    const SphereRec<R>* spheres;
-    const TriRec<R>* tris;
-    const RectRec<R>* rects;
-    const BoxRec<R>* boxes;
+    const SphereRec* spheres;
+    const TriRec* tris;
+    const RectRec* rects;
+    const BoxRec* boxes;
     const uint32_t* primrefs;
     const BvhNode* nodes;
-    const ObjRec<R>* objs;
+    const ObjRec* objs;
     const int32_t* world;
-    const MatRec<R>* mats;
-    const TexRec<R>* texs;
-    const PerlinRec<R>* perlins;
+    const MatRec* mats;
+    const TexRec* texs;
+    const PerlinRec* perlins;
     const ImageRec* images;
     const uint8_t* texels;
-    const TriRec<R>* leaf_tris;  // leaf_tris[slot] = tris[index of primrefs[slot]] for triangle refs, zeros otherwise
-    const TriRec112<R>* leaf_tris112;  // the same with each triangle's plane (n, dd), for the LM 1 kernels' LDS copy
+    const TriRec* leaf_tris;  // leaf_tris[slot] = tris[index of primrefs[slot]] for triangle refs, zeros otherwise
+    const TriRec112* leaf_tris112;  // the same with each triangle's plane (n, dd), for the LM 1 kernels' LDS copy
     const PrimRec80* leaf_prims;  // leaf_prims[slot]: the record of primrefs[slot] of any type (triangle-free kernels)
     const PrimRec80* obj_prims;  // obj_prims[o] = the record of prim object o's primitive (indexed like objs)
     const uint8_t* lds_image;   // layout.h LDS scene image (nullptr unless the scene qualifies)
@@ -236,14 +214,13 @@ struct DevScene {
     uint32_t nodes_lds;         // k_paths_g LM 2: LDS byte address of the copy of nodes [0, n_lds_nodes) (top levels)
     uint32_t n_lds_nodes;
     int32_t nworld;
-    R bg[3];
+    double bg[3];
 };
 
 // sphere_uv.h's table (glibc_trig.h's constants, then its acos / atan tables) rides in front of the image records
 // (DevScene::images - kUvTableBytes, uploaded with them), so the scene view -- the kernels' argument block -- keeps its layout (a new field moved every later kernel
 // argument and cost k_paths 0.3 %)
-template <class R>
-__device__ __forceinline__ const double* uv_table(const DevScene<R>& S) {
+__device__ __forceinline__ const double* uv_table(const DevScene& S) {
     return reinterpret_cast<const double*>(reinterpret_cast<const uint8_t*>(S.images) - kUvTableBytes);
 }
 
@@ -255,23 +232,22 @@ constexpr uint32_t kMediumHit = 0xFFFFFFFFu;  // hit.prim value of a constant_me
 // theorem, e.g. Muller et al., Handbook of Floating-Point Arithmetic, 2nd ed., Thm. 4.10) -- the same bits as the
 // division, for a, x and the quotient away from the overflow/underflow ranges: 3 FLOPs instead of the ~10-instruction
 // scaled division sequence.  Callers guarantee the range (see hit_lds_slot and gen_ray).
-template <class R>
-__device__ __forceinline__ R div_rcp(R x, R a, R inv_a) {
-    const R q = x * inv_a;
+__device__ __forceinline__ double div_rcp(double x, double a, double inv_a) {
+    const double q = x * inv_a;
     return fma(fma(-q, a, x), inv_a, q);
 }
 
 // sphere.h:39-65 / moving_sphere.h:41-58 (root selection only; the surface is rebuilt in shade).  a = |d|^2 of the
 // ray; RCP: the two root divisions by a use div_rcp with inv_a = 1 / a (same bits).
-template <class R, bool RCP>
-__device__ __forceinline__ bool sphere_root(V3<R> center, R r2, const Ray<R>& r, R a, R inv_a, R tmin, R tmax, R& t) {
-    const V3<R> oc = r.o - center;
-    const R half_b = dot(oc, r.d);
-    const R c = len2(oc) - r2;
-    const R disc = half_b * half_b - a * c;
-    if (disc < R(0)) return false;
-    const R sqrtd = sqrt_rn(disc);
-    R root = RCP ? div_rcp(-half_b - sqrtd, a, inv_a) : (-half_b - sqrtd) / a;
+template <bool RCP>
+__device__ __forceinline__ bool sphere_root(V3 center, double r2, const Ray& r, double a, double inv_a, double tmin, double tmax, double& t) {
+    const V3 oc = r.o - center;
+    const double half_b = dot(oc, r.d);
+    const double c = len2(oc) - r2;
+    const double disc = half_b * half_b - a * c;
+    if (disc < 0.0) return false;
+    const double sqrtd = sqrt_rn(disc);
+    double root = RCP ? div_rcp(-half_b - sqrtd, a, inv_a) : (-half_b - sqrtd) / a;
     if (root < tmin || tmax < root) {
         root = RCP ? div_rcp(-half_b + sqrtd, a, inv_a) : (-half_b + sqrtd) / a;
         if (root < tmin || tmax < root) return false;
@@ -280,16 +256,15 @@ __device__ __forceinline__ bool sphere_root(V3<R> center, R r2, const Ray<R>& r,
     return true;
 }
 // sphere_root with the reciprocal taken where first needed: inv_a = 0 until a root division of this ray needs it
-template <class R>
-__device__ __forceinline__ bool sphere_root_lazy(V3<R> center, R r2, const Ray<R>& r, R a, R& inv_a, R tmin, R tmax, R& t) {
-    const V3<R> oc = r.o - center;
-    const R half_b = dot(oc, r.d);
-    const R c = len2(oc) - r2;
-    const R disc = half_b * half_b - a * c;
-    if (disc < R(0)) return false;
-    const R sqrtd = sqrt_rn(disc);
-    if (inv_a == R(0)) inv_a = R(1) / a;
-    R root = div_rcp(-half_b - sqrtd, a, inv_a);
+__device__ __forceinline__ bool sphere_root_lazy(V3 center, double r2, const Ray& r, double a, double& inv_a, double tmin, double tmax, double& t) {
+    const V3 oc = r.o - center;
+    const double half_b = dot(oc, r.d);
+    const double c = len2(oc) - r2;
+    const double disc = half_b * half_b - a * c;
+    if (disc < 0.0) return false;
+    const double sqrtd = sqrt_rn(disc);
+    if (inv_a == 0.0) inv_a = 1.0 / a;
+    double root = div_rcp(-half_b - sqrtd, a, inv_a);
     if (root < tmin || tmax < root) {
         root = div_rcp(-half_b + sqrtd, a, inv_a);
         if (root < tmin || tmax < root) return false;
@@ -297,12 +272,10 @@ __device__ __forceinline__ bool sphere_root_lazy(V3<R> center, R r2, const Ray<R
     t = root;
     return true;
 }
-template <class R>
-__device__ __forceinline__ bool hit_sphere_r2(V3<R> center, R r2, const Ray<R>& r, R tmin, R tmax, R& t) {  // r2 = radius * radius
-    return sphere_root<R, false>(center, r2, r, len2(r.d), R(0), tmin, tmax, t);
+__device__ __forceinline__ bool hit_sphere_r2(V3 center, double r2, const Ray& r, double tmin, double tmax, double& t) {  // r2 = radius * radius
+    return sphere_root<false>(center, r2, r, len2(r.d), 0.0, tmin, tmax, t);
 }
-template <class R>
-__device__ __forceinline__ bool hit_sphere_at(V3<R> center, R radius, const Ray<R>& r, R tmin, R tmax, R& t) {
+__device__ __forceinline__ bool hit_sphere_at(V3 center, double radius, const Ray& r, double tmin, double tmax, double& t) {
     return hit_sphere_r2(center, radius * radius, r, tmin, tmax, t);
 }
 // std::pow(x, 5) of material.h:97 (Schlick reflectance).  x^5 is carried as a double-double product (each step's
@@ -312,89 +285,80 @@ __device__ __forceinline__ bool hit_sphere_at(V3<R> center, R radius, const Ray<
 // lies within 1 ulp of refl_p (probability < 2^-28 per draw).  Ten FLOPs instead of the generic log/exp pow, whose
 // table constants also spilled registers of the persistent kernel.  x = 1 - cos(theta) is 0 or >= 2^-53, so
 // nothing underflows.
-template <class R>
-__host__ __device__ __forceinline__ R pow5(R x) {
-    const R p = x * x, pe = fma(x, x, -p);                  // x^2 = p + pe exactly
-    const R q = p * p, qe = fma(p, p, -q) + (R(2) * p) * pe;  // x^4 = q + qe (pe^2 dropped: 2^-106 relative)
-    const R r = q * x, re = fma(q, x, -r) + qe * x;         // x^5 = r + re
+__host__ __device__ __forceinline__ double pow5(double x) {
+    const double p = x * x, pe = fma(x, x, -p);                  // x^2 = p + pe exactly
+    const double q = p * p, qe = fma(p, p, -q) + (2.0 * p) * pe;  // x^4 = q + qe (pe^2 dropped: 2^-106 relative)
+    const double r = q * x, re = fma(q, x, -r) + qe * x;         // x^5 = r + re
     return r + re;
 }
 // moving_sphere.h:72-74 center(time) = center0 + ((time - time0) / (time1 - time0)) * (center1 - center0)
 // (time - time0) / (time1 - time0): x / 1 == x exactly, so the divide is skipped for the common unit shutter span
 // (every moving sphere of the reference scenes) without changing a bit.
-template <class R>
-__device__ __forceinline__ R motion_fraction(R tm, R t0, R dt) {
-    R x = tm - t0;
-    if (dt != R(1)) {
+__device__ __forceinline__ double motion_fraction(double tm, double t0, double dt) {
+    double x = tm - t0;
+    if (dt != 1.0) {
         __asm__ volatile("" : "+v"(x));  // keeps the divide inside the branch (no if-conversion into a select)
         x = x / dt;
     }
     return x;
 }
-template <class R>
-__device__ __forceinline__ V3<R> moving_center(V3<R> c0, V3<R> d, R t0, R dt, R tm) { return c0 + motion_fraction(tm, t0, dt) * d; }
-template <class R>
-__device__ __forceinline__ bool hit_sphere(const SphereRec<R>& s, const Ray<R>& r, R tmin, R tmax, R& t) {
-    V3<R> center = ld3(s.c);
+__device__ __forceinline__ V3 moving_center(V3 c0, V3 d, double t0, double dt, double tm) { return c0 + motion_fraction(tm, t0, dt) * d; }
+__device__ __forceinline__ bool hit_sphere(const SphereRec& s, const Ray& r, double tmin, double tmax, double& t) {
+    V3 center = ld3(s.c);
     if (s.flags & SPH_MOVING) center = moving_center(center, ld3(s.d), s.t0, s.dt, r.tm);
     return hit_sphere_at(center, s.r, r, tmin, tmax, t);
 }
 
 // triangle.h:22-88 (geometric test, unnormalised normal).
-template <class R>
-__device__ __forceinline__ bool hit_tri_v(V3<R> p1, V3<R> p2, V3<R> p3, const Ray<R>& r, R tmin, R tmax, R& t) {
-    const V3<R> N = cross(p2 - p1, p3 - p1);
-    const R ndd = dot(N, r.d);
-    if (fabs(ndd) < R(DBL_EPSILON)) return false;
-    const R dd = -dot(N, p1);
-    const R tt = -(dot(N, r.o) + dd) / ndd;
+__device__ __forceinline__ bool hit_tri_v(V3 p1, V3 p2, V3 p3, const Ray& r, double tmin, double tmax, double& t) {
+    const V3 N = cross(p2 - p1, p3 - p1);
+    const double ndd = dot(N, r.d);
+    if (fabs(ndd) < DBL_EPSILON) return false;
+    const double dd = -dot(N, p1);
+    const double tt = -(dot(N, r.o) + dd) / ndd;
     if (tt < tmin || tmax < tt) return false;
-    const V3<R> p = r.o + tt * r.d;
-    if (dot(N, cross(p2 - p1, p - p1)) < R(0)) return false;
-    if (dot(N, cross(p3 - p2, p - p2)) < R(0)) return false;
-    if (dot(N, cross(p1 - p3, p - p3)) < R(0)) return false;
+    const V3 p = r.o + tt * r.d;
+    if (dot(N, cross(p2 - p1, p - p1)) < 0.0) return false;
+    if (dot(N, cross(p3 - p2, p - p2)) < 0.0) return false;
+    if (dot(N, cross(p1 - p3, p - p3)) < 0.0) return false;
     t = tt;
     return true;
 }
 // hit_tri_v with the plane (N, dd) precomputed on the host by the same operations (TriRec112)
-template <class R>
-__device__ __forceinline__ bool hit_tri_pre(V3<R> p1, V3<R> p2, V3<R> p3, V3<R> N, R dd, const Ray<R>& r, R tmin, R tmax, R& t) {
-    const R ndd = dot(N, r.d);
-    if (fabs(ndd) < R(DBL_EPSILON)) return false;
-    const R tt = -(dot(N, r.o) + dd) / ndd;
+__device__ __forceinline__ bool hit_tri_pre(V3 p1, V3 p2, V3 p3, V3 N, double dd, const Ray& r, double tmin, double tmax, double& t) {
+    const double ndd = dot(N, r.d);
+    if (fabs(ndd) < DBL_EPSILON) return false;
+    const double tt = -(dot(N, r.o) + dd) / ndd;
     if (tt < tmin || tmax < tt) return false;
-    const V3<R> p = r.o + tt * r.d;
-    if (dot(N, cross(p2 - p1, p - p1)) < R(0)) return false;
-    if (dot(N, cross(p3 - p2, p - p2)) < R(0)) return false;
-    if (dot(N, cross(p1 - p3, p - p3)) < R(0)) return false;
+    const V3 p = r.o + tt * r.d;
+    if (dot(N, cross(p2 - p1, p - p1)) < 0.0) return false;
+    if (dot(N, cross(p3 - p2, p - p2)) < 0.0) return false;
+    if (dot(N, cross(p1 - p3, p - p3)) < 0.0) return false;
     t = tt;
     return true;
 }
-template <class R>
-__device__ __forceinline__ bool hit_tri(const TriRec<R>& tr, const Ray<R>& r, R tmin, R tmax, R& t) {
+__device__ __forceinline__ bool hit_tri(const TriRec& tr, const Ray& r, double tmin, double tmax, double& t) {
     return hit_tri_v(ld3(tr.p), ld3(tr.p + 3), ld3(tr.p + 6), r, tmin, tmax, t);
 }
 
-template <class R> __device__ __forceinline__ R comp(V3<R> v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }
+__device__ __forceinline__ double comp(V3 v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }
 
 // aarect.cpp:3-55.  axis 0: xy (k on z), 1: xz (k on y), 2: yz (k on x).
-template <class R>
-__device__ __forceinline__ bool hit_rect(int axis, R a0, R a1, R b0, R b1, R k, const Ray<R>& r, R tmin, R tmax, R& t) {
+__device__ __forceinline__ bool hit_rect(int axis, double a0, double a1, double b0, double b1, double k, const Ray& r, double tmin, double tmax, double& t) {
     const int ka = axis == 0 ? 2 : (axis == 1 ? 1 : 0);
     const int ia = axis == 2 ? 1 : 0;
     const int ib = axis == 0 ? 1 : 2;
-    const R tt = (k - comp(r.o, ka)) / comp(r.d, ka);
+    const double tt = (k - comp(r.o, ka)) / comp(r.d, ka);
     if (tt < tmin || tt > tmax) return false;
-    const R x = comp(r.o, ia) + tt * comp(r.d, ia);
-    const R y = comp(r.o, ib) + tt * comp(r.d, ib);
+    const double x = comp(r.o, ia) + tt * comp(r.d, ia);
+    const double y = comp(r.o, ib) + tt * comp(r.d, ib);
     if (x < a0 || x > a1 || y < b0 || y > b1) return false;
     t = tt;
     return true;
 }
 
 // box.cpp:3-19: face f of a box, in the reference's side order.
-template <class R>
-__device__ __forceinline__ void box_face(const BoxRec<R>& b, int f, int& axis, R& a0, R& a1, R& b0, R& b1, R& k) {
+__device__ __forceinline__ void box_face(const BoxRec& b, int f, int& axis, double& a0, double& a1, double& b0, double& b1, double& k) {
     const int pair = f >> 1;       // 0: xy, 1: xz, 2: yz
     const bool hi = (f & 1) == 0;  // even faces sit on p1
     axis = pair;
@@ -403,13 +367,13 @@ __device__ __forceinline__ void box_face(const BoxRec<R>& b, int f, int& axis, R
     else { a0 = b.mn[1]; a1 = b.mx[1]; b0 = b.mn[2]; b1 = b.mx[2]; k = hi ? b.mx[0] : b.mn[0]; }
 }
 // ANY (occlusion queries): true at the first side accepted in [tmin, tmax]; t and face are not set.
-template <class R, bool ANY = false>
-__device__ __forceinline__ bool hit_box(const BoxRec<R>& b, const Ray<R>& r, R tmin, R tmax, R& t, uint32_t& face) {
+template <bool ANY = false>
+__device__ __forceinline__ bool hit_box(const BoxRec& b, const Ray& r, double tmin, double tmax, double& t, uint32_t& face) {
     bool any = false;  // hittable_list semantics over the six sides: closest wins, a later equal t replaces
-    R closest = tmax;
+    double closest = tmax;
     for (int f = 0; f < 6; ++f) {
         int axis;
-        R a0, a1, b0, b1, k, tt;
+        double a0, a1, b0, b1, k, tt;
         box_face(b, f, axis, a0, a1, b0, b1, k);
         const bool h = hit_rect(axis, a0, a1, b0, b1, k, r, tmin, closest, tt);
         if constexpr (ANY) {
@@ -427,30 +391,30 @@ __device__ __forceinline__ bool hit_box(const BoxRec<R>& b, const Ray<R>& r, R t
 }
 
 // The test of a primitive given its record (a prim object's copy, DevScene::obj_prims): the same arithmetic as hit_prim.
-template <class R, uint32_t F, bool ANY = false>
-__device__ __forceinline__ bool hit_prim_rec(uint32_t type, const PrimRec80& rec, const Ray<R>& r, R tmin, R tmax, R& t, uint32_t& face) {
-    if ((F & F_SPHERE) && (fbase(F) == F_SPHERE || type == PRIM_SPHERE)) return hit_sphere(reinterpret_cast<const SphereRec<R>&>(rec), r, tmin, tmax, t);
-    if ((F & F_TRI) && (fbase(F) == F_TRI || type == PRIM_TRIANGLE)) return hit_tri(reinterpret_cast<const TriRec<R>&>(rec), r, tmin, tmax, t);
+template <uint32_t F, bool ANY = false>
+__device__ __forceinline__ bool hit_prim_rec(uint32_t type, const PrimRec80& rec, const Ray& r, double tmin, double tmax, double& t, uint32_t& face) {
+    if ((F & F_SPHERE) && (fbase(F) == F_SPHERE || type == PRIM_SPHERE)) return hit_sphere(reinterpret_cast<const SphereRec&>(rec), r, tmin, tmax, t);
+    if ((F & F_TRI) && (fbase(F) == F_TRI || type == PRIM_TRIANGLE)) return hit_tri(reinterpret_cast<const TriRec&>(rec), r, tmin, tmax, t);
     if ((F & F_RECT) && type == PRIM_RECT) {
-        const RectRec<R>& q = reinterpret_cast<const RectRec<R>&>(rec);
+        const RectRec& q = reinterpret_cast<const RectRec&>(rec);
         return hit_rect(static_cast<int>(q.axis), q.a0, q.a1, q.b0, q.b1, q.k, r, tmin, tmax, t);
     }
-    if ((F & F_BOX) && type == PRIM_BOX) return hit_box<R, ANY>(reinterpret_cast<const BoxRec<R>&>(rec), r, tmin, tmax, t, face);
+    if ((F & F_BOX) && type == PRIM_BOX) return hit_box<ANY>(reinterpret_cast<const BoxRec&>(rec), r, tmin, tmax, t, face);
     return false;
 }
 // F (layout.h Feature bits) prunes the primitive kinds a scene cannot contain, so a kernel instantiated for a
 // spheres-only scene carries no triangle/box/transform/medium code and needs far fewer registers.
-template <class R, uint32_t F, bool ANY = false>
-__device__ __forceinline__ bool hit_prim(const DevScene<R>& S, uint32_t ref, const Ray<R>& r, R tmin, R tmax, R& t, uint32_t& face) {
+template <uint32_t F, bool ANY = false>
+__device__ __forceinline__ bool hit_prim(const DevScene& S, uint32_t ref, const Ray& r, double tmin, double tmax, double& t, uint32_t& face) {
     const uint32_t idx = primref_index(ref);
     const uint32_t type = primref_type(ref);
     if ((F & F_SPHERE) && (fbase(F) == F_SPHERE || type == PRIM_SPHERE)) return hit_sphere(S.spheres[idx], r, tmin, tmax, t);
     if ((F & F_TRI) && (fbase(F) == F_TRI || type == PRIM_TRIANGLE)) return hit_tri(S.tris[idx], r, tmin, tmax, t);
     if ((F & F_RECT) && type == PRIM_RECT) {
-        const RectRec<R>& q = S.rects[idx];
+        const RectRec& q = S.rects[idx];
         return hit_rect(static_cast<int>(q.axis), q.a0, q.a1, q.b0, q.b1, q.k, r, tmin, tmax, t);
     }
-    if ((F & F_BOX) && type == PRIM_BOX) return hit_box<R, ANY>(S.boxes[idx], r, tmin, tmax, t, face);
+    if ((F & F_BOX) && type == PRIM_BOX) return hit_box<ANY>(S.boxes[idx], r, tmin, tmax, t, face);
     return false;
 }
 
@@ -459,14 +423,12 @@ __device__ __forceinline__ bool hit_prim(const DevScene<R>& S, uint32_t ref, con
 // lane; the stack is a dynamic LDS array of the scene's worst-case depth + 2 rows: stk[-B] is a kNodeEmpty sentinel and
 // the last row takes the discarded write of a branchless push).  Each node visit tests its four child
 // boxes at once, goes to the nearest hit child and pushes the other hit children far-to-near.  Box tests are f32 and
-// conservative (boxes padded at build time, interval widened here); leaves run the exact R tests and shrink tmax, so
+// conservative (boxes padded at build time, interval widened here); leaves run the exact f64 tests and shrink tmax, so
 // the closest hit equals the reference's bvh_node::hit (bvh.cpp:44-52) up to exact-t ties.
 constexpr int kBlock = 256;
 
 __device__ __forceinline__ float f_lo(double t) { return t == -__builtin_inf() ? -__builtin_inff() : static_cast<float>(t) * (1.0f - 2e-6f) - 1e-30f; }
-__device__ __forceinline__ float f_lo(float t) { return t * (1.0f - 2e-6f) - 1e-30f; }
 __device__ __forceinline__ float f_hi(double t) { return t == __builtin_inf() ? __builtin_inff() : static_cast<float>(t) * (1.0f + 2e-6f) + 1e-30f; }
-__device__ __forceinline__ float f_hi(float t) { return t * (1.0f + 2e-6f) + 1e-30f; }
 
 // Slab entry distances of the four child boxes of a node, +inf when a box is missed (or the slot is empty).  The plane
 // distances are single-rounding FMAs fma(plane, 1/d, -o/d), two children per v_pk_fma_f32; one rounding is no worse
@@ -584,7 +546,7 @@ __device__ __forceinline__ double2 lds_d2(uint32_t addr) {
 }
 __device__ __forceinline__ double lds_d1(uint32_t addr) { return *(__attribute__((address_space(3))) const double*)(size_t)addr; }
 __device__ __forceinline__ uint32_t lds_u1(uint32_t addr) { return *(__attribute__((address_space(3))) const uint32_t*)(size_t)addr; }
-__device__ __forceinline__ bool hit_lds_slot(const uint8_t* lds, uint32_t slot, const Ray<double>& r, double d_a, double d_inv_a,
+__device__ __forceinline__ bool hit_lds_slot(const uint8_t* lds, uint32_t slot, const Ray& r, double d_a, double d_inv_a,
                                              double tmin, double tmax, double& t, uint32_t& prim, uint32_t& mt) {
     const double2 a = lds_d2(kLdsOffSph + slot * 16u), b = lds_d2(kLdsOffSph + (kLdsSlotCap + slot) * 16u);
 #if ART_LDS_LEAF_NOREF
@@ -595,14 +557,14 @@ __device__ __forceinline__ bool hit_lds_slot(const uint8_t* lds, uint32_t slot, 
 #else
     const uint32_t code = lds_u1(kLdsOffRef + slot * 4u);
 #endif
-    V3<double> center{a.x, a.y, b.x};
+    V3 center{a.x, a.y, b.x};
     // y motion only (lds_scene_image): c + tm * (+-0, dy, +-0) leaves x and z as they are; static slots hold dy = -0
     center.y = center.y + r.tm * lds_d1(kLdsOffMov + slot * 8u);
 #if !ART_LDS_LEAF_NOREF
     prim = make_primref(PRIM_SPHERE, code & kLdsRefIndexMask);
     mt = code >> kLdsRefMatShift;
 #endif
-    return sphere_root<double, true>(center, b.y, r, d_a, d_inv_a, tmin, tmax, t);
+    return sphere_root<true>(center, b.y, r, d_a, d_inv_a, tmin, tmax, t);
 }
 
 #ifdef ART_STATS
@@ -727,9 +689,9 @@ struct TravResume {
 // test accepted in [tmin, tmax] and sets none of t, prim, face, mt.  tmax -- and so the f32 interval of the box tests --
 // is then constant over the walk, so no visit is stale and the child order only decides how soon an occluder is met:
 // 1 keeps the nearest-first sorting network, 2 pushes the entered children in node order without it.
-template <class R, uint32_t F, int B, bool L, int PL = 0, bool RES = false, int ANY = 0>
-__device__ __forceinline__ bool traverse(const DevScene<R>& S, const uint8_t* lds, int32_t root, const Ray<R>& r, R tmin, R tmax,
-                                         StackF<L, F>* stk, R& t, uint32_t& prim, uint32_t& face, uint32_t& mt, TravResume* rs = nullptr,
+template <uint32_t F, int B, bool L, int PL = 0, bool RES = false, int ANY = 0>
+__device__ __forceinline__ bool traverse(const DevScene& S, const uint8_t* lds, int32_t root, const Ray& r, double tmin, double tmax,
+                                         StackF<L, F>* stk, double& t, uint32_t& prim, uint32_t& face, uint32_t& mt, TravResume* rs = nullptr,
                                          int32_t hoisted = kNodeEmpty) {
     static_assert(!(L && (F & F_MEDIA)), "packed LDS keys need tmin > 0: no medium boundary tests in the LDS variant");
     static_assert(!RES || !L, "resumable traversal: HBM-scene variant only");
@@ -764,8 +726,8 @@ __device__ __forceinline__ bool traverse(const DevScene<R>& S, const uint8_t* ld
     // two perlin spheres +3.5 %, earth +0.6 %; the Next-Week final's kernel, 1000 leaf spheres, keeps the eager one:
     // lazy -0.4 %)
     constexpr bool kSphLazy = kSphPre && (F & (F_BOX | F_RECT | F_XFORM | F_MEDIA)) == 0;
-    const R d_a = (L || kSphPre) ? len2(r.d) : R(0);
-    R d_inv_a = (L || (kSphPre && !kSphLazy)) ? R(1) / d_a : R(0);
+    const double d_a = (L || kSphPre) ? len2(r.d) : 0.0;
+    double d_inv_a = (L || (kSphPre && !kSphLazy)) ? 1.0 / d_a : 0.0;
     bool hit = false;
     // PK (k_paths_g instantiations with F_CODE16): the HBM-scene traversal sorts packed keys as the LDS variant does,
     // with the node's 16-bit child codes (BvhNode::pad, layout.h make_leaf16) in the low half of each key; codes,
@@ -1054,7 +1016,7 @@ __device__ __forceinline__ bool traverse(const DevScene<R>& S, const uint8_t* ld
         for (uint32_t k = 0; k < cnt12; ++k) {
             ART_STAT_WAVE(2);
             ART_STAT_LANE(3);
-            R tt;
+            double tt;
             uint32_t fc = 0, ref, m = kMatUnknown;
             bool h;
             if constexpr (L) {
@@ -1066,24 +1028,24 @@ __device__ __forceinline__ bool traverse(const DevScene<R>& S, const uint8_t* ld
                 if constexpr ((F & F_TRI) != 0 && PL == 2) {
                     // the LM 1 kernels' leaf triangles with their planes (TriRec112, in LDS): no cross product or
                     // plane offset per test
-                    const TriRec112<R>& lt = S.leaf_tris112[slot];
-                    V3<R> p1 = ld3(lt.p), p2 = ld3(lt.p + 3), p3 = ld3(lt.p + 6), nn = ld3(lt.n);
-                    R pdd = lt.dd;
+                    const TriRec112& lt = S.leaf_tris112[slot];
+                    V3 p1 = ld3(lt.p), p2 = ld3(lt.p + 3), p3 = ld3(lt.p + 6), nn = ld3(lt.n);
+                    double pdd = lt.dd;
                     ref = S.primrefs[slot];
                     __asm__ volatile("" : "+v"(p1.x), "+v"(p1.y), "+v"(p1.z), "+v"(p2.x), "+v"(p2.y), "+v"(p2.z), "+v"(p3.x), "+v"(p3.y), "+v"(p3.z));
                     __asm__ volatile("" : "+v"(nn.x), "+v"(nn.y), "+v"(nn.z), "+v"(pdd));
                     if (fbase(F) == F_TRI || primref_type(ref) == PRIM_TRIANGLE) h = hit_tri_pre(p1, p2, p3, nn, pdd, r, tmin, tmax, tt);
-                    else h = hit_prim<R, F & ~F_TRI, ANY != 0>(S, ref, r, tmin, tmax, tt, fc);
+                    else h = hit_prim<F & ~F_TRI, ANY != 0>(S, ref, r, tmin, tmax, tt, fc);
                 } else if constexpr ((F & F_TRI) != 0) {
                     // the leaf-ordered triangle copy: its address depends on the slot alone, so its loads go out
                     // beside the primref's instead of behind it (one L2 round trip per test instead of two); the
                     // empty asm keeps the compiler from sinking them under the type test
-                    const TriRec<R>& lt = S.leaf_tris[slot];
-                    V3<R> p1 = ld3(lt.p), p2 = ld3(lt.p + 3), p3 = ld3(lt.p + 6);
+                    const TriRec& lt = S.leaf_tris[slot];
+                    V3 p1 = ld3(lt.p), p2 = ld3(lt.p + 3), p3 = ld3(lt.p + 6);
                     ref = S.primrefs[slot];
                     __asm__ volatile("" : "+v"(p1.x), "+v"(p1.y), "+v"(p1.z), "+v"(p2.x), "+v"(p2.y), "+v"(p2.z), "+v"(p3.x), "+v"(p3.y), "+v"(p3.z));
                     if (fbase(F) == F_TRI || primref_type(ref) == PRIM_TRIANGLE) h = hit_tri_v(p1, p2, p3, r, tmin, tmax, tt);
-                    else h = hit_prim<R, F & ~F_TRI, ANY != 0>(S, ref, r, tmin, tmax, tt, fc);
+                    else h = hit_prim<F & ~F_TRI, ANY != 0>(S, ref, r, tmin, tmax, tt, fc);
                 } else {
                     // the leaf-ordered record copy: its loads go out beside the primref's instead of behind it
                     const uint4* lp = reinterpret_cast<const uint4*>(S.leaf_prims + slot);
@@ -1098,16 +1060,16 @@ __device__ __forceinline__ bool traverse(const DevScene<R>& S, const uint8_t* ld
                     if constexpr (kSphPre) {
                         // spheres with the ray's |d|^2 and its reciprocal (div_rcp roots), as the LDS variant
                         if (primref_type(ref) == PRIM_SPHERE) {
-                            const SphereRec<R>& sr = reinterpret_cast<const SphereRec<R>&>(rec);
-                            V3<R> center = ld3(sr.c);
+                            const SphereRec& sr = reinterpret_cast<const SphereRec&>(rec);
+                            V3 center = ld3(sr.c);
                             if (sr.flags & SPH_MOVING) center = moving_center(center, ld3(sr.d), sr.t0, sr.dt, r.tm);
-                            if constexpr (kSphLazy) h = sphere_root_lazy<R>(center, sr.r * sr.r, r, d_a, d_inv_a, tmin, tmax, tt);
-                            else h = sphere_root<R, true>(center, sr.r * sr.r, r, d_a, d_inv_a, tmin, tmax, tt);
+                            if constexpr (kSphLazy) h = sphere_root_lazy(center, sr.r * sr.r, r, d_a, d_inv_a, tmin, tmax, tt);
+                            else h = sphere_root<true>(center, sr.r * sr.r, r, d_a, d_inv_a, tmin, tmax, tt);
                         } else {
-                            h = hit_prim_rec<R, F & ~F_SPHERE, ANY != 0>(primref_type(ref), rec, r, tmin, tmax, tt, fc);
+                            h = hit_prim_rec<F & ~F_SPHERE, ANY != 0>(primref_type(ref), rec, r, tmin, tmax, tt, fc);
                         }
                     } else {
-                        h = hit_prim_rec<R, F, ANY != 0>(primref_type(ref), rec, r, tmin, tmax, tt, fc);
+                        h = hit_prim_rec<F, ANY != 0>(primref_type(ref), rec, r, tmin, tmax, tt, fc);
                     }
                     // the record's material index (sphere / box / rect: dword 18 / 12 / 11) and a rect's axis (dword 10,
                     // in the face field): the hit's surface then needs no reload of a box or rect record (prim_surface)
@@ -1145,13 +1107,12 @@ __device__ __forceinline__ bool traverse(const DevScene<R>& S, const uint8_t* ld
 }
 
 // ------------------------------------------------------------------------------------------------ objects
-template <class R>
-__device__ __forceinline__ Ray<R> xform_in(const ObjRec<R>& o, const Ray<R>& r) {
-    Ray<R> out = r;
+__device__ __forceinline__ Ray xform_in(const ObjRec& o, const Ray& r) {
+    Ray out = r;
     if (o.kind == OBJ_TRANSLATE) {  // hittable.cpp:4: moved_r(origin - offset, direction, time)
         out.o = r.o - mk(o.p[0], o.p[1], o.p[2]);
     } else {  // hittable.cpp:58-67
-        const R s = o.p[0], c = o.p[1];
+        const double s = o.p[0], c = o.p[1];
         out.o.x = c * r.o.x - s * r.o.z;
         out.o.z = s * r.o.x + c * r.o.z;
         out.d.x = c * r.d.x - s * r.d.z;
@@ -1161,19 +1122,19 @@ __device__ __forceinline__ Ray<R> xform_in(const ObjRec<R>& o, const Ray<R>& r) 
 }
 
 // Any non-medium object: prim, BVH, or a translate/rotate_y chain (<= kMaxXformChain) over one of them.
-template <class R, uint32_t F, int B, bool L, int PL = 0, bool RES = false, int ANY = 0>
-__device__ __forceinline__ bool hit_object(const DevScene<R>& S, const uint8_t* lds, int32_t oi, Ray<R> r, R tmin, R tmax, StackF<L, F>* stk,
-                                           R& t, uint32_t& prim, uint32_t& face, uint32_t& mt, TravResume* rs = nullptr) {
+template <uint32_t F, int B, bool L, int PL = 0, bool RES = false, int ANY = 0>
+__device__ __forceinline__ bool hit_object(const DevScene& S, const uint8_t* lds, int32_t oi, Ray r, double tmin, double tmax, StackF<L, F>* stk,
+                                           double& t, uint32_t& prim, uint32_t& face, uint32_t& mt, TravResume* rs = nullptr) {
     if (F & F_XFORM) {
 #pragma unroll
         for (int c = 0; c < kMaxXformChain; ++c) {
-            const ObjRec<R>& o = S.objs[oi];
+            const ObjRec& o = S.objs[oi];
             if (o.kind != OBJ_TRANSLATE && o.kind != OBJ_ROTATE_Y) break;
             r = xform_in(o, r);
             oi = o.a;
         }
     }
-    const ObjRec<R>& o = S.objs[oi];
+    const ObjRec& o = S.objs[oi];
     if (o.kind == OBJ_PRIM) {
         prim = static_cast<uint32_t>(o.a);
         mt = kMatUnknown;
@@ -1181,7 +1142,7 @@ __device__ __forceinline__ bool hit_object(const DevScene<R>& S, const uint8_t* 
         if constexpr (!L) {
             const PrimRec80& rec = S.obj_prims[oi];
             const uint32_t ty = primref_type(prim);
-            const bool h = hit_prim_rec<R, F, ANY != 0>(ty, rec, r, tmin, tmax, t, face);
+            const bool h = hit_prim_rec<F, ANY != 0>(ty, rec, r, tmin, tmax, t, face);
             if constexpr ((F & F_TRI) == 0) {  // as the leaf records: the material index, a rect's axis in `face`
                 const uint32_t* wd = reinterpret_cast<const uint32_t*>(rec.b);
                 mt = ty == PRIM_SPHERE ? wd[18] : ty == PRIM_BOX ? wd[12] : wd[11];
@@ -1189,10 +1150,10 @@ __device__ __forceinline__ bool hit_object(const DevScene<R>& S, const uint8_t* 
             }
             return h;
         } else {
-            return hit_prim<R, F, ANY != 0>(S, prim, r, tmin, tmax, t, face);
+            return hit_prim<F, ANY != 0>(S, prim, r, tmin, tmax, t, face);
         }
     }
-    return traverse<R, F, B, L, PL, RES, ANY>(S, lds, o.a, r, tmin, tmax, stk, t, prim, face, mt, rs, o.b);
+    return traverse<F, B, L, PL, RES, ANY>(S, lds, o.a, r, tmin, tmax, stk, t, prim, face, mt, rs, o.b);
 }
 
 // Out of line: measured +0.2 % (cow) to +1.8 % (Next-Week final) over the inlined body, which raised the register
@@ -1204,37 +1165,37 @@ __device__ __forceinline__ bool hit_object(const DevScene<R>& S, const uint8_t* 
     return sphere_uv(x, y, z, TrigTab(c, t));
 }
 // constant_medium.h:37-82.  Consumes one uniform when the clamped interval is non-empty.
-template <class R, uint32_t F, int B, bool L, int PL = 0>
-__device__ __forceinline__ bool hit_medium(const DevScene<R>& S, const uint8_t* lds, const ObjRec<R>& m, const Ray<R>& r, R tmin, R tmax,
-                                           StackF<L, F>* stk, uint64_t& rng, R& t) {
-    const R inf = R(__builtin_inf());
-    R t1, t2;
-    const ObjRec<R>& bo = S.objs[m.a];
+template <uint32_t F, int B, bool L, int PL = 0>
+__device__ __forceinline__ bool hit_medium(const DevScene& S, const uint8_t* lds, const ObjRec& m, const Ray& r, double tmin, double tmax,
+                                           StackF<L, F>* stk, uint64_t& rng, double& t) {
+    const double inf = __builtin_inf();
+    double t1, t2;
+    const ObjRec& bo = S.objs[m.a];
     if ((F & F_SPHERE) && bo.kind == OBJ_PRIM && primref_type(static_cast<uint32_t>(bo.a)) == PRIM_SPHERE) {
         // A sphere boundary (every medium of the reference scenes but the Cornell smoke boxes): the two boundary->hit
         // calls (constant_medium.h:43, :46) compute the same oc, half_b, c, discriminant and sqrt (sphere.h:39-47)
         // from the same ray and sphere, so both root selections (sphere.h:49-55) run on one quadratic: the same
         // values, half the arithmetic.
-        const SphereRec<R>& sp = [&]() -> const SphereRec<R>& {
-            if constexpr (!L) return reinterpret_cast<const SphereRec<R>&>(S.obj_prims[m.a]);
+        const SphereRec& sp = [&]() -> const SphereRec& {
+            if constexpr (!L) return reinterpret_cast<const SphereRec&>(S.obj_prims[m.a]);
             else return S.spheres[primref_index(static_cast<uint32_t>(bo.a))];
         }();
-        V3<R> center = ld3(sp.c);
+        V3 center = ld3(sp.c);
         if (sp.flags & SPH_MOVING) center = moving_center(center, ld3(sp.d), sp.t0, sp.dt, r.tm);
-        const V3<R> oc = r.o - center;
-        const R a = len2(r.d);
-        const R half_b = dot(oc, r.d);
-        const R c = len2(oc) - sp.r * sp.r;
-        const R disc = half_b * half_b - a * c;
-        if (disc < R(0)) return false;
-        const R sqrtd = sqrt_rn(disc);
-        const R r_near = (-half_b - sqrtd) / a, r_far = (-half_b + sqrtd) / a;
+        const V3 oc = r.o - center;
+        const double a = len2(r.d);
+        const double half_b = dot(oc, r.d);
+        const double c = len2(oc) - sp.r * sp.r;
+        const double disc = half_b * half_b - a * c;
+        if (disc < 0.0) return false;
+        const double sqrtd = sqrt_rn(disc);
+        const double r_near = (-half_b - sqrtd) / a, r_far = (-half_b + sqrtd) / a;
         t1 = r_near;  // first call, t in [-inf, inf]
         if (t1 < -inf || inf < t1) {
             t1 = r_far;
             if (t1 < -inf || inf < t1) return false;
         }
-        const R tmin2 = t1 + R(0.0001);  // second call, t in [t1 + 0.0001, inf]
+        const double tmin2 = t1 + 0.0001;  // second call, t in [t1 + 0.0001, inf]
         t2 = r_near;
         if (t2 < tmin2 || inf < t2) {
             t2 = r_far;
@@ -1242,23 +1203,23 @@ __device__ __forceinline__ bool hit_medium(const DevScene<R>& S, const uint8_t* 
         }
     } else if constexpr ((F & F_MEDIA_G) != 0) {
         uint32_t p, f, mt;
-        if (!hit_object<R, F, B, L, PL>(S, lds, m.a, r, -inf, inf, stk, t1, p, f, mt)) return false;
-        if (!hit_object<R, F, B, L, PL>(S, lds, m.a, r, t1 + R(0.0001), inf, stk, t2, p, f, mt)) return false;
+        if (!hit_object<F, B, L, PL>(S, lds, m.a, r, -inf, inf, stk, t1, p, f, mt)) return false;
+        if (!hit_object<F, B, L, PL>(S, lds, m.a, r, t1 + 0.0001, inf, stk, t2, p, f, mt)) return false;
     } else {
         return false;  // unreachable: a scene with a non-sphere medium boundary has F_MEDIA_G
     }
     if (t1 < tmin) t1 = tmin;
     if (t2 > tmax) t2 = tmax;
     if (t1 >= t2) return false;
-    if (t1 < R(0)) t1 = R(0);
-    const R ray_length = sqrt_rn(len2(r.d));
-    const R inside = (t2 - t1) * ray_length;
+    if (t1 < 0.0) t1 = 0.0;
+    const double ray_length = sqrt_rn(len2(r.d));
+    const double inside = (t2 - t1) * ray_length;
     // log(random_double()) of constant_medium.h:61 is the C library's log (glibc) in the reference; the device's own
     // f64 log differs from it in the last bit for 445 762 of the 2^24 arguments a uniform can take, which moves a
     // scattering path's t and every sum after it.  glibc_log.h restates glibc's log operation by operation (equal for
     // every k * 2^-24); it replaced a 128 MiB table of glibc's values, whose random reads (an L2 miss per draw) cost 5-10 % on the medium scenes.
     const uint32_t k = uniform_k(rng);
-    const R hit_distance = m.p[0] * glibc_log_call(static_cast<double>(k) * 0x1p-24);
+    const double hit_distance = m.p[0] * glibc_log_call(static_cast<double>(k) * 0x1p-24);
     if (hit_distance > inside) return false;
     t = t1 + hit_distance / ray_length;
     return true;
@@ -1272,18 +1233,18 @@ struct HitOut {
 };
 // t_max: the search interval is [0.001, t_max] (rt_query_rays; every renderer call site searches to +inf).
 // no_media (RT_Q_NO_MEDIA): constant_medium objects are skipped and draw nothing from rng.
-template <class R, uint32_t F, int B, bool L, int PL = 0>
-__device__ __forceinline__ bool trace_world(const DevScene<R>& S, const uint8_t* lds, const Ray<R>& r, StackF<L, F>* stk, uint64_t& rng, R& t,
-                                            HitOut& h, R t_max = R(__builtin_inf()), bool no_media = false) {
-    R closest = t_max;
+template <uint32_t F, int B, bool L, int PL = 0>
+__device__ __forceinline__ bool trace_world(const DevScene& S, const uint8_t* lds, const Ray& r, StackF<L, F>* stk, uint64_t& rng, double& t,
+                                            HitOut& h, double t_max = __builtin_inf(), bool no_media = false) {
+    double closest = t_max;
     bool any = false;
     for (int w = 0; w < S.nworld; ++w) {
         const int32_t oi = S.world[w];
-        const ObjRec<R>& o = S.objs[oi];
-        R tt;
+        const ObjRec& o = S.objs[oi];
+        double tt;
         if ((F & F_MEDIA) && o.kind == OBJ_MEDIUM) {
             if (no_media) continue;
-            if (hit_medium<R, F, B, L, PL>(S, lds, o, r, R(0.001), closest, stk, rng, tt)) {
+            if (hit_medium<F, B, L, PL>(S, lds, o, r, 0.001, closest, stk, rng, tt)) {
                 closest = tt;
                 any = true;
                 h.prim = kMediumHit;
@@ -1292,7 +1253,7 @@ __device__ __forceinline__ bool trace_world(const DevScene<R>& S, const uint8_t*
             }
         } else {
             uint32_t prim = 0, face = 0, mt = kMatUnknown;
-            if (hit_object<R, F, B, L, PL>(S, lds, oi, r, R(0.001), closest, stk, tt, prim, face, mt)) {
+            if (hit_object<F, B, L, PL>(S, lds, oi, r, 0.001, closest, stk, tt, prim, face, mt)) {
                 closest = tt;
                 any = true;
                 h.prim = prim;
@@ -1309,15 +1270,15 @@ __device__ __forceinline__ bool trace_world(const DevScene<R>& S, const uint8_t*
 // own hit test in [0.001, t_max].  The list walk stops at the first occluder; constant_medium objects never occlude.
 // Every primitive whose test accepts is inside a leaf whose padded f32 box the constant interval enters, so the answer
 // depends on neither the tree nor the order of the walk.  F carries no media bits.  ANY: traverse's 1 or 2.
-template <class R, uint32_t F, int B, bool L, int ANY>
-__device__ __forceinline__ bool occlude_world(const DevScene<R>& S, const uint8_t* lds, const Ray<R>& r, StackF<L, F>* stk, R t_max) {
+template <uint32_t F, int B, bool L, int ANY>
+__device__ __forceinline__ bool occlude_world(const DevScene& S, const uint8_t* lds, const Ray& r, StackF<L, F>* stk, double t_max) {
     static_assert((F & (F_MEDIA | F_MEDIA_G)) == 0 && ANY != 0, "any-hit walks test no medium");
     for (int w = 0; w < S.nworld; ++w) {
         const int32_t oi = S.world[w];
         if (S.objs[oi].kind == OBJ_MEDIUM) continue;
-        R tt;
+        double tt;
         uint32_t prim = 0, face = 0, mt = kMatUnknown;
-        if (hit_object<R, F, B, L, 0, false, ANY>(S, lds, oi, r, R(0.001), t_max, stk, tt, prim, face, mt)) return true;
+        if (hit_object<F, B, L, 0, false, ANY>(S, lds, oi, r, 0.001, t_max, stk, tt, prim, face, mt)) return true;
     }
     return false;
 }
@@ -1325,29 +1286,28 @@ __device__ __forceinline__ bool occlude_world(const DevScene<R>& S, const uint8_
 // trace_world with suspendable BVH traversals (ART_SUSPEND_LANES): the world list walk of one segment, resumed at
 // world slot w with the closest hit so far.  Returns true when the segment's trace is complete.  Medium boundaries
 // and prim objects never suspend.
-template <class R>
 struct TraceState {
-    R closest;
+    double closest;
     HitOut h;
     int32_t w;
     bool any;
     TravResume tr;
     __device__ __forceinline__ void start() {
-        closest = R(__builtin_inf());
+        closest = __builtin_inf();
         any = false;
         w = 0;
         tr.fresh = true;
     }
 };
-template <class R, uint32_t F, int B, int PL>
-__device__ __forceinline__ bool trace_world_res(const DevScene<R>& S, const Ray<R>& r, StackF<false, F>* stk, uint64_t& rng, TraceState<R>& ts) {
+template <uint32_t F, int B, int PL>
+__device__ __forceinline__ bool trace_world_res(const DevScene& S, const Ray& r, StackF<false, F>* stk, uint64_t& rng, TraceState& ts) {
     ts.tr.suspended = false;
     for (int32_t w = ts.w; w < S.nworld; ++w) {
         const int32_t oi = S.world[w];
-        const ObjRec<R>& o = S.objs[oi];
-        R tt;
+        const ObjRec& o = S.objs[oi];
+        double tt;
         if ((F & F_MEDIA) && o.kind == OBJ_MEDIUM) {
-            if (hit_medium<R, F, B, false, PL>(S, nullptr, o, r, R(0.001), ts.closest, stk, rng, tt)) {
+            if (hit_medium<F, B, false, PL>(S, nullptr, o, r, 0.001, ts.closest, stk, rng, tt)) {
                 ts.closest = tt;
                 ts.any = true;
                 ts.h.prim = kMediumHit;
@@ -1356,7 +1316,7 @@ __device__ __forceinline__ bool trace_world_res(const DevScene<R>& S, const Ray<
             }
         } else {
             uint32_t prim = 0, face = 0, mt = kMatUnknown;
-            if (hit_object<R, F, B, false, PL, true>(S, nullptr, oi, r, R(0.001), ts.closest, stk, tt, prim, face, mt, &ts.tr)) {
+            if (hit_object<F, B, false, PL, true>(S, nullptr, oi, r, 0.001, ts.closest, stk, tt, prim, face, mt, &ts.tr)) {
                 ts.closest = tt;
                 ts.any = true;
                 ts.h.prim = prim;
@@ -1374,39 +1334,36 @@ __device__ __forceinline__ bool trace_world_res(const DevScene<R>& S, const Ray<
 }
 
 // ------------------------------------------------------------------------------------------------ surfaces
-template <class R>
 struct Surf {
-    V3<R> p, n;
-    R u, v;
+    V3 p, n;
+    double u, v;
     bool ff;
     uint32_t mat;
 };
-template <class R>
-__device__ __forceinline__ void set_face_normal(Surf<R>& s, const Ray<R>& r, V3<R> outward) {  // hittable.h:18-22
-    s.ff = dot(r.d, outward) < R(0);
+__device__ __forceinline__ void set_face_normal(Surf& s, const Ray& r, V3 outward) {  // hittable.h:18-22
+    s.ff = dot(r.d, outward) < 0.0;
     s.n = s.ff ? outward : -outward;
 }
 // hittable.h:18-22 into locals (prim_surface)
-template <class R>
-__device__ __forceinline__ void face_normal(const Ray<R>& r, V3<R> outward, bool& ff, V3<R>& n) {
-    ff = dot(r.d, outward) < R(0);
+__device__ __forceinline__ void face_normal(const Ray& r, V3 outward, bool& ff, V3& n) {
+    ff = dot(r.d, outward) < 0.0;
     n = ff ? outward : -outward;
 }
 // An axis-aligned rect's surface into prim_surface's locals.  prim_surface builds every field in locals and stores s
 // once: stores into s in several branches were merged by the compiler into one store through a phi of addresses
 // (different fields), which kept parts of Surf in scratch memory.
-template <class R, bool UV = true>
-__device__ __forceinline__ void rect_surface(V3<R>& p, V3<R>& n, bool& ff, R& su, R& sv, int axis, R a0, R a1, R b0, R b1, const Ray<R>& r,
-                                             R t, bool need_uv = true) {
+template <bool UV = true>
+__device__ __forceinline__ void rect_surface(V3& p, V3& n, bool& ff, double& su, double& sv, int axis, double a0, double a1, double b0, double b1, const Ray& r,
+                                             double t, bool need_uv = true) {
     if (UV && need_uv) {  // u, v feed image textures only (materials without MATF_NEEDS_UV skip the two divisions)
         const int ia = axis == 2 ? 1 : 0;
         const int ib = axis == 0 ? 1 : 2;
-        const R x = comp(r.o, ia) + t * comp(r.d, ia);
-        const R y = comp(r.o, ib) + t * comp(r.d, ib);
+        const double x = comp(r.o, ia) + t * comp(r.d, ia);
+        const double y = comp(r.o, ib) + t * comp(r.d, ib);
         su = (x - a0) / (a1 - a0);
         sv = (y - b0) / (b1 - b0);
     }
-    const V3<R> on = axis == 0 ? mk(R(0), R(0), R(1)) : (axis == 1 ? mk(R(0), R(1), R(0)) : mk(R(1), R(0), R(0)));
+    const V3 on = axis == 0 ? mk(0.0, 0.0, 1.0) : (axis == 1 ? mk(0.0, 1.0, 0.0) : mk(1.0, 0.0, 0.0));
     face_normal(r, on, ff, n);
     p = r.at(t);
 }
@@ -1418,25 +1375,25 @@ __device__ __forceinline__ void rect_surface(V3<R>& p, V3<R>& n, bool& ff, R& su
 // TUV: triangle u, v (barycentric image textures); UV: u, v of every primitive (TF_IMAGE kernels)
 // ALLUV (k_query_rays' hit record): u, v whatever the material samples -- of static spheres, triangles, rects and box
 // sides, the primitives whose hit() sets them in the reference; a moving sphere's stay 0 (moving_sphere.h sets none)
-template <class R, uint32_t F, bool UV = true, bool TUV = UV, bool ALLUV = false>
-__device__ __forceinline__ void prim_surface(const DevScene<R>& S, uint32_t ref, uint32_t face, const Ray<R>& r, R t, Surf<R>& s,
+template <uint32_t F, bool UV = true, bool TUV = UV, bool ALLUV = false>
+__device__ __forceinline__ void prim_surface(const DevScene& S, uint32_t ref, uint32_t face, const Ray& r, double t, Surf& s,
                                              uint32_t mat_hint, const double* uvc) {
     const uint32_t idx = primref_index(ref);
     const uint32_t type = (fbase(F) == F_SPHERE) ? PRIM_SPHERE : primref_type(ref);
-    V3<R> sp_p = mk(R(0), R(0), R(0)), sp_n = mk(R(0), R(0), R(0));
+    V3 sp_p = mk(0.0, 0.0, 0.0), sp_n = mk(0.0, 0.0, 0.0);
     bool ff = false;
-    R su = R(0), sv = R(0);
+    double su = 0.0, sv = 0.0;
     uint32_t mat = 0;
     switch (type) {
         case PRIM_SPHERE: {  // sphere.h:57-63, :24-37
             ART_STAT_WAVE(40);
             ART_STAT_LANE(41);
-            const SphereRec<R>& sp = S.spheres[idx];
-            V3<R> center = ld3(sp.c);
+            const SphereRec& sp = S.spheres[idx];
+            V3 center = ld3(sp.c);
             const bool moving = (sp.flags & SPH_MOVING) != 0;
             if (moving) center = center + motion_fraction(r.tm, sp.t0, sp.dt) * ld3(sp.d);
             sp_p = r.at(t);
-            const V3<R> outward = divs(sp_p - center, sp.r);
+            const V3 outward = divs(sp_p - center, sp.r);
             face_normal(r, outward, ff, sp_n);
             // u,v only feed image textures: acos/atan2 are skipped for materials that never sample them
             if (UV && !moving && (ALLUV || (S.mats[sp.mat].flags & MATF_NEEDS_UV))) {
@@ -1444,25 +1401,24 @@ __device__ __forceinline__ void prim_surface(const DevScene<R>& S, uint32_t ref,
                 ART_STAT_LANE(33);
                 // get_sphere_uv (sphere.h:24-37) with glibc's acos / atan2 restated (sphere_uv.h; their constants are
                 // loaded where used, not hoisted into the path loop's registers)
-                const UvPair uv = sphere_uv_call(static_cast<double>(outward.x), static_cast<double>(outward.y), static_cast<double>(outward.z),
-                                                 uvc, uv_table(S));
-                su = R(uv.u);
-                sv = R(uv.v);
+                const UvPair uv = sphere_uv_call(outward.x, outward.y, outward.z, uvc, uv_table(S));
+                su = uv.u;
+                sv = uv.v;
             }
             mat = sp.mat;
             break;
         }
         case PRIM_TRIANGLE: {  // triangle.h:57-85
             if (!(F & F_TRI)) break;
-            const TriRec<R>& tr = S.tris[idx];
-            const V3<R> p1 = ld3(tr.p), p2 = ld3(tr.p + 3), p3 = ld3(tr.p + 6);
-            const V3<R> N = cross(p2 - p1, p3 - p1);
-            const V3<R> p = r.o + t * r.d;
+            const TriRec& tr = S.tris[idx];
+            const V3 p1 = ld3(tr.p), p2 = ld3(tr.p + 3), p3 = ld3(tr.p + 6);
+            const V3 N = cross(p2 - p1, p3 - p1);
+            const V3 p = r.o + t * r.d;
             sp_p = p;
             face_normal(r, N, ff, sp_n);
             if (TUV && (ALLUV || (S.mats[tr.mat].flags & MATF_NEEDS_UV))) {  // barycentric u, v feed image textures only (texture.h:135-154)
-                const R u = dot(N, cross(p3 - p2, p - p2));
-                const R v = dot(N, cross(p1 - p3, p - p3));
+                const double u = dot(N, cross(p3 - p2, p - p2));
+                const double v = dot(N, cross(p1 - p3, p - p3));
                 su = u / len2(N);
                 sv = v / len2(N);
             }
@@ -1474,14 +1430,14 @@ __device__ __forceinline__ void prim_surface(const DevScene<R>& S, uint32_t ref,
             if (mat_hint != kMatUnknown && !(UV && (ALLUV || (S.mats[mat_hint].flags & MATF_NEEDS_UV)))) {
                 ART_STAT_WAVE(42);
                 ART_STAT_LANE(43);
-                rect_surface<R, false>(sp_p, sp_n, ff, su, sv, static_cast<int>(face), R(0), R(0), R(0), R(0), r, t);
+                rect_surface<false>(sp_p, sp_n, ff, su, sv, static_cast<int>(face), 0.0, 0.0, 0.0, 0.0, r, t);
                 mat = mat_hint;
                 break;
             }
             ART_STAT_WAVE(38);
             ART_STAT_LANE(39);
-            const RectRec<R>& q = S.rects[idx];
-            rect_surface<R, UV>(sp_p, sp_n, ff, su, sv, static_cast<int>(q.axis), q.a0, q.a1, q.b0, q.b1, r, t, ALLUV || (S.mats[q.mat].flags & MATF_NEEDS_UV) != 0);
+            const RectRec& q = S.rects[idx];
+            rect_surface<UV>(sp_p, sp_n, ff, su, sv, static_cast<int>(q.axis), q.a0, q.a1, q.b0, q.b1, r, t, ALLUV || (S.mats[q.mat].flags & MATF_NEEDS_UV) != 0);
             mat = q.mat;
             break;
         }
@@ -1490,17 +1446,17 @@ __device__ __forceinline__ void prim_surface(const DevScene<R>& S, uint32_t ref,
             if (mat_hint != kMatUnknown && !(UV && (ALLUV || (S.mats[mat_hint].flags & MATF_NEEDS_UV)))) {
                 ART_STAT_WAVE(42);
                 ART_STAT_LANE(43);
-                rect_surface<R, false>(sp_p, sp_n, ff, su, sv, static_cast<int>(face >> 1), R(0), R(0), R(0), R(0), r, t);  // box_face: axis = f >> 1
+                rect_surface<false>(sp_p, sp_n, ff, su, sv, static_cast<int>(face >> 1), 0.0, 0.0, 0.0, 0.0, r, t);  // box_face: axis = f >> 1
                 mat = mat_hint;
                 break;
             }
             ART_STAT_WAVE(38);
             ART_STAT_LANE(39);
-            const BoxRec<R>& b = S.boxes[idx];
+            const BoxRec& b = S.boxes[idx];
             int axis;
-            R a0, a1, b0, b1, k;
+            double a0, a1, b0, b1, k;
             box_face(b, static_cast<int>(face), axis, a0, a1, b0, b1, k);
-            rect_surface<R, UV>(sp_p, sp_n, ff, su, sv, axis, a0, a1, b0, b1, r, t, ALLUV || (S.mats[b.mat].flags & MATF_NEEDS_UV) != 0);
+            rect_surface<UV>(sp_p, sp_n, ff, su, sv, axis, a0, a1, b0, b1, r, t, ALLUV || (S.mats[b.mat].flags & MATF_NEEDS_UV) != 0);
             mat = b.mat;
             break;
         }
@@ -1515,8 +1471,8 @@ __device__ __forceinline__ void prim_surface(const DevScene<R>& S, uint32_t ref,
 
 // Rebuilds the hit_record of the world object that won (transform chain unwound as translate::hit / rotate_y::hit
 // do it: hittable.cpp:7-11, :72-84, including set_face_normal against the transformed ray).
-template <class R, uint32_t F, bool UV = true, bool TUV = UV, bool ALLUV = false>
-__device__ __forceinline__ void world_surface(const DevScene<R>& S, const HitOut& h, const Ray<R>& r, R t, Surf<R>& s, const double* uvc = nullptr) {
+template <uint32_t F, bool UV = true, bool TUV = UV, bool ALLUV = false>
+__device__ __forceinline__ void world_surface(const DevScene& S, const HitOut& h, const Ray& r, double t, Surf& s, const double* uvc = nullptr) {
     const int32_t w = static_cast<int32_t>(h.obj & 0xFFFFu);
     int32_t oi = S.world[w];
     ART_STAT_WAVE(44);
@@ -1525,23 +1481,23 @@ __device__ __forceinline__ void world_surface(const DevScene<R>& S, const HitOut
         ART_STAT_WAVE(36);
         ART_STAT_LANE(37);
         s.p = r.at(t);
-        s.n = mk(R(1), R(0), R(0));
+        s.n = mk(1.0, 0.0, 0.0);
         s.ff = true;
-        s.u = R(0);
-        s.v = R(0);
+        s.u = 0.0;
+        s.v = 0.0;
         s.mat = static_cast<uint32_t>(S.objs[oi].b);
         return;
     }
     static_assert(kMaxXformChain == 2, "world_surface unwinds at most two transforms");
     int32_t o0 = -1, o1 = -1;
-    Ray<R> r1 = r, r2 = r;
+    Ray r1 = r, r2 = r;
     if (F & F_XFORM) {
-        const ObjRec<R>& o = S.objs[oi];
+        const ObjRec& o = S.objs[oi];
         if (o.kind == OBJ_TRANSLATE || o.kind == OBJ_ROTATE_Y) {
             o0 = oi;
             r1 = xform_in(o, r);
             oi = o.a;
-            const ObjRec<R>& q = S.objs[oi];
+            const ObjRec& q = S.objs[oi];
             if (q.kind == OBJ_TRANSLATE || q.kind == OBJ_ROTATE_Y) {
                 o1 = oi;
                 r2 = xform_in(q, r1);
@@ -1551,7 +1507,7 @@ __device__ __forceinline__ void world_surface(const DevScene<R>& S, const HitOut
             }
         }
     }
-    prim_surface<R, F, UV, TUV, ALLUV>(S, h.prim, h.obj >> 16, r2, t, s, (F & F_TRI) == 0 ? h.mt : kMatUnknown, uvc);
+    prim_surface<F, UV, TUV, ALLUV>(S, h.prim, h.obj >> 16, r2, t, s, (F & F_TRI) == 0 ? h.mt : kMatUnknown, uvc);
     if (!(F & F_XFORM)) return;
 #ifdef ART_STATS
     if (o0 >= 0) {
@@ -1559,14 +1515,14 @@ __device__ __forceinline__ void world_surface(const DevScene<R>& S, const HitOut
         ART_STAT_LANE(35);
     }
 #endif
-    auto unwind = [&](int32_t xo, const Ray<R>& inner) {
-        const ObjRec<R>& o = S.objs[xo];
+    auto unwind = [&](int32_t xo, const Ray& inner) {
+        const ObjRec& o = S.objs[xo];
         if (o.kind == OBJ_TRANSLATE) {
             s.p = s.p + mk(o.p[0], o.p[1], o.p[2]);
             set_face_normal(s, inner, s.n);
         } else {
-            const R sn = o.p[0], c = o.p[1];
-            V3<R> p = s.p, n = s.n;
+            const double sn = o.p[0], c = o.p[1];
+            V3 p = s.p, n = s.n;
             p.x = c * s.p.x + sn * s.p.z;
             p.z = -sn * s.p.x + c * s.p.z;
             n.x = c * s.n.x + sn * s.n.z;
@@ -1580,49 +1536,47 @@ __device__ __forceinline__ void world_surface(const DevScene<R>& S, const HitOut
 }
 
 // ------------------------------------------------------------------------------------------------ textures
-template <class R>
-__device__ __forceinline__ R perlin_noise(const PerlinRec<R>& pn, V3<R> p) {  // perlin.h:21-40, :83-97
-    const R u = p.x - floor(p.x), v = p.y - floor(p.y), w = p.z - floor(p.z);
+__device__ __forceinline__ double perlin_noise(const PerlinRec& pn, V3 p) {  // perlin.h:21-40, :83-97
+    const double u = p.x - floor(p.x), v = p.y - floor(p.y), w = p.z - floor(p.z);
     const int i = static_cast<int>(floor(p.x)), j = static_cast<int>(floor(p.y)), k = static_cast<int>(floor(p.z));
-    const R uu = u * u * (R(3) - R(2) * u), vv = v * v * (R(3) - R(2) * v), ww = w * w * (R(3) - R(2) * w);
+    const double uu = u * u * (3.0 - 2.0 * u), vv = v * v * (3.0 - 2.0 * v), ww = w * w * (3.0 - 2.0 * w);
     // perlin_interp's weights i*uu + (1-i)*(1-uu) with i in {0, 1}: u, v, w lie in [+0, 1), so uu, vv, ww and 1 - uu,
     // ... are >= +0 and finite; 0 * x is then +0, 1 * x is x and x + (+0) is x -- the weight is exactly 1 - uu (i = 0)
     // or uu (i = 1), and u - 0 is exactly u.  Folding them (the compiler may not: 0 * x is not +0 for every double)
     // leaves the same products and sums in the same order.
-    const R wx[2] = {R(1) - uu, uu}, wy[2] = {R(1) - vv, vv}, wz[2] = {R(1) - ww, ww};
-    const R dx[2] = {u, u - R(1)}, dy[2] = {v, v - R(1)}, dz[2] = {w, w - R(1)};
+    const double wx[2] = {1.0 - uu, uu}, wy[2] = {1.0 - vv, vv}, wz[2] = {1.0 - ww, ww};
+    const double dx[2] = {u, u - 1.0}, dy[2] = {v, v - 1.0}, dz[2] = {w, w - 1.0};
     const int px[2] = {pn.perm[0][i & 255], pn.perm[0][(i + 1) & 255]};
     const int py[2] = {pn.perm[1][j & 255], pn.perm[1][(j + 1) & 255]};
     const int pz[2] = {pn.perm[2][k & 255], pn.perm[2][(k + 1) & 255]};
-    R accum = R(0);
+    double accum = 0.0;
 #pragma unroll
     for (int a = 0; a < 2; a++)
 #pragma unroll
         for (int b = 0; b < 2; b++)
 #pragma unroll
             for (int c = 0; c < 2; c++) {
-                const V3<R> g = ld3(pn.ranvec[px[a] ^ py[b] ^ pz[c]]);
+                const V3 g = ld3(pn.ranvec[px[a] ^ py[b] ^ pz[c]]);
                 accum += wx[a] * wy[b] * wz[c] * dot(g, mk(dx[a], dy[b], dz[c]));
             }
     return accum;
 }
 // perlin noise out of line, as the medium's log and get_sphere_uv: measured r4z3 the two-perlin-spheres scene +6.5 %,
 // the Next-Week final +-0
-[[maybe_unused]] static __device__ __noinline__ double perlin_call(const PerlinRec<double>* pn, double x, double y, double z) {
+[[maybe_unused]] static __device__ __noinline__ double perlin_call(const PerlinRec* pn, double x, double y, double z) {
     return perlin_noise(*pn, mk(x, y, z));
 }
-template <class R>
-__device__ __forceinline__ V3<R> image_value(const DevScene<R>& S, int32_t im, R u, R v) {  // texture.h:90-117
+__device__ __forceinline__ V3 image_value(const DevScene& S, int32_t im, double u, double v) {  // texture.h:90-117
     const ImageRec& I = S.images[im];
-    u = fmin(fmax(u, R(0)), R(1));
-    v = R(1) - fmin(fmax(v, R(0)), R(1));
-    int i = static_cast<int>(u * R(I.w));
-    int j = static_cast<int>(v * R(I.h));
+    u = fmin(fmax(u, 0.0), 1.0);
+    v = 1.0 - fmin(fmax(v, 0.0), 1.0);
+    int i = static_cast<int>(u * static_cast<double>(I.w));
+    int j = static_cast<int>(v * static_cast<double>(I.h));
     if (i >= I.w) i = I.w - 1;
     if (j >= I.h) j = I.h - 1;
-    const R cs = R(1.0 / 255.0);
+    const double cs = 1.0 / 255.0;
     const uint8_t* px = S.texels + I.offset + static_cast<uint64_t>(j) * static_cast<uint64_t>(I.bpp * I.w) + static_cast<uint64_t>(i) * I.bpp;
-    return mk(cs * R(px[0]), cs * R(px[1]), cs * R(px[2]));
+    return mk(cs * static_cast<double>(px[0]), cs * static_cast<double>(px[1]), cs * static_cast<double>(px[2]));
 }
 // checker_texture (texture.h:41-48): sin(10x)*sin(10y)*sin(10z) < 0.  Only the SIGN of the product matters, so it
 // is evaluated as a sign parity: sin(y) == 0 exactly iff y == 0 for doubles (pi is irrational), and for y != 0
@@ -1630,23 +1584,21 @@ __device__ __forceinline__ V3<R> image_value(const DevScene<R>& S, int32_t im, R
 // full f64 sin (46 VGPRs in the shade kernel); it can only differ when y is within ~1 ulp of a multiple of pi.
 // sin(y) < 0 as a bool (y != 0): floor(y / pi) odd, the parity read in floating point (k / 2 == floor(k / 2) for even
 // k; every double >= 2^53 is even, as its integer conversion would say) -- no f64 -> int64 conversion sequence.
-template <class R>
-__device__ __forceinline__ bool sin_negative(R y) {
-    const R k = floor(y * R(0.31830988618379067154));
-    return R(0.5) * k != floor(R(0.5) * k);
+__device__ __forceinline__ bool sin_negative(double y) {
+    const double k = floor(y * 0.31830988618379067154);
+    return 0.5 * k != floor(0.5 * k);
 }
-template <class R>
-__device__ __forceinline__ bool checker_odd(V3<R> p) {  // sin(10x) * sin(10y) * sin(10z) < 0
-    const R x = R(10) * p.x, y = R(10) * p.y, z = R(10) * p.z;
-    const bool nonzero = x != R(0) && y != R(0) && z != R(0);
+__device__ __forceinline__ bool checker_odd(V3 p) {  // sin(10x) * sin(10y) * sin(10z) < 0
+    const double x = 10.0 * p.x, y = 10.0 * p.y, z = 10.0 * p.z;
+    const bool nonzero = x != 0.0 && y != 0.0 && z != 0.0;
     return nonzero && (sin_negative(x) != (sin_negative(y) != sin_negative(z)));
 }
 
 // rendering/texture.h.  TF (layout.h TexFeature bits) prunes the texture kinds a scene cannot contain.
-template <class R, uint32_t TF = TF_ALL>
-__device__ __forceinline__ V3<R> tex_value(const DevScene<R>& S, int32_t ti, R u, R v, V3<R> p) {
+template <uint32_t TF = TF_ALL>
+__device__ __forceinline__ V3 tex_value(const DevScene& S, int32_t ti, double u, double v, V3 p) {
     for (int level = 0; level < 4; ++level) {
-        const TexRec<R>& t = S.texs[ti];
+        const TexRec& t = S.texs[ti];
         if (TF == TF_SOLID || t.type == TEX_SOLID) return ld3(t.c);
         if ((TF & TF_CHECKER) && t.type == TEX_CHECKER) {
             ti = checker_odd(p) ? t.odd : t.even;
@@ -1655,9 +1607,9 @@ __device__ __forceinline__ V3<R> tex_value(const DevScene<R>& S, int32_t ti, R u
         if ((TF & TF_NOISE) && t.type == TEX_NOISE) {
             ART_STAT_WAVE(28);
             ART_STAT_LANE(29);
-            const V3<R> q = t.scale * p;
-            const R n = perlin_call(&S.perlins[t.perlin], q.x, q.y, q.z);
-            const R h = (R(1) + n) * R(0.5);
+            const V3 q = t.scale * p;
+            const double n = perlin_call(&S.perlins[t.perlin], q.x, q.y, q.z);
+            const double h = (1.0 + n) * 0.5;
             return mk(h, h, h);
         }
         if ((TF & TF_IMAGE) && t.type == TEX_IMAGE) {
@@ -1666,20 +1618,20 @@ __device__ __forceinline__ V3<R> tex_value(const DevScene<R>& S, int32_t ti, R u
             return image_value(S, t.image, u, v);
         }
         if ((TF & (TF_IMAGE | TF_BARY)) && t.type == TEX_BARY_IMAGE) {
-            const R w = R(1) - u - v;
+            const double w = 1.0 - u - v;
             return image_value(S, t.image, u * t.uv[0] + v * t.uv[2] + w * t.uv[4], u * t.uv[1] + v * t.uv[3] + w * t.uv[5]);
         }
         break;
     }
-    return mk(R(0), R(1), R(1));
+    return mk(0.0, 1.0, 1.0);
 }
 
 // The texture value of material m (lambertian / diffuse_light / isotropic): the inlined solid colour (MATF_SOLID) or
 // tex_value of its texture tree -- the same doubles either way.
-template <class R, uint32_t TF = TF_ALL>
-__device__ __forceinline__ V3<R> mat_tex_value(const DevScene<R>& S, const MatRec<R>& m, R u, R v, V3<R> p) {
+template <uint32_t TF = TF_ALL>
+__device__ __forceinline__ V3 mat_tex_value(const DevScene& S, const MatRec& m, double u, double v, V3 p) {
     if (m.flags & MATF_SOLID) return ld3(m.albedo);
-    return tex_value<R, TF>(S, m.tex, u, v, p);
+    return tex_value<TF>(S, m.tex, u, v, p);
 }
 
 }  // namespace art

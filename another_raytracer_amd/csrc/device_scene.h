@@ -10,10 +10,9 @@
 
 namespace art {
 
-template <class R>
 struct DeviceScene {
     std::vector<void*> allocs;
-    DevScene<R> view{};
+    DevScene view{};
     bool media = false;
     uint32_t features = F_ALL;
     int max_stack = kMaxStackDepth;
@@ -48,7 +47,6 @@ constexpr size_t kLdsPerCu = 160 * 1024;  // gfx950
 inline uint32_t stack_rows(int max_stack) { return static_cast<uint32_t>(std::max(1, max_stack)) + 2u; }
 inline size_t extend_lds_bytes(bool L, uint32_t stack) { return extend_pre_offset(L, stack) + 4 * (kShards + 1); }
 
-template <class R>
-void build_device_scene(const FlatScene& f0, DeviceScene<R>& ds);  // device_scene.hip: R = double
+void build_device_scene(const FlatScene& f0, DeviceScene& ds);  // device_scene.hip
 
 }  // namespace art

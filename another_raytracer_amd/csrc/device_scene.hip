@@ -11,12 +11,6 @@
 
 namespace art {
 
-template <class R, class D>
-static void cvt_sphere(const SphereRec<D>& s, SphereRec<R>& o) {
-    for (int a = 0; a < 3; ++a) { o.c[a] = R(s.c[a]); o.d[a] = R(s.d[a]); }
-    o.r = R(s.r); o.t0 = R(s.t0); o.dt = R(s.dt); o.mat = s.mat; o.flags = s.flags;
-}
-
 // Builds the layout.h LDS scene image when the f64 scene qualifies: spheres only, every BVH node and leaf slot within
 // the plane capacities, and image + stack within one CU's LDS.  Returns an empty vector otherwise.
 static std::vector<uint8_t> lds_scene_image(const FlatScene& f, uint32_t& nmov, bool& shade_ok) {
@@ -33,7 +27,7 @@ static std::vector<uint8_t> lds_scene_image(const FlatScene& f, uint32_t& nmov, 
         if (w < 0 || static_cast<size_t>(w) >= f.objs.size() || f.objs[w].kind != OBJ_BVH) return img;
     for (uint32_t ref : f.primrefs) {
         if (primref_type(ref) != PRIM_SPHERE) return img;
-        const SphereRec<double>& sp = f.spheres[primref_index(ref)];
+        const SphereRec& sp = f.spheres[primref_index(ref)];
         if (sp.flags & SPH_MOVING) {
             // the image's moving spheres span the unit shutter (every moving_sphere of the reference scenes,
             // scene_manager.cpp:34-35, :201): their centre fraction is the ray time itself (hit_lds_slot); and they
@@ -143,7 +137,7 @@ static std::vector<uint8_t> lds_scene_image(const FlatScene& f, uint32_t& nmov, 
 // an empty vector when the leaves overlap or the padded codes still do not fit.  A leaf tests the same primitives in
 // the same order, so every closest hit, and the image, is unchanged.
 static std::vector<uint32_t> pair_align_leaves(const std::vector<uint32_t>& primrefs, std::vector<BvhNode>& nodes,
-                                               std::vector<ObjRec<double>>& objs, std::vector<uint8_t>& pad) {
+                                               std::vector<ObjRec>& objs, std::vector<uint8_t>& pad) {
     std::vector<std::pair<uint32_t, uint32_t>> leaves;  // (first, count)
     for (const BvhNode& b : nodes)
         for (int c = 0; c < 4; ++c)
@@ -187,8 +181,7 @@ static std::vector<uint32_t> pair_align_leaves(const std::vector<uint32_t>& prim
     return out;
 }
 
-template <class R>
-void build_device_scene(const FlatScene& f0, DeviceScene<R>& ds) {
+void build_device_scene(const FlatScene& f0, DeviceScene& ds) {
     // the device copy of the BVH arrays, with leaves pair-aligned where 16-bit codes need it (pair_align_leaves)
     FlatScene f = f0;
     std::vector<uint8_t> slot_pad(f.primrefs.size(), 0);
@@ -205,7 +198,7 @@ void build_device_scene(const FlatScene& f0, DeviceScene<R>& ds) {
         const bool mesh = (f.features & ~kFeatMesh) == 0 && (f.features & F_TRI) != 0;
         if (!fit && mesh && f.nodes.size() <= 32768u && opt(Opt::Leaf2) != 0) {
             std::vector<BvhNode> nodes = f.nodes;
-            std::vector<ObjRec<double>> objs = f.objs;
+            std::vector<ObjRec> objs = f.objs;
             std::vector<uint8_t> pad;
             std::vector<uint32_t> refs = pair_align_leaves(f.primrefs, nodes, objs, pad);
             if (!refs.empty()) {
@@ -217,57 +210,27 @@ void build_device_scene(const FlatScene& f0, DeviceScene<R>& ds) {
             }
         }
     }
-    std::vector<SphereRec<R>> sph(f.spheres.size());
-    for (size_t i = 0; i < sph.size(); ++i) cvt_sphere(f.spheres[i], sph[i]);
-    std::vector<TriRec<R>> tri(f.tris.size());
-    for (size_t i = 0; i < tri.size(); ++i) {
-        for (int a = 0; a < 9; ++a) tri[i].p[a] = R(f.tris[i].p[a]);
-        tri[i].mat = f.tris[i].mat;
-        tri[i].pad = 0;
-    }
-    std::vector<RectRec<R>> rect(f.rects.size());
-    for (size_t i = 0; i < rect.size(); ++i) {
-        const auto& s = f.rects[i];
-        rect[i] = RectRec<R>{R(s.a0), R(s.a1), R(s.b0), R(s.b1), R(s.k), s.axis, s.mat};
-    }
-    std::vector<BoxRec<R>> box(f.boxes.size());
-    for (size_t i = 0; i < box.size(); ++i) {
-        for (int a = 0; a < 3; ++a) { box[i].mn[a] = R(f.boxes[i].mn[a]); box[i].mx[a] = R(f.boxes[i].mx[a]); }
-        box[i].mat = f.boxes[i].mat;
-        box[i].pad = 0;
-    }
-    std::vector<ObjRec<R>> objs(f.objs.size());
-    for (size_t i = 0; i < objs.size(); ++i) {
-        objs[i].kind = f.objs[i].kind; objs[i].a = f.objs[i].a; objs[i].b = f.objs[i].b; objs[i].pad = 0;
-        for (int a = 0; a < 4; ++a) objs[i].p[a] = R(f.objs[i].p[a]);
-    }
-    std::vector<MatRec<R>> mats(f.mats.size());
-    for (size_t i = 0; i < mats.size(); ++i) {
-        mats[i].type = f.mats[i].type; mats[i].tex = f.mats[i].tex; mats[i].flags = f.mats[i].flags; mats[i].pad = 0;
-        for (int a = 0; a < 3; ++a) mats[i].albedo[a] = R(f.mats[i].albedo[a]);
-        mats[i].fuzz = R(f.mats[i].fuzz); mats[i].ir = R(f.mats[i].ir);
-        mats[i].flags &= ~static_cast<uint32_t>(MATF_SOLID);
-        const int32_t t = f.mats[i].tex;
-        const uint32_t ty = f.mats[i].type;
-        if ((ty == MAT_LAMBERTIAN || ty == MAT_LIGHT || ty == MAT_ISOTROPIC) && t >= 0 && static_cast<size_t>(t) < f.texs.size() &&
+    // the records go up as the flat scene holds them (f64 throughout), with their pad words zeroed
+    for (auto& t : f.tris) t.pad = 0;
+    for (auto& b : f.boxes) b.pad = 0;
+    for (auto& o : f.objs) o.pad = 0;
+    for (auto& t : f.texs) t.pad = 0;
+    const std::vector<SphereRec>& sph = f.spheres;
+    const std::vector<TriRec>& tri = f.tris;
+    const std::vector<RectRec>& rect = f.rects;
+    const std::vector<BoxRec>& box = f.boxes;
+    const std::vector<ObjRec>& objs = f.objs;
+    std::vector<MatRec> mats = f.mats;
+    for (MatRec& m : mats) {
+        m.pad = 0;
+        m.flags &= ~static_cast<uint32_t>(MATF_SOLID);
+        const int32_t t = m.tex;
+        if ((m.type == MAT_LAMBERTIAN || m.type == MAT_LIGHT || m.type == MAT_ISOTROPIC) && t >= 0 && static_cast<size_t>(t) < f.texs.size() &&
             f.texs[t].type == TEX_SOLID) {
             // the solid colour itself: tex_value's ld3(t.c), the same doubles
-            for (int a = 0; a < 3; ++a) mats[i].albedo[a] = R(f.texs[t].c[a]);
-            mats[i].flags |= MATF_SOLID;
+            for (int a = 0; a < 3; ++a) m.albedo[a] = f.texs[t].c[a];
+            m.flags |= MATF_SOLID;
         }
-    }
-    std::vector<TexRec<R>> texs(f.texs.size());
-    for (size_t i = 0; i < texs.size(); ++i) {
-        const auto& s = f.texs[i];
-        texs[i].type = s.type; texs[i].even = s.even; texs[i].odd = s.odd; texs[i].perlin = s.perlin; texs[i].image = s.image; texs[i].pad = 0;
-        for (int a = 0; a < 3; ++a) texs[i].c[a] = R(s.c[a]);
-        texs[i].scale = R(s.scale);
-        for (int a = 0; a < 6; ++a) texs[i].uv[a] = R(s.uv[a]);
-    }
-    std::vector<PerlinRec<R>> per(f.perlins.size());
-    for (size_t i = 0; i < per.size(); ++i) {
-        for (int v = 0; v < 256; ++v) for (int a = 0; a < 3; ++a) per[i].ranvec[v][a] = R(f.perlins[i].ranvec[v][a]);
-        std::memcpy(per[i].perm, f.perlins[i].perm, sizeof per[i].perm);
     }
     ds.view.spheres = ds.upload(sph);
     ds.view.tris = ds.upload(tri);
@@ -275,19 +238,19 @@ void build_device_scene(const FlatScene& f0, DeviceScene<R>& ds) {
     ds.view.boxes = ds.upload(box);
     ds.view.primrefs = ds.upload(f.primrefs);
     {  // every scene with a BVH: any kernel instantiated with triangles reads it, whatever the scene holds
-        std::vector<TriRec<R>> lt(f.primrefs.size());
+        std::vector<TriRec> lt(f.primrefs.size());
         for (size_t i = 0; i < lt.size(); ++i)
             if (!slot_pad[i] && primref_type(f.primrefs[i]) == PRIM_TRIANGLE) lt[i] = tri[primref_index(f.primrefs[i])];
         ds.view.leaf_tris = ds.upload(lt);
-        if constexpr (std::is_same<R, double>::value) {
+        {
             // TriRec112: the plane of each leaf triangle by the device's operations in its order (device.h cross, dot;
             // -ffp-contract=off on both sides): n = cross(p2 - p1, p3 - p1), dd = -dot(n, p1), bit for bit
-            std::vector<TriRec112<R>> l112(lt.size());
+            std::vector<TriRec112> l112(lt.size());
             for (size_t i = 0; i < lt.size(); ++i) {
-                const R* q = lt[i].p;
-                const R ux = q[3] - q[0], uy = q[4] - q[1], uz = q[5] - q[2];
-                const R vx = q[6] - q[0], vy = q[7] - q[1], vz = q[8] - q[2];
-                const R nx = uy * vz - uz * vy, ny = uz * vx - ux * vz, nz = ux * vy - uy * vx;
+                const double* q = lt[i].p;
+                const double ux = q[3] - q[0], uy = q[4] - q[1], uz = q[5] - q[2];
+                const double vx = q[6] - q[0], vy = q[7] - q[1], vz = q[8] - q[2];
+                const double nx = uy * vz - uz * vy, ny = uz * vx - ux * vz, nz = ux * vy - uy * vx;
                 for (int k = 0; k < 9; ++k) l112[i].p[k] = q[k];
                 l112[i].n[0] = nx;
                 l112[i].n[1] = ny;
@@ -354,14 +317,12 @@ void build_device_scene(const FlatScene& f0, DeviceScene<R>& ds) {
                 default: std::memcpy(op[i].b, &box[idx], sizeof(box[idx])); break;
             }
         }
-        static_assert(sizeof(SphereRec<R>) <= sizeof(PrimRec80) && sizeof(TriRec<R>) <= sizeof(PrimRec80) &&
-                      sizeof(RectRec<R>) <= sizeof(PrimRec80) && sizeof(BoxRec<R>) <= sizeof(PrimRec80), "PrimRec80 holds every record");
         ds.view.obj_prims = ds.upload(op);
     }
     ds.view.world = ds.upload(f.world);
     ds.view.mats = ds.upload(mats);
-    ds.view.texs = ds.upload(texs);
-    ds.view.perlins = ds.upload(per);
+    ds.view.texs = ds.upload(f.texs);
+    ds.view.perlins = ds.upload(f.perlins);
     {  // [sphere_uv.h's table][image records]: device.h uv_table reads the table in front of DevScene::images
         std::vector<uint8_t> ib(kUvTableBytes + sizeof(ImageRec) * f.images.size(), 0);
         std::memcpy(ib.data(), glibc_trig_data::kTrigHost, sizeof(glibc_trig_data::kTrigHost));
@@ -369,7 +330,7 @@ void build_device_scene(const FlatScene& f0, DeviceScene<R>& ds) {
         ds.view.images = reinterpret_cast<const ImageRec*>(ds.upload(ib) + kUvTableBytes);
     }
     ds.view.texels = ds.upload(f.texels);
-    if (std::is_same<R, double>::value) {
+    {
         uint32_t nmov = 0;
         bool shade_ok = false;
         const std::vector<uint8_t> img = ds.leaf_shift ? std::vector<uint8_t>() : lds_scene_image(f, nmov, shade_ok);
@@ -385,7 +346,7 @@ void build_device_scene(const FlatScene& f0, DeviceScene<R>& ds) {
     ds.view.n_primrefs = static_cast<uint32_t>(f.primrefs.size());
     ds.view.n_tris = static_cast<uint32_t>(f.tris.size());
     ds.view.nworld = static_cast<int32_t>(f.world.size());
-    for (int a = 0; a < 3; ++a) ds.view.bg[a] = R(f.background[a]);
+    for (int a = 0; a < 3; ++a) ds.view.bg[a] = f.background[a];
     ds.media = f.has_media;
     ds.features = f.features;
     ds.max_stack = f.max_stack;
@@ -412,6 +373,5 @@ void build_device_scene(const FlatScene& f0, DeviceScene<R>& ds) {
     ds.mat_types = 0;
     for (const auto& m : f.mats) ds.mat_types |= 1u << m.type;
 }
-template void build_device_scene<double>(const FlatScene&, DeviceScene<double>&);
 
 }  // namespace art

@@ -55,7 +55,7 @@ struct PathPool {
     }
     // Claims the next 64 slots and generates their camera rays: true for a lane whose slot is a pixel of the pass
     // (st: the new path, q: its slot); a padding slot of a partial tile or a slot >= P does nothing.
-    __device__ __forceinline__ bool batch(const PassGeom& sg, const CameraRec<double>& sc, uint32_t* next_slot, uint32_t lane, PathState<double>& st,
+    __device__ __forceinline__ bool batch(const PassGeom& sg, const CameraRec& sc, uint32_t* next_slot, uint32_t lane, PathState& st,
                                           uint32_t& q) {
         if (cur == end) {
             const uint32_t chunk = sg.chunk;
@@ -79,7 +79,7 @@ struct PathPool {
         return true;
     }
     // The paths a batch displaces, compacted: the busy lane of rank r among `m` stores at pool_push_pos(count, r).
-    __device__ __forceinline__ void push(uint64_t m, uint32_t rank, bool busy, const PathState<double>& st, uint32_t q, int depth) {
+    __device__ __forceinline__ void push(uint64_t m, uint32_t rank, bool busy, const PathState& st, uint32_t q, int depth) {
         if (busy) {
             PoolRay& e = base[pool_push_pos(count, rank)];
             e.a = make_double2(st.ray.o.x, st.ray.o.y);
@@ -95,7 +95,7 @@ struct PathPool {
         __asm__ volatile("" ::: "memory");  // the stores are issued before the batch's camera rays and trace
     }
     // The idle lane of rank `rank` < npop takes the entry pool_pop_pos(count, rank); the caller lowers count by npop.
-    __device__ __forceinline__ void pop(uint32_t rank, PathState<double>& st, uint32_t& q, int& depth) const {
+    __device__ __forceinline__ void pop(uint32_t rank, PathState& st, uint32_t& q, int& depth) const {
         const PoolRay& e = base[pool_pop_pos(count, rank)];
         const double2 a = e.a, b = e.b, c = e.c, d = e.d, f = e.e;
         st.ray.o = mk(a.x, a.y, b.x);
@@ -107,8 +107,7 @@ struct PathPool {
         depth = static_cast<int>(e.depth);
     }
 };
-__global__ __launch_bounds__(kBlockL, 1) void k_paths(DevScene<double> S0, PassGeom g, CameraRec<double> cam, Work<double> w, uint32_t* next_slot) {
-    using R = double;
+__global__ __launch_bounds__(kBlockL, 1) void k_paths(DevScene S0, PassGeom g, CameraRec cam, Work w, uint32_t* next_slot) {
     constexpr int B = kBlockL;
     // dynamic LDS only (no static __shared__, so the image starts at LDS address 0 and every image offset is an
     // immediate): [scene image][traversal stack][camera][pass geometry] -- the camera and pass geometry are read
@@ -118,8 +117,8 @@ __global__ __launch_bounds__(kBlockL, 1) void k_paths(DevScene<double> S0, PassG
     const uint8_t* lds = smem;
     StackT<true>* stk = reinterpret_cast<StackT<true>*>(smem + kLdsImageBytes) + B + stack_column<true>(threadIdx.x);
     JumpEntry* jt = reinterpret_cast<JumpEntry*>(smem + kLdsImageBytes + paths_stack_bytes(g.stack));
-    CameraRec<double>& s_cam = *reinterpret_cast<CameraRec<double>*>(smem + kLdsImageBytes + paths_stack_bytes(g.stack) + kJumpBytes);
-    PassGeom& s_g = *reinterpret_cast<PassGeom*>(smem + kLdsImageBytes + paths_stack_bytes(g.stack) + kJumpBytes + sizeof(CameraRec<double>));
+    CameraRec& s_cam = *reinterpret_cast<CameraRec*>(smem + kLdsImageBytes + paths_stack_bytes(g.stack) + kJumpBytes);
+    PassGeom& s_g = *reinterpret_cast<PassGeom*>(smem + kLdsImageBytes + paths_stack_bytes(g.stack) + kJumpBytes + sizeof(CameraRec));
     stk[-B] = static_cast<StackT<true>>(kNodeEmpty);
     load_lds_image<B>(S0.lds_image, smem);
     if (threadIdx.x < static_cast<uint32_t>(kJumpEntries)) jt[threadIdx.x] = pcg_jump(3u * threadIdx.x);
@@ -132,24 +131,24 @@ __global__ __launch_bounds__(kBlockL, 1) void k_paths(DevScene<double> S0, PassG
             s_g.P = n * g.k;
         }
     }
-    DevScene<double> S = S0;
+    DevScene S = S0;
     {
         uint8_t* wb = smem + paths_lds_head(g.stack);
         uint8_t* ob = wb + sizeof(int32_t) * kPathsWorldCap;
         if (threadIdx.x < static_cast<uint32_t>(S0.nworld)) reinterpret_cast<int32_t*>(wb)[threadIdx.x] = S0.world[threadIdx.x];
-        if (threadIdx.x < S0.n_objs * (sizeof(ObjRec<double>) / 16))
+        if (threadIdx.x < S0.n_objs * (sizeof(ObjRec) / 16))
             reinterpret_cast<uint4*>(ob)[threadIdx.x] = reinterpret_cast<const uint4*>(S0.objs)[threadIdx.x];
         S.world = reinterpret_cast<const int32_t*>(wb);
-        S.objs = reinterpret_cast<const ObjRec<double>*>(ob);
+        S.objs = reinterpret_cast<const ObjRec*>(ob);
     }
     __syncthreads();
     const uint32_t lane = __lane_id();
     const uint64_t below = (1ull << lane) - 1ull;
-    const V3<R> bg = mk(S.bg[0], S.bg[1], S.bg[2]);
+    const V3 bg = mk(S.bg[0], S.bg[1], S.bg[2]);
     bool busy = false;
     uint32_t q = 0;
     int depth = 0;
-    PathState<R> st;
+    PathState st;
     unsigned long long segs = 0;
 #ifdef ART_STATS
     unsigned long long tm_load = 0, tm_trace = 0, tm_shade = 0, tm_app = 0, tm_fb = 0, tm_prev = __builtin_amdgcn_s_memtime();
@@ -189,12 +188,12 @@ __global__ __launch_bounds__(kBlockL, 1) void k_paths(DevScene<double> S0, PassG
             act = busy;
         }
         ART_TICK((fb ? tm_fb : tm_load));
-        R t = R(0);
+        double t = 0.0;
         HitOut h{0, 0, kMatUnknown};
         bool hitw = false;
         if (act) {
             ++segs;
-            hitw = trace_world<R, kFeatSpheres, B, true>(S, lds, st.ray, stk, st.rng, t, h);
+            hitw = trace_world<kFeatSpheres, B, true>(S, lds, st.ray, stk, st.rng, t, h);
 #if ART_LDS_LEAF_NOREF
             if (hitw) h.mt = reinterpret_cast<const uint32_t*>(lds + kLdsOffRef)[h.obj >> 16] >> kLdsRefMatShift;
 #endif
@@ -205,11 +204,11 @@ __global__ __launch_bounds__(kBlockL, 1) void k_paths(DevScene<double> S0, PassG
         // the whole wave draws random_in_unit_sphere for its lambertian and metal hits (material.h:33, :55), which
         // scatter with it first; lights and the max_depth bounce draw nothing
         const bool need = act && hitw && (h.mt == MAT_LAMBERTIAN || h.mt == MAT_METAL) && depth + 1 < g.max_depth;
-        const V3<R> ps = coop_unit_sphere<R>(need, st.rng, jt);
+        const V3 ps = coop_unit_sphere(need, st.rng, jt);
         bool cont = false;
         if (act) {
             // a live path's radiance is zero: only a miss (engine.h:455-456) or a light adds to it, and both end the path
-            st.L = mk(R(0), R(0), R(0));
+            st.L = mk(0.0, 0.0, 0.0);
             if (hitw) {
                 cont = shade_hit_lds(lds, h.obj >> 16, h.mt, t, depth + 1 >= g.max_depth, st, &ps);
             } else {  // engine.h:455-456: miss -> background
@@ -247,7 +246,7 @@ __global__ __launch_bounds__(kBlockL, 1) void k_paths(DevScene<double> S0, PassG
 #endif
 }
 
-void launch_paths(int num_cu, hipStream_t st, const DevScene<double>& S, const PassGeom& g, const CameraRec<double>& cam, const Work<double>& w,
+void launch_paths(int num_cu, hipStream_t st, const DevScene& S, const PassGeom& g, const CameraRec& cam, const Work& w,
                   uint32_t* next_slot) {
     const size_t lds = paths_lds_bytes(g.stack);
     static const bool checked = static_lds_is_zero(reinterpret_cast<const void*>(k_paths));

@@ -27,7 +27,7 @@ __host__ __device__ constexpr size_t align128(size_t x) { return (x + 127u) & ~s
 // s16: 16-bit stack entries (F_CODE16 instantiations, device.h StackF)
 __host__ __device__ constexpr size_t paths_g_stack_bytes(uint32_t stack, int block, bool s16) { return (s16 ? 2u : 4u) * stack * block; }
 __host__ __device__ constexpr size_t paths_g_head_bytes(uint32_t stack, int block, bool s16) {  // stack, camera, pass geometry, jumps, u,v
-    return align16(paths_g_stack_bytes(stack, block, s16) + sizeof(CameraRec<double>) + sizeof(PassGeom)) + kJumpBytes + kUvConstBytes;
+    return align16(paths_g_stack_bytes(stack, block, s16) + sizeof(CameraRec) + sizeof(PassGeom)) + kJumpBytes + kUvConstBytes;
 }
 // LM kernels also hold the world list and the object records (a few KiB): every segment walks them, and a prim
 // object's test otherwise waits on three dependent L1 loads (world slot -> object -> primitive).  The textured ones
@@ -40,11 +40,11 @@ __host__ __device__ constexpr uint32_t lds_mats(uint32_t n_mats) {
     return ((TF & (TF_NOISE | TF_IMAGE)) != 0 && n_mats <= kMatsLdsCap) ? n_mats : 0u;
 }
 __host__ __device__ constexpr size_t paths_g_world_bytes(int32_t nworld, uint32_t n_objs, uint32_t n_lds_mats) {
-    return align16(sizeof(int32_t) * static_cast<uint32_t>(nworld)) + (sizeof(ObjRec<double>) + sizeof(PrimRec80)) * n_objs +
-           sizeof(MatRec<double>) * n_lds_mats;
+    return align16(sizeof(int32_t) * static_cast<uint32_t>(nworld)) + (sizeof(ObjRec) + sizeof(PrimRec80)) * n_objs +
+           sizeof(MatRec) * n_lds_mats;
 }
 // LM 1's LDS copy of the leaf triangle records: TriRec112 (plane precomputed, traverse's PL 2 path)
-constexpr size_t kLm1TriBytes = sizeof(TriRec112<double>);
+constexpr size_t kLm1TriBytes = sizeof(TriRec112);
 __host__ __device__ constexpr size_t paths_g_mesh_bytes(uint32_t n_nodes, uint32_t n_primrefs, uint32_t n_tris) {  // n_tris: 0 unless F_TRI
     return sizeof(BvhNode) * n_nodes + align16(sizeof(uint32_t) * n_primrefs) + kLm1TriBytes * n_tris;
 }
@@ -74,7 +74,7 @@ struct RingG {
     __device__ __forceinline__ double& at(uint32_t field, uint32_t k) const { return f[field * kRingG + k]; }
 };
 // 1 = a path starts (st, q), 0 = a padding slot (idle this round), 2 = the pass is drained
-__device__ __forceinline__ int ring_take_g(const RingG& ring, uint32_t k, uint32_t b0, PathState<double>& st, uint32_t& q) {
+__device__ __forceinline__ int ring_take_g(const RingG& ring, uint32_t k, uint32_t b0, PathState& st, uint32_t& q) {
     const double tm = ring.at(6, k);
     if (tm != tm) return 0;
     if (tm == __builtin_inf()) return 2;
@@ -87,7 +87,7 @@ __device__ __forceinline__ int ring_take_g(const RingG& ring, uint32_t k, uint32
     q = b0 + k;
     return 1;
 }
-__device__ __forceinline__ void ring_fill_g(const RingG& ring, uint32_t lane, uint32_t slot, const PassGeom& sg, const CameraRec<double>& sc) {
+__device__ __forceinline__ void ring_fill_g(const RingG& ring, uint32_t lane, uint32_t slot, const PassGeom& sg, const CameraRec& sc) {
     double v[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, __builtin_inf(), 0.0};
     if (slot < sg.P) {
         v[6] = __builtin_nan("");
@@ -95,7 +95,7 @@ __device__ __forceinline__ void ring_fill_g(const RingG& ring, uint32_t lane, ui
         uint32_t qi, j;
         slot_split(sg, slot, qi, j);
         if (slot_pixel(sg, qi, lx, ly)) {
-            Ray<double> r;
+            Ray r;
             uint64_t rng;
             cam_ray(sg, sc, j, lx, ly, r, rng);
             v[0] = r.o.x; v[1] = r.o.y; v[2] = r.o.z; v[3] = r.d.x;
@@ -106,9 +106,8 @@ __device__ __forceinline__ void ring_fill_g(const RingG& ring, uint32_t lane, ui
     for (uint32_t f = 0; f < 8; ++f) ring.at(f, lane) = v[f];
 }
 template <uint32_t F, uint32_t TF, int LM>
-__global__ __launch_bounds__(LM ? kBlockM : kBlock, LM ? 1 : ART_PATHS_G_WAVES) void k_paths_g(DevScene<double> S0, PassGeom g, CameraRec<double> cam,
-                                                                                     Work<double> w, uint32_t* next_slot) {
-    using R = double;
+__global__ __launch_bounds__(LM ? kBlockM : kBlock, LM ? 1 : ART_PATHS_G_WAVES) void k_paths_g(DevScene S0, PassGeom g, CameraRec cam, Work w,
+                                                                                     uint32_t* next_slot) {
     // explicit-LDS node reads (traverse's PL path): LM 2 for its LDS part; LM 1 for every node (the XOR near/far
     // addressing needs the explicit LDS addresses; through the LDS-inferred pointer it costs more adds)
     constexpr int kLdsNodesPL = LM == 2 ? 1 : LM == 1 ? 2 : 0;
@@ -120,8 +119,8 @@ __global__ __launch_bounds__(LM ? kBlockM : kBlock, LM ? 1 : ART_PATHS_G_WAVES) 
     constexpr bool S16 = (F & F_CODE16) != 0;
     using ST = StackF<false, F>;
     ST* stk = reinterpret_cast<ST*>(smem) + B + stack_column<S16>(threadIdx.x);
-    CameraRec<double>& s_cam = *reinterpret_cast<CameraRec<double>*>(smem + paths_g_stack_bytes(g.stack, B, S16));
-    PassGeom& s_g = *reinterpret_cast<PassGeom*>(smem + paths_g_stack_bytes(g.stack, B, S16) + sizeof(CameraRec<double>));
+    CameraRec& s_cam = *reinterpret_cast<CameraRec*>(smem + paths_g_stack_bytes(g.stack, B, S16));
+    PassGeom& s_g = *reinterpret_cast<PassGeom*>(smem + paths_g_stack_bytes(g.stack, B, S16) + sizeof(CameraRec));
     stk[-B] = static_cast<ST>(kNodeEmpty);
     if (threadIdx.x == 0) {
         s_cam = cam;
@@ -132,9 +131,9 @@ __global__ __launch_bounds__(LM ? kBlockM : kBlock, LM ? 1 : ART_PATHS_G_WAVES) 
             s_g.P = n * g.k;
         }
     }
-    [[maybe_unused]] JumpEntry* jt = reinterpret_cast<JumpEntry*>(smem + align16(paths_g_stack_bytes(g.stack, B, S16) + sizeof(CameraRec<double>) + sizeof(PassGeom)));
+    [[maybe_unused]] JumpEntry* jt = reinterpret_cast<JumpEntry*>(smem + align16(paths_g_stack_bytes(g.stack, B, S16) + sizeof(CameraRec) + sizeof(PassGeom)));
     if (threadIdx.x < static_cast<uint32_t>(kJumpEntries)) jt[threadIdx.x] = pcg_jump(3u * threadIdx.x);
-    DevScene<double> S = S0;
+    DevScene S = S0;
     [[maybe_unused]] double* uvc = reinterpret_cast<double*>(jt + kJumpEntries);  // sphere u, v constants, LDS copy
     if constexpr ((TF & TF_IMAGE) != 0)
         if (threadIdx.x < static_cast<uint32_t>(kUvConsts)) uvc[threadIdx.x] = uv_table(S0)[threadIdx.x];
@@ -144,20 +143,20 @@ __global__ __launch_bounds__(LM ? kBlockM : kBlock, LM ? 1 : ART_PATHS_G_WAVES) 
         for (int32_t i = static_cast<int32_t>(threadIdx.x); i < S0.nworld; i += B) reinterpret_cast<int32_t*>(wb)[i] = S0.world[i];
         uint8_t* ob = wb + align16(sizeof(int32_t) * static_cast<uint32_t>(S0.nworld));
         const uint4* os = reinterpret_cast<const uint4*>(S0.objs);
-        for (uint32_t i = threadIdx.x; i < S0.n_objs * (sizeof(ObjRec<double>) / 16); i += B) reinterpret_cast<uint4*>(ob)[i] = os[i];
-        uint8_t* pb = ob + sizeof(ObjRec<double>) * S0.n_objs;
+        for (uint32_t i = threadIdx.x; i < S0.n_objs * (sizeof(ObjRec) / 16); i += B) reinterpret_cast<uint4*>(ob)[i] = os[i];
+        uint8_t* pb = ob + sizeof(ObjRec) * S0.n_objs;
         const uint4* ps = reinterpret_cast<const uint4*>(S0.obj_prims);
         for (uint32_t i = threadIdx.x; i < S0.n_objs * (sizeof(PrimRec80) / 16); i += B) reinterpret_cast<uint4*>(pb)[i] = ps[i];
         S.world = reinterpret_cast<const int32_t*>(wb);
-        S.objs = reinterpret_cast<const ObjRec<double>*>(ob);
+        S.objs = reinterpret_cast<const ObjRec*>(ob);
         S.obj_prims = reinterpret_cast<const PrimRec80*>(pb);
         const uint32_t nm = lds_mats<TF>(S0.n_mats);
         if (nm) {
             uint8_t* mb = pb + sizeof(PrimRec80) * S0.n_objs;
             const uint2* ms = reinterpret_cast<const uint2*>(S0.mats);
-            static_assert(sizeof(MatRec<double>) % 8 == 0, "material records copied in 8-B pieces");
-            for (uint32_t i = threadIdx.x; i < nm * (sizeof(MatRec<double>) / 8); i += B) reinterpret_cast<uint2*>(mb)[i] = ms[i];
-            S.mats = reinterpret_cast<const MatRec<double>*>(mb);
+            static_assert(sizeof(MatRec) % 8 == 0, "material records copied in 8-B pieces");
+            for (uint32_t i = threadIdx.x; i < nm * (sizeof(MatRec) / 8); i += B) reinterpret_cast<uint2*>(mb)[i] = ms[i];
+            S.mats = reinterpret_cast<const MatRec*>(mb);
         }
         lm_off += paths_g_world_bytes(S0.nworld, S0.n_objs, nm);
     }
@@ -189,7 +188,7 @@ __global__ __launch_bounds__(LM ? kBlockM : kBlock, LM ? 1 : ART_PATHS_G_WAVES) 
         S.primrefs = reinterpret_cast<const uint32_t*>(m + nb);
         if constexpr ((F & F_TRI) != 0) {
             copy(m + nb + pb, S0.leaf_tris112, tb);
-            S.leaf_tris112 = reinterpret_cast<const TriRec112<double>*>(m + nb + pb);
+            S.leaf_tris112 = reinterpret_cast<const TriRec112*>(m + nb + pb);
         }
         lm_off = align16(lm_off + nb + pb + tb);  // the camera-ray rings follow (kRing)
     }
@@ -206,19 +205,19 @@ __global__ __launch_bounds__(LM ? kBlockM : kBlock, LM ? 1 : ART_PATHS_G_WAVES) 
     __syncthreads();
     const uint32_t lane = __lane_id();
     const uint64_t below = (1ull << lane) - 1ull;
-    const V3<R> bg = mk(S.bg[0], S.bg[1], S.bg[2]);
+    const V3 bg = mk(S.bg[0], S.bg[1], S.bg[2]);
     uint32_t cur = 0, end = 0;  // this wave's claimed slots [cur, end): wave-uniform
     bool busy = false, drained = false;
     uint32_t q = 0;
     int depth = 0;
-    PathState<R> st;
+    PathState st;
     unsigned long long segs = 0;
     // suspendable BVH traversals (ART_SUSPEND_LANES) where node fetches go to L2 (LM 0, 2); with the whole BVH in LDS
     // (LM 1) a traversal is short and suspending only adds rounds
     // (LM 1, the BVH in LDS: thresholds 4-40 measured -5 % to -22 % on dino and the final scene)
     constexpr int kSuspLanes = LM == 1 ? 0 : ART_SUSPEND_LANES;
     constexpr bool SUSP = kSuspLanes > 0;
-    TraceState<R> ts;  // the lane's segment trace, possibly suspended in a BVH
+    TraceState ts;  // the lane's segment trace, possibly suspended in a BVH
     bool in_trace = false;
 #ifdef ART_TRACE
     bool tracing = false;
@@ -323,10 +322,10 @@ __global__ __launch_bounds__(LM ? kBlockM : kBlock, LM ? 1 : ART_PATHS_G_WAVES) 
             continue;
         }
         const bool allow = SUSP && __ballot(drained) == 0;  // suspend only while there are paths to start
-        R t;
+        double t;
         HitOut h{0, 0, kMatUnknown};
         bool hitw = false, susp = false;
-        Surf<R> s;
+        Surf s;
         [[maybe_unused]] uint32_t mtype = MAT_LIGHT;
         if (busy) {
             const bool fresh = !in_trace;
@@ -343,17 +342,17 @@ __global__ __launch_bounds__(LM ? kBlockM : kBlock, LM ? 1 : ART_PATHS_G_WAVES) 
             if constexpr (SUSP) {
                 ts.tr.allow = allow;
                 ts.tr.lanes = kSuspLanes;
-                in_trace = !trace_world_res<R, F, B, kLdsNodesPL>(S, st.ray, stk, st.rng, ts);
+                in_trace = !trace_world_res<F, B, kLdsNodesPL>(S, st.ray, stk, st.rng, ts);
                 hitw = ts.any;
                 t = ts.closest;
                 h = ts.h;
             } else {
-                hitw = trace_world<R, F, B, false, kLdsNodesPL>(S, nullptr, st.ray, stk, st.rng, t, h);
+                hitw = trace_world<F, B, false, kLdsNodesPL>(S, nullptr, st.ray, stk, st.rng, t, h);
             }
             susp = in_trace;  // suspended: nothing to shade this round
             ART_TICK(tm_trace);
             if (!susp && hitw) {
-                world_surface<R, F, (TF & TF_IMAGE) != 0, (TF & (TF_IMAGE | TF_BARY)) != 0>(S, h, st.ray, t, s, uvc);
+                world_surface<F, (TF & TF_IMAGE) != 0, (TF & (TF_IMAGE | TF_BARY)) != 0>(S, h, st.ray, t, s, uvc);
                 mtype = S.mats[s.mat].type;
             }
         }
@@ -362,8 +361,8 @@ __global__ __launch_bounds__(LM ? kBlockM : kBlock, LM ? 1 : ART_PATHS_G_WAVES) 
         // :129: each scatters with it first; metal's unit_vector draws nothing), as k_paths does
         const bool need = busy && !susp && hitw && (mtype == MAT_LAMBERTIAN || mtype == MAT_METAL || mtype == MAT_ISOTROPIC) &&
                           depth + 1 < max_depth;
-        const V3<R> ps = coop_unit_sphere<R>(need, st.rng, jt);
-        const V3<R>* pre = &ps;
+        const V3 ps = coop_unit_sphere(need, st.rng, jt);
+        const V3* pre = &ps;
         ART_TICK(tm_coop);
         if (busy) {
             bool cont = false;
@@ -375,34 +374,34 @@ __global__ __launch_bounds__(LM ? kBlockM : kBlock, LM ? 1 : ART_PATHS_G_WAVES) 
                            ART_DBITS(s.p.x), ART_DBITS(s.p.y), ART_DBITS(s.p.z), ART_DBITS(s.n.x), ART_DBITS(s.n.y), ART_DBITS(s.n.z), s.ff ? 1 : 0,
                            static_cast<int>(s.mat), h.prim, h.obj);
 #endif
-                const MatRec<R>& mat = S.mats[s.mat];
+                const MatRec& mat = S.mats[s.mat];
                 // In kernels with noise or image textures (where a texture value is costly): the
                 // steps several materials take, once for the wave instead of once per material branch present -- the
                 // texture value (diffuse_light, lambertian, isotropic: no draws) and one unit_vector (of the sphere
                 // draw for lambertian, of the ray direction for metal and dielectric).  Measured +1.3 % on the
                 // Next-Week final; with solid / checker textures only (cow, dino) the longer live ranges cost 1.5-2 %.
                 constexpr bool kShared = (TF & (TF_NOISE | TF_IMAGE)) != 0;
-                V3<R> texc = mk(R(0), R(0), R(0)), uv = mk(R(0), R(0), R(0));
+                V3 texc = mk(0.0, 0.0, 0.0), uv = mk(0.0, 0.0, 0.0);
                 if constexpr (kShared) {
                     const bool scat = depth + 1 < max_depth;
                     if (mat.type == MAT_LIGHT || (scat && (mat.type == MAT_LAMBERTIAN || mat.type == MAT_ISOTROPIC)))
-                        texc = mat_tex_value<R, TF>(S, mat, s.u, s.v, s.p);
+                        texc = mat_tex_value<TF>(S, mat, s.u, s.v, s.p);
                     if (scat && (mat.type == MAT_LAMBERTIAN || mat.type == MAT_METAL || mat.type == MAT_DIELECTRIC))
                         uv = unit(mat.type == MAT_LAMBERTIAN ? *pre : st.ray.d);
                 }
-                const V3<R>* texp = kShared ? &texc : nullptr;
-                const V3<R>* uvp = kShared ? &uv : nullptr;
+                const V3* texp = kShared ? &texc : nullptr;
+                const V3* uvp = kShared ? &uv : nullptr;
                 ART_TICK(tm_tex);
                 if (mat.type == MAT_LIGHT) {  // material.h:114-116; diffuse_light never scatters
-                    st.L = st.L + st.T * (texp ? *texp : mat_tex_value<R, TF>(S, mat, s.u, s.v, s.p));
+                    st.L = st.L + st.T * (texp ? *texp : mat_tex_value<TF>(S, mat, s.u, s.v, s.p));
                 } else if (depth + 1 < max_depth) {
-                    V3<R> att, dir;
+                    V3 att, dir;
                     bool sc = false;
                     switch (mat.type) {
-                        case MAT_LAMBERTIAN: sc = scatter<R, MAT_LAMBERTIAN, TF>(S, mat, s, st, att, dir, pre, uvp, texp); break;
-                        case MAT_METAL: sc = scatter<R, MAT_METAL, TF>(S, mat, s, st, att, dir, pre, uvp); break;
-                        case MAT_DIELECTRIC: sc = scatter<R, MAT_DIELECTRIC, TF>(S, mat, s, st, att, dir, nullptr, uvp); break;
-                        case MAT_ISOTROPIC: sc = scatter<R, MAT_ISOTROPIC, TF>(S, mat, s, st, att, dir, pre, nullptr, texp); break;
+                        case MAT_LAMBERTIAN: sc = scatter<MAT_LAMBERTIAN, TF>(S, mat, s, st, att, dir, pre, uvp, texp); break;
+                        case MAT_METAL: sc = scatter<MAT_METAL, TF>(S, mat, s, st, att, dir, pre, uvp); break;
+                        case MAT_DIELECTRIC: sc = scatter<MAT_DIELECTRIC, TF>(S, mat, s, st, att, dir, nullptr, uvp); break;
+                        case MAT_ISOTROPIC: sc = scatter<MAT_ISOTROPIC, TF>(S, mat, s, st, att, dir, pre, nullptr, texp); break;
                         default: break;
                     }
                     if (sc) {
@@ -451,7 +450,7 @@ __global__ __launch_bounds__(LM ? kBlockM : kBlock, LM ? 1 : ART_PATHS_G_WAVES) 
 // the default scheduler; dino's LM 1 kernel loses 0.9 % under it and the Next-Week final's 4.6 % (its spills double), so
 // they stay in kernels.hip's object (r3z2)
 constexpr uint32_t kMeshG = kFeatMesh | F_CODE16;
-extern template __global__ void k_paths_g<kMeshG, kTexBasic, 0>(DevScene<double>, PassGeom, CameraRec<double>, Work<double>, uint32_t*);
-extern template __global__ void k_paths_g<kMeshG, kTexBasic, 2>(DevScene<double>, PassGeom, CameraRec<double>, Work<double>, uint32_t*);
+extern template __global__ void k_paths_g<kMeshG, kTexBasic, 0>(DevScene, PassGeom, CameraRec, Work, uint32_t*);
+extern template __global__ void k_paths_g<kMeshG, kTexBasic, 2>(DevScene, PassGeom, CameraRec, Work, uint32_t*);
 
 }  // namespace art

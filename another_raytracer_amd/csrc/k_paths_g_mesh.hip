@@ -3,6 +3,6 @@
 #include "k_paths_g.h"
 
 namespace art {
-template __global__ void k_paths_g<kMeshG, kTexBasic, 0>(DevScene<double>, PassGeom, CameraRec<double>, Work<double>, uint32_t*);
-template __global__ void k_paths_g<kMeshG, kTexBasic, 2>(DevScene<double>, PassGeom, CameraRec<double>, Work<double>, uint32_t*);
+template __global__ void k_paths_g<kMeshG, kTexBasic, 0>(DevScene, PassGeom, CameraRec, Work, uint32_t*);
+template __global__ void k_paths_g<kMeshG, kTexBasic, 2>(DevScene, PassGeom, CameraRec, Work, uint32_t*);
 }  // namespace art

@@ -4,12 +4,12 @@
 // flattened into an iterative per-ray wavefront loop over a pool of P = k * npix paths (k samples of every local
 // pixel per pass).  Per pass:
 //   for depth d < max_depth:
-//     k_extend<R, F>           closest hit over the world list (LDS-stack BVH traversal, f32 boxes, R leaf tests);
+//     k_extend<F>              closest hit over the world list (LDS-stack BVH traversal, f32 boxes, f64 leaf tests);
 //                              at depth 0 it first generates the camera ray of every (pixel, sample) slot itself
 //                              (PCG32 keyed by (seed, pixel, sample)); F = the scene's feature subset (layout.h),
 //                              misses finish their path (L += T*background); hits are appended to one of five
 //                              material queues (branch sorting for the shade stage)
-//     k_shade<R, F, M, TF>     one launch per material type M present: emitted + scatter on that material's queue
+//     k_shade<F, M, TF>        one launch per material type M present: emitted + scatter on that material's queue
 //                              (branch-sorted shading); survivors go to the next active queue
 //   k_accum                    adds the k per-slot radiances into the f64 pixel sums in sample order
 // then k_finalize (write_color, color.h:6-22).  All queue sizes live on the device: extend/shade are persistent
@@ -22,6 +22,7 @@
 #include <map>
 #include <mutex>
 #include <tuple>
+#include <type_traits>
 
 #include "art.h"
 #include "k_paths_g.h"
@@ -37,9 +38,8 @@ namespace art {
 // FUSE (L scenes with solid/checker textures, no media): every hit is shaded in place (shade_hit) and goes straight to
 // the next depth's active queue -- no hit record, no material queues, no k_shade launches, one path-record round trip
 // per bounce.
-template <class R, uint32_t F, bool L, bool FUSE>
-__global__ __launch_bounds__(L ? kBlockL : kBlock, L ? 1 : ART_EXTEND_MIN_WAVES) void k_extend(DevScene<R> S, PassGeom g, CameraRec<R> cam,
-                                                                                                 Work<R> w, int d) {
+template <uint32_t F, bool L, bool FUSE>
+__global__ __launch_bounds__(L ? kBlockL : kBlock, L ? 1 : ART_EXTEND_MIN_WAVES) void k_extend(DevScene S, PassGeom g, CameraRec cam, Work w, int d) {
     constexpr int B = L ? kBlockL : kBlock;
     // dynamic LDS: [scene image (L only)][traversal stack: g.stack entries x B lanes] (sized per scene at launch)
     // dynamic LDS only, so the scene image starts at LDS address 0 (device.h lds_f4)
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(L ? kBlockL : kBlock, L ? 1 : ART_EXTEND_MIN_WAVES)
         bool cont = false;  // FUSE: the path continues at depth d + 1
         uint32_t q = 0;
         bool live = i < count;
-        PathState<R> st;
+        PathState st;
         if (live) {
             if (d == 0) {
                 q = i;
@@ -97,12 +97,12 @@ __global__ __launch_bounds__(L ? kBlockL : kBlock, L ? 1 : ART_EXTEND_MIN_WAVES)
         }
         ART_TICK(tm_load);
         if (FUSE) {
-            R t;
+            double t;
             HitOut h{0, 0, kMatUnknown};
-            const bool hitf = live && trace_world<R, F, B, L>(S, lds, st.ray, stk, st.rng, t, h);
+            const bool hitf = live && trace_world<F, B, L>(S, lds, st.ray, stk, st.rng, t, h);
             ART_TICK(tm_trace);
             if (hitf) {
-                if constexpr (std::is_same<R, double>::value) cont = shade_hit_lds(lds, h.obj >> 16, h.mt, t, d + 1 >= g.max_depth, st);
+                cont = shade_hit_lds(lds, h.obj >> 16, h.mt, t, d + 1 >= g.max_depth, st);
                 if (cont) store_path(w.paths, q, st);
                 else store_res(w.res, q, st.L);
             } else if (live) {  // engine.h:455-456: miss -> background
@@ -111,10 +111,10 @@ __global__ __launch_bounds__(L ? kBlockL : kBlock, L ? 1 : ART_EXTEND_MIN_WAVES)
             }
             ART_TICK(tm_shade);
         } else if (live) {
-            R t;
+            double t;
             HitOut h{0, 0, kMatUnknown};
-            if (trace_world<R, F, B, L>(S, lds, st.ray, stk, st.rng, t, h)) {
-                w.hits[q] = HitRecD<R>{t, h.prim, h.obj};
+            if (trace_world<F, B, L>(S, lds, st.ray, stk, st.rng, t, h)) {
+                w.hits[q] = HitRecD{t, h.prim, h.obj};
                 if (L && h.mt != kMatUnknown) {
                     mtype = static_cast<int>(h.mt);  // from the LDS image: no dependent global loads
                 } else {
@@ -157,8 +157,8 @@ __global__ __launch_bounds__(L ? kBlockL : kBlock, L ? 1 : ART_EXTEND_MIN_WAVES)
 }
 
 // Input: the kShards shards of material queue M at depth d (the extend stage sorted hits by material type).
-template <class R, uint32_t F, uint32_t M, uint32_t TF>
-__global__ __launch_bounds__(kBlock) void k_shade(DevScene<R> S, PassGeom g, Work<R> w, int d) {
+template <uint32_t F, uint32_t M, uint32_t TF>
+__global__ __launch_bounds__(kBlock) void k_shade(DevScene S, PassGeom g, Work w, int d) {
     __shared__ uint32_t pre[kShards + 1];
     block_prefix(pre, kShards, threadIdx.x < kShards ? *counter(w, d, 1 + static_cast<int>(M), threadIdx.x) : 0u);
     const uint32_t total = pre[kShards];
@@ -175,16 +175,16 @@ __global__ __launch_bounds__(kBlock) void k_shade(DevScene<R> S, PassGeom g, Wor
         if (i < total) {
             const int sg = find_segment(pre, kShards, i);
             q = in[static_cast<size_t>(sg) * g.cap + (i - pre[sg])];
-            PathState<R> st;
+            PathState st;
             load_path(w.paths, q, st, true);
-            const HitRecD<R> h = w.hits[q];
-            Surf<R> s;
-            world_surface<R, F, (TF & TF_IMAGE) != 0>(S, HitOut{h.prim, h.obj, kMatUnknown}, st.ray, h.t, s, uv_table(S));
-            const MatRec<R>& mat = S.mats[s.mat];
-            if (M == MAT_LIGHT) st.L = st.L + st.T * mat_tex_value<R, TF>(S, mat, s.u, s.v, s.p);  // material.h:114-116
+            const HitRecD h = w.hits[q];
+            Surf s;
+            world_surface<F, (TF & TF_IMAGE) != 0>(S, HitOut{h.prim, h.obj, kMatUnknown}, st.ray, h.t, s, uv_table(S));
+            const MatRec& mat = S.mats[s.mat];
+            if (M == MAT_LIGHT) st.L = st.L + st.T * mat_tex_value<TF>(S, mat, s.u, s.v, s.p);  // material.h:114-116
             if (M != MAT_LIGHT && !last) {
-                V3<R> att, dir;
-                if (scatter<R, M, TF>(S, mat, s, st, att, dir)) {
+                V3 att, dir;
+                if (scatter<M, TF>(S, mat, s, st, att, dir)) {
                     st.T = st.T * att;
                     st.ray.o = s.p;
                     st.ray.d = dir;
@@ -198,8 +198,7 @@ __global__ __launch_bounds__(kBlock) void k_shade(DevScene<R> S, PassGeom g, Wor
     }
 }
 
-template <class R>
-__global__ __launch_bounds__(256) void k_accum(PassGeom g, Work<R> w) {
+__global__ __launch_bounds__(256) void k_accum(PassGeom g, Work w) {
     const uint32_t qi = blockIdx.x * blockDim.x + threadIdx.x;
     if (qi >= g.npix_pad) return;
     int lx, ly;
@@ -223,8 +222,7 @@ __global__ __launch_bounds__(256) void k_accum(PassGeom g, Work<R> w) {
 // Its samples are summed in order into the quarter sum q (f64, as the reference's pixel_color); when the quarter's
 // last sample is in, write_color_raw<float> rounds q to float and the running image sum takes it:
 // acc = ((c1 + c2) + c3) + c4 in double, the reference's `pixel_color1 + ... + pixel_color4`.  q persists across passes.
-template <class R>
-__global__ __launch_bounds__(256) void k_accum_images(PassGeom g, Work<R> w, double* qsum, uint32_t m) {
+__global__ __launch_bounds__(256) void k_accum_images(PassGeom g, Work w, double* qsum, uint32_t m) {
     const uint32_t qi = blockIdx.x * blockDim.x + threadIdx.x;
     if (qi >= g.npix_pad) return;
     int lx, ly;
@@ -259,9 +257,8 @@ __global__ __launch_bounds__(256) void k_accum_images(PassGeom g, Work<R> w, dou
 // (hit_record::set_face_normal), so traversal edge cases (axis-parallel rays, origins on faces) can be checked one ray
 // at a time against the oracle.  Ray i's medium draws come from the PCG stream pcg_seed(0, i, 0).
 template <uint32_t F, bool L>
-__global__ __launch_bounds__(L ? kBlockL : kBlock) void k_trace_rays(DevScene<double> S, const double* rays, uint32_t n, uint32_t stack_rows,
+__global__ __launch_bounds__(L ? kBlockL : kBlock) void k_trace_rays(DevScene S, const double* rays, uint32_t n, uint32_t stack_rows,
                                                                        double* t_out, double* n_out) {
-    using R = double;
     constexpr int B = L ? kBlockL : kBlock;
     extern __shared__ __align__(16) uint8_t smem[];
     StackT<L>* stk = reinterpret_cast<StackT<L>*>(smem + (L ? kLdsImageBytes : 0u)) + B + stack_column<L>(threadIdx.x);
@@ -274,16 +271,16 @@ __global__ __launch_bounds__(L ? kBlockL : kBlock) void k_trace_rays(DevScene<do
     const uint32_t i = blockIdx.x * B + threadIdx.x;
     if (i >= n) return;
     const double* q = rays + 7 * static_cast<size_t>(i);
-    Ray<R> r;
+    Ray r;
     r.o = mk(q[0], q[1], q[2]);
     r.d = mk(q[3], q[4], q[5]);
     r.tm = q[6];
     uint64_t rng = pcg_seed(0, i, 0);
-    R t = R(0);
+    double t = 0.0;
     HitOut h{0, 0, kMatUnknown};
-    if (trace_world<R, F, B, L>(S, L ? smem : nullptr, r, stk, rng, t, h)) {
-        Surf<R> s;
-        world_surface<R, F, false>(S, h, r, t, s);
+    if (trace_world<F, B, L>(S, L ? smem : nullptr, r, stk, rng, t, h)) {
+        Surf s;
+        world_surface<F, false>(S, h, r, t, s);
         t_out[i] = t;
         n_out[3 * i] = s.n.x;
         n_out[3 * i + 1] = s.n.y;
@@ -302,9 +299,8 @@ __global__ __launch_bounds__(L ? kBlockL : kBlock) void k_trace_rays(DevScene<do
 // a medium scattering event; mat: the material index.  A miss: t = point = +inf, prim = mat = -1, everything else 0.
 // With t_max null and no_media 0 the traversal is k_trace_rays' own: the same t and normal.
 template <uint32_t F, bool L>
-__global__ __launch_bounds__(L ? kBlockL : kBlock) void k_query_rays(DevScene<double> S, const double* rays, const double* t_max, uint32_t n,
+__global__ __launch_bounds__(L ? kBlockL : kBlock) void k_query_rays(DevScene S, const double* rays, const double* t_max, uint32_t n,
                                                                        uint32_t no_media, double* hits) {
-    using R = double;
     constexpr int B = L ? kBlockL : kBlock;
     extern __shared__ __align__(16) uint8_t smem[];
     StackT<L>* stk = reinterpret_cast<StackT<L>*>(smem + (L ? kLdsImageBytes : 0u)) + B + stack_column<L>(threadIdx.x);
@@ -316,19 +312,19 @@ __global__ __launch_bounds__(L ? kBlockL : kBlock) void k_query_rays(DevScene<do
     const uint32_t i = blockIdx.x * B + threadIdx.x;
     if (i >= n) return;
     const double* q = rays + 7 * static_cast<size_t>(i);
-    Ray<R> r;
+    Ray r;
     r.o = mk(q[0], q[1], q[2]);
     r.d = mk(q[3], q[4], q[5]);
     r.tm = q[6];
-    const R inf = __builtin_inf();
-    const R tm = t_max ? t_max[i] : inf;
+    const double inf = __builtin_inf();
+    const double tm = t_max ? t_max[i] : inf;
     uint64_t rng = pcg_seed(0, i, 0);
-    R t = R(0);
+    double t = 0.0;
     HitOut h{0, 0, kMatUnknown};
     double* o = hits + 12 * static_cast<size_t>(i);
-    if (trace_world<R, F, B, L>(S, L ? smem : nullptr, r, stk, rng, t, h, tm, no_media != 0)) {
-        Surf<R> s;
-        world_surface<R, F, true, true, true>(S, h, r, t, s, uv_table(S));
+    if (trace_world<F, B, L>(S, L ? smem : nullptr, r, stk, rng, t, h, tm, no_media != 0)) {
+        Surf s;
+        world_surface<F, true, true, true>(S, h, r, t, s, uv_table(S));
         o[0] = t;
         o[1] = s.n.x; o[2] = s.n.y; o[3] = s.n.z;
         o[4] = s.p.x; o[5] = s.p.y; o[6] = s.p.z;
@@ -350,9 +346,8 @@ __global__ __launch_bounds__(L ? kBlockL : kBlock) void k_query_rays(DevScene<do
 // carries no media bits; no RNG.  ANY: traverse's child order (1 sorted, 2 node order: option query.any_sorted; the node
 // order is the default, DESIGN.md 4.7 measured both).
 template <uint32_t F, bool L, int ANY>
-__global__ __launch_bounds__(L ? kBlockL : kBlock) void k_occlude_rays(DevScene<double> S, const double* rays, const double* t_max, uint32_t n,
+__global__ __launch_bounds__(L ? kBlockL : kBlock) void k_occlude_rays(DevScene S, const double* rays, const double* t_max, uint32_t n,
                                                                          uint8_t* occluded) {
-    using R = double;
     constexpr int B = L ? kBlockL : kBlock;
     extern __shared__ __align__(16) uint8_t smem[];
     StackT<L>* stk = reinterpret_cast<StackT<L>*>(smem + (L ? kLdsImageBytes : 0u)) + B + stack_column<L>(threadIdx.x);
@@ -364,12 +359,12 @@ __global__ __launch_bounds__(L ? kBlockL : kBlock) void k_occlude_rays(DevScene<
     const uint32_t i = blockIdx.x * B + threadIdx.x;
     if (i >= n) return;
     const double* q = rays + 7 * static_cast<size_t>(i);
-    Ray<R> r;
+    Ray r;
     r.o = mk(q[0], q[1], q[2]);
     r.d = mk(q[3], q[4], q[5]);
     r.tm = q[6];
-    const R tm = t_max ? t_max[i] : R(__builtin_inf());
-    occluded[i] = occlude_world<R, F, B, L, ANY>(S, L ? smem : nullptr, r, stk, tm) ? 1 : 0;
+    const double tm = t_max ? t_max[i] : __builtin_inf();
+    occluded[i] = occlude_world<F, B, L, ANY>(S, L ? smem : nullptr, r, stk, tm) ? 1 : 0;
 }
 
 // First-hit guide buffers (rt_render_guides): one ray per local pixel through the pixel centre -- no render RNG draw,
@@ -378,8 +373,7 @@ __global__ __launch_bounds__(L ? kBlockL : kBlock) void k_occlude_rays(DevScene<
 // mat_tex_value for lambertian / isotropic, MatRec::albedo for metal, 1 for dielectric, diffuse_light and a miss.
 // Record per local pixel (RT_GUIDE_DOUBLES = 10): albedo[3], normal[3], position[3], t; a miss has t = position = +inf.
 template <uint32_t F, bool L, uint32_t TF>
-__global__ __launch_bounds__(L ? kBlockL : kBlock) void k_guides(DevScene<double> S, GuideGeom g, CameraRec<double> cam, double* guides, double* rays_out) {
-    using R = double;
+__global__ __launch_bounds__(L ? kBlockL : kBlock) void k_guides(DevScene S, GuideGeom g, CameraRec cam, double* guides, double* rays_out) {
     constexpr int B = L ? kBlockL : kBlock;
     extern __shared__ __align__(16) uint8_t smem[];
     StackT<L>* stk = reinterpret_cast<StackT<L>*>(smem + (L ? kLdsImageBytes : 0u)) + B + stack_column<L>(threadIdx.x);
@@ -393,9 +387,9 @@ __global__ __launch_bounds__(L ? kBlockL : kBlock) void k_guides(DevScene<double
     const int ly = static_cast<int>(lp / static_cast<uint32_t>(g.W));
     const int lx = static_cast<int>(lp - static_cast<uint32_t>(ly) * static_cast<uint32_t>(g.W));
     const int gy = band_global_row(ly, g.band_rows, g.band_count, g.band_index);
-    const R s = (R(lx) + R(0.5)) / R(g.W - 1);
-    const R t_img = (R(g.H - 1 - gy) + R(0.5)) / R(g.H - 1);
-    Ray<R> r;
+    const double s = (static_cast<double>(lx) + 0.5) / static_cast<double>(g.W - 1);
+    const double t_img = (static_cast<double>(g.H - 1 - gy) + 0.5) / static_cast<double>(g.H - 1);
+    Ray r;
     r.o = ld3(cam.origin);
     r.d = ld3(cam.llc) + s * ld3(cam.horizontal) + t_img * ld3(cam.vertical) - ld3(cam.origin);
     r.tm = cam.time0;
@@ -406,16 +400,16 @@ __global__ __launch_bounds__(L ? kBlockL : kBlock) void k_guides(DevScene<double
         q[6] = r.tm;
     }
     uint64_t rng = pcg_seed(0, static_cast<uint32_t>(gy) * static_cast<uint32_t>(g.W) + static_cast<uint32_t>(lx), 0);
-    R t = R(0);
+    double t = 0.0;
     HitOut h{0, 0, kMatUnknown};
-    const R inf = __builtin_inf();
-    V3<R> alb = mk(R(1), R(1), R(1)), nrm = mk(R(0), R(0), R(0)), pos = mk(inf, inf, inf);
-    R t_hit = inf;
-    if (trace_world<R, F, B, L>(S, L ? smem : nullptr, r, stk, rng, t, h)) {
-        Surf<R> sf;
-        world_surface<R, F, (TF & TF_IMAGE) != 0, (TF & (TF_IMAGE | TF_BARY)) != 0>(S, h, r, t, sf, uv_table(S));
-        const MatRec<R>& m = S.mats[sf.mat];
-        if (m.type == MAT_LAMBERTIAN || m.type == MAT_ISOTROPIC) alb = mat_tex_value<R, TF>(S, m, sf.u, sf.v, sf.p);
+    const double inf = __builtin_inf();
+    V3 alb = mk(1.0, 1.0, 1.0), nrm = mk(0.0, 0.0, 0.0), pos = mk(inf, inf, inf);
+    double t_hit = inf;
+    if (trace_world<F, B, L>(S, L ? smem : nullptr, r, stk, rng, t, h)) {
+        Surf sf;
+        world_surface<F, (TF & TF_IMAGE) != 0, (TF & (TF_IMAGE | TF_BARY)) != 0>(S, h, r, t, sf, uv_table(S));
+        const MatRec& m = S.mats[sf.mat];
+        if (m.type == MAT_LAMBERTIAN || m.type == MAT_ISOTROPIC) alb = mat_tex_value<TF>(S, m, sf.u, sf.v, sf.p);
         else if (m.type == MAT_METAL) alb = ld3(m.albedo);
         nrm = sf.n;
         pos = sf.p;
@@ -471,7 +465,7 @@ __global__ void k_adapt_store(const uint32_t* list, uint32_t n, const double* ac
 // entry, 100 records each, left every level's accumulation latency-bound at ~62 us whatever its size (rocprofv3
 // kernel trace of the default run; 45 us with 20 loads in flight per thread).
 constexpr int kAdaptAccumWaves = 4;
-__global__ __launch_bounds__(64 * kAdaptAccumWaves) void k_adapt_accum(const uint32_t* list, const ResRec<double>* res, uint32_t k, int spp,
+__global__ __launch_bounds__(64 * kAdaptAccumWaves) void k_adapt_accum(const uint32_t* list, const ResRec* res, uint32_t k, int spp,
                                                                       int32_t* work) {
     __shared__ double buf[kAdaptAccumWaves][3 * 64];
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
@@ -479,7 +473,7 @@ __global__ __launch_bounds__(64 * kAdaptAccumWaves) void k_adapt_accum(const uin
     if (e >= list[-1]) return;  // wave-uniform
     double* b = buf[wv];
     double acc = 0.0;  // lane c < 3: channel c
-    const ResRec<double>* r = res + static_cast<size_t>(e) * k;
+    const ResRec* r = res + static_cast<size_t>(e) * k;
     for (uint32_t j0 = 0; j0 < k; j0 += 64) {
         const uint32_t n = min(64u, k - j0);
         if (lane < n) {
@@ -641,56 +635,56 @@ int blocks_per_cu(const void* kernel, int block, size_t lds) {
     cache.emplace(key, per_cu);
     return per_cu;
 }
-template <class R, uint32_t F, uint32_t M, uint32_t TF>
+template <uint32_t F, uint32_t M, uint32_t TF>
 static int shade_blocks(int num_cu) {
-    return blocks_per_cu(reinterpret_cast<const void*>(k_shade<R, F, M, TF>), kBlock, 0) * num_cu;
+    return blocks_per_cu(reinterpret_cast<const void*>(k_shade<F, M, TF>), kBlock, 0) * num_cu;
 }
 // Textured materials get the "solid + checker" instantiation unless the scene holds noise or image textures.
-template <class R, uint32_t F, uint32_t M>
-static void launch_shade(uint32_t mat_types, bool tex_basic, int num_cu, hipStream_t st, const DevScene<R>& S, const PassGeom& g,
-                         const Work<R>& w, int d) {
+template <uint32_t F, uint32_t M>
+static void launch_shade(uint32_t mat_types, bool tex_basic, int num_cu, hipStream_t st, const DevScene& S, const PassGeom& g,
+                         const Work& w, int d) {
     if (!(mat_types & (1u << M))) return;
     constexpr bool textured = M == MAT_LAMBERTIAN || M == MAT_LIGHT || M == MAT_ISOTROPIC;
     if (!textured || tex_basic)
-        hipLaunchKernelGGL((k_shade<R, F, M, kTexBasic>), dim3(shade_blocks<R, F, M, kTexBasic>(num_cu)), dim3(kBlock), 0, st, S, g, w, d);
+        hipLaunchKernelGGL((k_shade<F, M, kTexBasic>), dim3(shade_blocks<F, M, kTexBasic>(num_cu)), dim3(kBlock), 0, st, S, g, w, d);
     else
-        hipLaunchKernelGGL((k_shade<R, F, M, TF_ALL>), dim3(shade_blocks<R, F, M, TF_ALL>(num_cu)), dim3(kBlock), 0, st, S, g, w, d);
+        hipLaunchKernelGGL((k_shade<F, M, TF_ALL>), dim3(shade_blocks<F, M, TF_ALL>(num_cu)), dim3(kBlock), 0, st, S, g, w, d);
 }
 // One bounce (extend + one shade launch per material type present) of the smallest kernel instantiation that
 // covers the scene's features.
-template <class R, uint32_t F, bool L, bool FUSE>
-static void launch_extend(int num_cu, hipStream_t st, const DevScene<R>& S, const PassGeom& g, const CameraRec<R>& cam, const Work<R>& w, int d) {
+template <uint32_t F, bool L, bool FUSE>
+static void launch_extend(int num_cu, hipStream_t st, const DevScene& S, const PassGeom& g, const CameraRec& cam, const Work& w, int d) {
     const size_t lds = extend_lds_bytes(L, g.stack);
-    static const bool checked = !L || static_lds_is_zero(reinterpret_cast<const void*>(k_extend<R, F, L, FUSE>));
+    static const bool checked = !L || static_lds_is_zero(reinterpret_cast<const void*>(k_extend<F, L, FUSE>));
     (void)checked;
     // num_cu (256) is a multiple of 8: the wave count is a multiple of kShards
-    const int blocks = blocks_per_cu(reinterpret_cast<const void*>(k_extend<R, F, L, FUSE>), L ? kBlockL : kBlock, lds) * num_cu;
-    hipLaunchKernelGGL((k_extend<R, F, L, FUSE>), dim3(blocks), dim3(L ? kBlockL : kBlock), lds, st, S, g, cam, w, d);
+    const int blocks = blocks_per_cu(reinterpret_cast<const void*>(k_extend<F, L, FUSE>), L ? kBlockL : kBlock, lds) * num_cu;
+    hipLaunchKernelGGL((k_extend<F, L, FUSE>), dim3(blocks), dim3(L ? kBlockL : kBlock), lds, st, S, g, cam, w, d);
 }
 // One bounce (extend + one shade launch per material type present, unless fused) of the smallest kernel
 // instantiation that covers the scene's features.
-template <class R, uint32_t F>
-static void launch_bounce(uint32_t mat_types, bool tex_basic, int variant, int num_cu, hipStream_t st, const DevScene<R>& S, const PassGeom& g,
-                          const CameraRec<R>& cam, const Work<R>& w, int d, const std::function<void()>& mark) {
+template <uint32_t F>
+static void launch_bounce(uint32_t mat_types, bool tex_basic, int variant, int num_cu, hipStream_t st, const DevScene& S, const PassGeom& g,
+                          const CameraRec& cam, const Work& w, int d, const std::function<void()>& mark) {
     if (mark) mark();
-    if constexpr (F == kFeatSpheres && std::is_same<R, double>::value) {
-        if (variant == EXT_FUSED) launch_extend<R, F, true, true>(num_cu, st, S, g, cam, w, d);
-        else if (variant == EXT_LDS) launch_extend<R, F, true, false>(num_cu, st, S, g, cam, w, d);
-        else launch_extend<R, F, false, false>(num_cu, st, S, g, cam, w, d);
+    if constexpr (F == kFeatSpheres) {
+        if (variant == EXT_FUSED) launch_extend<F, true, true>(num_cu, st, S, g, cam, w, d);
+        else if (variant == EXT_LDS) launch_extend<F, true, false>(num_cu, st, S, g, cam, w, d);
+        else launch_extend<F, false, false>(num_cu, st, S, g, cam, w, d);
     } else {
-        launch_extend<R, F, false, false>(num_cu, st, S, g, cam, w, d);
+        launch_extend<F, false, false>(num_cu, st, S, g, cam, w, d);
     }
     if (mark) mark();
     if (variant != EXT_FUSED) {
-        launch_shade<R, F, MAT_LAMBERTIAN>(mat_types, tex_basic, num_cu, st, S, g, w, d);
-        launch_shade<R, F, MAT_METAL>(mat_types, tex_basic, num_cu, st, S, g, w, d);
-        launch_shade<R, F, MAT_DIELECTRIC>(mat_types, tex_basic, num_cu, st, S, g, w, d);
-        launch_shade<R, F, MAT_LIGHT>(mat_types, tex_basic, num_cu, st, S, g, w, d);
-        launch_shade<R, F, MAT_ISOTROPIC>(mat_types, tex_basic, num_cu, st, S, g, w, d);
+        launch_shade<F, MAT_LAMBERTIAN>(mat_types, tex_basic, num_cu, st, S, g, w, d);
+        launch_shade<F, MAT_METAL>(mat_types, tex_basic, num_cu, st, S, g, w, d);
+        launch_shade<F, MAT_DIELECTRIC>(mat_types, tex_basic, num_cu, st, S, g, w, d);
+        launch_shade<F, MAT_LIGHT>(mat_types, tex_basic, num_cu, st, S, g, w, d);
+        launch_shade<F, MAT_ISOTROPIC>(mat_types, tex_basic, num_cu, st, S, g, w, d);
     }
     if (mark) mark();
 }
-int extend_variant(const DeviceScene<double>& ds, int flags) {
+int extend_variant(const DeviceScene& ds, int flags) {
     if (!ds.lds_scene || (flags & RT_GLOBAL_SCENE) || (ds.features & ~kFeatSpheres) != 0)
         return !(flags & RT_WAVEFRONT) ? EXT_MEGA_G : EXT_GLOBAL;
     // an LDS-image scene whose shading the LDS table cannot hold (noise / image textures: the two perlin spheres) runs
@@ -708,8 +702,16 @@ static void check_ring_waves(int blocks, int block, int num_cu) {
         throw std::runtime_error("internal: persistent grid larger than the camera-ray rings");
 }
 template <uint32_t F, uint32_t TF>
-static KernelId launch_paths_g_ft(int num_cu, hipStream_t st, const DevScene<double>& S, const PassGeom& g, const CameraRec<double>& cam,
-                              const Work<double>& w, uint32_t* next_slot) {
+static KernelId launch_paths_g_ft(int num_cu, hipStream_t st, const DevScene& S, const PassGeom& g, const CameraRec& cam,
+                              const Work& w, uint32_t* next_slot) {
+    // one persistent launch of the LM instantiation (a compile-time value) that was chosen
+    auto go = [&](auto lm, int block, size_t lds, const DevScene& scene, const PassGeom& geom) -> KernelId {
+        constexpr int LM = decltype(lm)::value;
+        const int blocks = blocks_per_cu(reinterpret_cast<const void*>(k_paths_g<F, TF, LM>), block, lds) * num_cu;
+        check_ring_waves(blocks, block, num_cu);
+        hipLaunchKernelGGL((k_paths_g<F, TF, LM>), dim3(blocks), dim3(block), lds, st, scene, geom, cam, w, next_slot);
+        return {F, TF, LM};
+    };
     // g.stack = stack_rows: sentinel + entries + spare row
     const size_t lm_head = paths_g_head_bytes(g.stack, kBlockM, (F & F_CODE16) != 0) + paths_g_world_bytes(S.nworld, S.n_objs, lds_mats<TF>(S.n_mats));
     const size_t lds_m = align16(align128(lm_head) + paths_g_mesh_bytes(S.n_nodes, S.n_primrefs, (F & F_TRI) ? S.n_primrefs : 0u));
@@ -722,35 +724,23 @@ static KernelId launch_paths_g_ft(int num_cu, hipStream_t st, const DevScene<dou
         // not for a world without a BVH node (the earth: one sphere): its traces are one primitive test and its paths end
         // after a segment or two, so most lanes start a path every round and the ring only adds LDS traffic (-1.4 %)
         gr.lds_ring = (paths_g_ring(F, 1) && S.n_nodes > 0 && lds_r <= kPathsGLdsCap) ? 1u : 0u;
-        const size_t lds = gr.lds_ring ? lds_r : lds_m;
-        const int blocks = blocks_per_cu(reinterpret_cast<const void*>(k_paths_g<F, TF, 1>), kBlockM, lds) * num_cu;
-        check_ring_waves(blocks, kBlockM, num_cu);
-        hipLaunchKernelGGL((k_paths_g<F, TF, 1>), dim3(blocks), dim3(kBlockM), lds, st, S, gr, cam, w, next_slot);
-        return {F, TF, 1};
+        return go(std::integral_constant<int, 1>{}, kBlockM, gr.lds_ring ? lds_r : lds_m, S, gr);
     }
     // too large for LM 1: as many of the first (top-level) nodes as fit beside the stacks
     const size_t head = align128(lm_head);
     const size_t node_bytes = sizeof(BvhNode);
     const uint32_t fit = head < kPathsGLdsCap ? static_cast<uint32_t>((kPathsGLdsCap - head) / node_bytes) : 0u;
     if (S.n_nodes > 0 && fit >= kLdsPartialMinNodes) {
-        DevScene<double> SP = S;
+        DevScene SP = S;
         // option render.lds_nodes_max (diagnostic): a cap on the LDS-resident nodes, to measure what each one is worth
         const uint32_t cap = static_cast<uint32_t>(opt(Opt::LdsNodesMax));
         SP.n_lds_nodes = std::min<uint32_t>(std::min<uint32_t>(fit, S.n_nodes), std::max<uint32_t>(cap, kLdsPartialMinNodes));
-        const size_t lds_p = head + node_bytes * SP.n_lds_nodes;
-        const int blocks = blocks_per_cu(reinterpret_cast<const void*>(k_paths_g<F, TF, 2>), kBlockM, lds_p) * num_cu;
-        check_ring_waves(blocks, kBlockM, num_cu);
-        hipLaunchKernelGGL((k_paths_g<F, TF, 2>), dim3(blocks), dim3(kBlockM), lds_p, st, SP, g, cam, w, next_slot);
-        return {F, TF, 2};
+        return go(std::integral_constant<int, 2>{}, kBlockM, head + node_bytes * SP.n_lds_nodes, SP, g);
     }
-    const size_t lds = paths_g_head_bytes(g.stack, kBlock, (F & F_CODE16) != 0);
-    const int blocks = blocks_per_cu(reinterpret_cast<const void*>(k_paths_g<F, TF, 0>), kBlock, lds) * num_cu;
-    check_ring_waves(blocks, kBlock, num_cu);
-    hipLaunchKernelGGL((k_paths_g<F, TF, 0>), dim3(blocks), dim3(kBlock), lds, st, S, g, cam, w, next_slot);
-    return {F, TF, 0};
+    return go(std::integral_constant<int, 0>{}, kBlock, paths_g_head_bytes(g.stack, kBlock, (F & F_CODE16) != 0), S, g);
 }
 KernelId launch_paths_g(uint32_t feat, bool tex_basic, bool tex_bary, bool codes16, uint32_t leaf_shift, int num_cu, hipStream_t st,
-                        const DevScene<double>& S, const PassGeom& g, const CameraRec<double>& cam, const Work<double>& w, uint32_t* next_slot) {
+                        const DevScene& S, const PassGeom& g, const CameraRec& cam, const Work& w, uint32_t* next_slot) {
     constexpr uint32_t C = F_CODE16;
     if (leaf_shift) {
         // pair-aligned leaves (build_device_scene: mesh feature sets with triangles only): the F_LEAF2 mesh kernels
@@ -795,74 +785,72 @@ KernelId launch_paths_g(uint32_t feat, bool tex_basic, bool tex_bary, bool codes
         return launch_paths_g_ft<F_ALL, TF_ALL>(num_cu, st, S, g, cam, w, next_slot);
     }
 }
-template <uint32_t F, bool L>
-static void launch_guides_fl(const DeviceScene<double>& ds, hipStream_t st, const GuideGeom& g, const CameraRec<double>& cam, double* guides, double* rays) {
-    const uint32_t stack = stack_rows(ds.max_stack), npix = static_cast<uint32_t>(g.rows) * static_cast<uint32_t>(g.W);
+// The ray kernels (one thread per ray or pixel: k_trace_rays, k_guides, k_query_rays, k_occlude_rays) share their choice of
+// instantiation and their launch.
+// The choice: the LDS scene image where the scene has one (spheres only) and global_scene does not rule it out, else
+// the smallest HBM-scene feature set that covers the scene's features & MASK.  fn(f, l) receives F and L as
+// compile-time values (std::integral_constant).
+template <uint32_t MASK = ~0u, class Fn>
+static void with_ray_features(const DeviceScene& ds, bool global_scene, Fn&& fn) {
+    const uint32_t feat = ds.features & MASK;
+    if (ds.lds_scene && !global_scene && (ds.features & ~kFeatSpheres) == 0) fn(std::integral_constant<uint32_t, kFeatSpheres>{}, std::true_type{});
+    else if ((feat & ~kFeatSpheres) == 0) fn(std::integral_constant<uint32_t, kFeatSpheres>{}, std::false_type{});
+    else if ((feat & ~kFeatMesh) == 0) fn(std::integral_constant<uint32_t, kFeatMesh & MASK>{}, std::false_type{});
+    else fn(std::integral_constant<uint32_t, F_ALL & MASK>{}, std::false_type{});
+}
+// The launch of `kernel` over n items: a block's traversal stacks in dynamic LDS, behind the scene image when L (more
+// than 64 KiB then: blocks_per_cu sets the attribute; and the image must start at LDS address 0).
+template <auto kernel, bool L, class... Args>
+static void launch_ray_kernel(const DeviceScene& ds, hipStream_t st, uint32_t n, const Args&... args) {
+    const uint32_t stack = stack_rows(ds.max_stack);
     constexpr int B = L ? kBlockL : kBlock;
     const size_t lds = L ? kLdsImageBytes + paths_stack_bytes(stack) : sizeof(int32_t) * stack * kBlock;
-    const dim3 grid((npix + B - 1) / B);
-    auto go = [&](auto kernel) {
-        if constexpr (L) {
-            static const bool checked = static_lds_is_zero(reinterpret_cast<const void*>(kernel));
-            (void)checked;
-            (void)blocks_per_cu(reinterpret_cast<const void*>(kernel), B, lds);  // the > 64 KiB dynamic-LDS attribute
-        }
-        hipLaunchKernelGGL(kernel, grid, dim3(B), lds, st, ds.view, g, cam, guides, rays);
-    };
-    // the texture kinds the scene needs: solid + checker, those plus barycentric images on triangles, or all
-    if (ds.tex_basic) return go(k_guides<F, L, kTexBasic>);
-    if constexpr ((F & F_TRI) != 0)
-        if (ds.tex_bary) return go(k_guides<F, L, kTexBary>);
-    go(k_guides<F, L, TF_ALL>);
-}
-
-void launch_trace_rays(const DeviceScene<double>& ds, bool global_scene, hipStream_t st, const double* d_rays, uint32_t nn, double* d_t, double* d_n) {
-    const uint32_t stack = stack_rows(ds.max_stack);
-    const uint32_t feat = ds.features;
-    if (ds.lds_scene && !global_scene && (feat & ~kFeatSpheres) == 0) {
-        const size_t lds = kLdsImageBytes + paths_stack_bytes(stack);
-        static const bool checked = static_lds_is_zero(reinterpret_cast<const void*>(k_trace_rays<kFeatSpheres, true>));
+    if constexpr (L) {
+        static const bool checked = static_lds_is_zero(reinterpret_cast<const void*>(kernel));
         (void)checked;
-        (void)blocks_per_cu(reinterpret_cast<const void*>(k_trace_rays<kFeatSpheres, true>), kBlockL, lds);
-        hipLaunchKernelGGL((k_trace_rays<kFeatSpheres, true>), dim3((nn + kBlockL - 1) / kBlockL), dim3(kBlockL), lds, st, ds.view, d_rays, nn, stack, d_t, d_n);
-    } else {
-        const size_t lds = sizeof(int32_t) * stack * kBlock;
-        const dim3 grid((nn + kBlock - 1) / kBlock);
-        if ((feat & ~kFeatSpheres) == 0)
-            hipLaunchKernelGGL((k_trace_rays<kFeatSpheres, false>), grid, dim3(kBlock), lds, st, ds.view, d_rays, nn, stack, d_t, d_n);
-        else if ((feat & ~kFeatMesh) == 0)
-            hipLaunchKernelGGL((k_trace_rays<kFeatMesh, false>), grid, dim3(kBlock), lds, st, ds.view, d_rays, nn, stack, d_t, d_n);
-        else
-            hipLaunchKernelGGL((k_trace_rays<F_ALL, false>), grid, dim3(kBlock), lds, st, ds.view, d_rays, nn, stack, d_t, d_n);
+        (void)blocks_per_cu(reinterpret_cast<const void*>(kernel), B, lds);
     }
+    hipLaunchKernelGGL(kernel, dim3((n + B - 1) / B), dim3(B), lds, st, args...);
 }
 
-void launch_guides(const DeviceScene<double>& ds, int flags, hipStream_t st, const GuideGeom& g, const CameraRec<double>& cam, double* guides,
+void launch_trace_rays(const DeviceScene& ds, bool global_scene, hipStream_t st, const double* d_rays, uint32_t nn, double* d_t, double* d_n) {
+    with_ray_features(ds, global_scene, [&](auto f, auto l) {
+        constexpr uint32_t F = decltype(f)::value;
+        constexpr bool L = decltype(l)::value;
+        launch_ray_kernel<k_trace_rays<F, L>, L>(ds, st, nn, ds.view, d_rays, nn, stack_rows(ds.max_stack), d_t, d_n);
+    });
+}
+
+void launch_guides(const DeviceScene& ds, int flags, hipStream_t st, const GuideGeom& g, const CameraRec& cam, double* guides,
                    double* rays) {
-    const uint32_t feat = ds.features;
-    if (ds.lds_scene && !(flags & RT_GLOBAL_SCENE) && (feat & ~kFeatSpheres) == 0) launch_guides_fl<kFeatSpheres, true>(ds, st, g, cam, guides, rays);
-    else if ((feat & ~kFeatSpheres) == 0) launch_guides_fl<kFeatSpheres, false>(ds, st, g, cam, guides, rays);
-    else if ((feat & ~kFeatMesh) == 0) launch_guides_fl<kFeatMesh, false>(ds, st, g, cam, guides, rays);
-    else launch_guides_fl<F_ALL, false>(ds, st, g, cam, guides, rays);
+    const uint32_t npix = static_cast<uint32_t>(g.rows) * static_cast<uint32_t>(g.W);
+    with_ray_features(ds, (flags & RT_GLOBAL_SCENE) != 0, [&](auto f, auto l) {
+        constexpr uint32_t F = decltype(f)::value;
+        constexpr bool L = decltype(l)::value;
+        // the texture kinds the scene needs: solid + checker, those plus barycentric images on triangles, or all
+        if (ds.tex_basic) return launch_ray_kernel<k_guides<F, L, kTexBasic>, L>(ds, st, npix, ds.view, g, cam, guides, rays);
+        if constexpr ((F & F_TRI) != 0)
+            if (ds.tex_bary) return launch_ray_kernel<k_guides<F, L, kTexBary>, L>(ds, st, npix, ds.view, g, cam, guides, rays);
+        launch_ray_kernel<k_guides<F, L, TF_ALL>, L>(ds, st, npix, ds.view, g, cam, guides, rays);
+    });
 }
 
-void bounce(const DeviceScene<double>& ds, int variant, int num_cu, hipStream_t st, const PassGeom& g, const CameraRec<double>& cam,
-            const Work<double>& w, int d, const std::function<void()>& mark) {
-    using R = double;
+void bounce(const DeviceScene& ds, int variant, int num_cu, hipStream_t st, const PassGeom& g, const CameraRec& cam,
+            const Work& w, int d, const std::function<void()>& mark) {
     const uint32_t feat = ds.features;
     if ((feat & ~kFeatSpheres) == 0)
-        launch_bounce<R, kFeatSpheres>(ds.mat_types, ds.tex_basic, variant, num_cu, st, ds.view, g, cam, w, d, mark);
+        launch_bounce<kFeatSpheres>(ds.mat_types, ds.tex_basic, variant, num_cu, st, ds.view, g, cam, w, d, mark);
     else if ((feat & ~kFeatMesh) == 0)
-        launch_bounce<R, kFeatMesh>(ds.mat_types, ds.tex_basic, EXT_GLOBAL, num_cu, st, ds.view, g, cam, w, d, mark);
+        launch_bounce<kFeatMesh>(ds.mat_types, ds.tex_basic, EXT_GLOBAL, num_cu, st, ds.view, g, cam, w, d, mark);
     else
-        launch_bounce<R, F_ALL>(ds.mat_types, ds.tex_basic, EXT_GLOBAL, num_cu, st, ds.view, g, cam, w, d, mark);
+        launch_bounce<F_ALL>(ds.mat_types, ds.tex_basic, EXT_GLOBAL, num_cu, st, ds.view, g, cam, w, d, mark);
 }
 
 // The small kernels renderer.hip runs between the path launches, one thread per item unless noted.
 static dim3 grid256(uint32_t n) { return dim3((n + 255) / 256); }
-void launch_accum(hipStream_t st, const PassGeom& g, const Work<double>& w, double* qsum, uint32_t m) {
-    if (qsum) hipLaunchKernelGGL(k_accum_images<double>, grid256(g.npix_pad), dim3(256), 0, st, g, w, qsum, m);
-    else hipLaunchKernelGGL(k_accum<double>, grid256(g.npix_pad), dim3(256), 0, st, g, w);
+void launch_accum(hipStream_t st, const PassGeom& g, const Work& w, double* qsum, uint32_t m) {
+    if (qsum) hipLaunchKernelGGL(k_accum_images, grid256(g.npix_pad), dim3(256), 0, st, g, w, qsum, m);
+    else hipLaunchKernelGGL(k_accum, grid256(g.npix_pad), dim3(256), 0, st, g, w);
 }
 void launch_finalize(hipStream_t st, const double* acc, uint8_t* rgb, uint32_t n, int spp) {
     hipLaunchKernelGGL(k_finalize, grid256(n), dim3(256), 0, st, acc, rgb, n, spp);
@@ -874,7 +862,7 @@ void launch_adapt_store(hipStream_t st, const uint32_t* list, uint32_t n, const 
     hipLaunchKernelGGL(k_adapt_store, grid256(n), dim3(256), 0, st, list, n, acc, spp, work);
 }
 // one wave per list entry, `cap` entries at the most (the count is on the device)
-void launch_adapt_accum(hipStream_t st, const uint32_t* list, uint32_t cap, const ResRec<double>* res, uint32_t k, int spp, int32_t* work) {
+void launch_adapt_accum(hipStream_t st, const uint32_t* list, uint32_t cap, const ResRec* res, uint32_t k, int spp, int32_t* work) {
     hipLaunchKernelGGL(k_adapt_accum, dim3((cap + kAdaptAccumWaves - 1) / kAdaptAccumWaves), dim3(64 * kAdaptAccumWaves), 0, st, list, res, k, spp, work);
 }
 void launch_adapt_level(hipStream_t st, int level, int32_t* work, int W, int sqx, uint32_t nsq, uint8_t* f0, uint8_t* f1, uint8_t* f2, uint32_t* list,
@@ -889,53 +877,24 @@ void launch_adapt_fill(hipStream_t st, int32_t* work, uint8_t* rgb, int W, int r
 // The rt_query_rays launchers close the file: they instantiate k_query_rays and k_occlude_rays, and the compiler emits
 // device functions in instantiation order, so every earlier kernel and the out-of-line helpers it calls keep their
 // relative places -- and with them their code bytes (DESIGN.md 4.7 compares them with the build before these kernels).
-// rt_query_rays, closest mode: launch_trace_rays' instantiation choice (the LDS image, else the smallest HBM-scene feature set)
-template <uint32_t F, bool L>
-static void launch_query_fl(const DeviceScene<double>& ds, hipStream_t st, const double* d_rays, const double* d_tmax, uint32_t nn, bool no_media,
-                            double* d_hits) {
-    const uint32_t stack = stack_rows(ds.max_stack);
-    constexpr int B = L ? kBlockL : kBlock;
-    const size_t lds = L ? kLdsImageBytes + paths_stack_bytes(stack) : sizeof(int32_t) * stack * kBlock;
-    if constexpr (L) {
-        static const bool checked = static_lds_is_zero(reinterpret_cast<const void*>(k_query_rays<F, L>));
-        (void)checked;
-        (void)blocks_per_cu(reinterpret_cast<const void*>(k_query_rays<F, L>), B, lds);  // the > 64 KiB dynamic-LDS attribute
-    }
-    hipLaunchKernelGGL((k_query_rays<F, L>), dim3((nn + B - 1) / B), dim3(B), lds, st, ds.view, d_rays, d_tmax, nn, no_media ? 1u : 0u, d_hits);
-}
-void launch_query_rays(const DeviceScene<double>& ds, bool global_scene, hipStream_t st, const double* d_rays, const double* d_tmax, uint32_t nn,
+// rt_query_rays, closest mode
+void launch_query_rays(const DeviceScene& ds, bool global_scene, hipStream_t st, const double* d_rays, const double* d_tmax, uint32_t nn,
                        bool no_media, double* d_hits) {
-    const uint32_t feat = ds.features;
-    if (ds.lds_scene && !global_scene && (feat & ~kFeatSpheres) == 0) launch_query_fl<kFeatSpheres, true>(ds, st, d_rays, d_tmax, nn, no_media, d_hits);
-    else if ((feat & ~kFeatSpheres) == 0) launch_query_fl<kFeatSpheres, false>(ds, st, d_rays, d_tmax, nn, no_media, d_hits);
-    else if ((feat & ~kFeatMesh) == 0) launch_query_fl<kFeatMesh, false>(ds, st, d_rays, d_tmax, nn, no_media, d_hits);
-    else launch_query_fl<F_ALL, false>(ds, st, d_rays, d_tmax, nn, no_media, d_hits);
+    with_ray_features(ds, global_scene, [&](auto f, auto l) {
+        constexpr uint32_t F = decltype(f)::value;
+        constexpr bool L = decltype(l)::value;
+        launch_ray_kernel<k_query_rays<F, L>, L>(ds, st, nn, ds.view, d_rays, d_tmax, nn, no_media ? 1u : 0u, d_hits);
+    });
 }
 // the any-hit kernels: the same choice with the media bits removed; the child order from option query.any_sorted
-template <uint32_t F, bool L>
-static void launch_occlude_fl(const DeviceScene<double>& ds, hipStream_t st, const double* d_rays, const double* d_tmax, uint32_t nn, uint8_t* d_occ) {
-    const uint32_t stack = stack_rows(ds.max_stack);
-    constexpr int B = L ? kBlockL : kBlock;
-    const size_t lds = L ? kLdsImageBytes + paths_stack_bytes(stack) : sizeof(int32_t) * stack * kBlock;
-    auto go = [&](auto kernel) {
-        if constexpr (L) {
-            static const bool checked = static_lds_is_zero(reinterpret_cast<const void*>(kernel));
-            (void)checked;
-            (void)blocks_per_cu(reinterpret_cast<const void*>(kernel), B, lds);
-        }
-        hipLaunchKernelGGL(kernel, dim3((nn + B - 1) / B), dim3(B), lds, st, ds.view, d_rays, d_tmax, nn, d_occ);
-    };
-    if (opt(Opt::QueryAnySorted) != 0) go(k_occlude_rays<F, L, 1>);
-    else go(k_occlude_rays<F, L, 2>);
-}
-void launch_occlude_rays(const DeviceScene<double>& ds, bool global_scene, hipStream_t st, const double* d_rays, const double* d_tmax, uint32_t nn,
+void launch_occlude_rays(const DeviceScene& ds, bool global_scene, hipStream_t st, const double* d_rays, const double* d_tmax, uint32_t nn,
                          uint8_t* d_occ) {
-    constexpr uint32_t kNoMedia = ~(F_MEDIA | F_MEDIA_G);
-    const uint32_t feat = ds.features & kNoMedia;
-    if (ds.lds_scene && !global_scene && (ds.features & ~kFeatSpheres) == 0) launch_occlude_fl<kFeatSpheres, true>(ds, st, d_rays, d_tmax, nn, d_occ);
-    else if ((feat & ~kFeatSpheres) == 0) launch_occlude_fl<kFeatSpheres, false>(ds, st, d_rays, d_tmax, nn, d_occ);
-    else if ((feat & ~kFeatMesh) == 0) launch_occlude_fl<kFeatMesh & kNoMedia, false>(ds, st, d_rays, d_tmax, nn, d_occ);
-    else launch_occlude_fl<F_ALL & kNoMedia, false>(ds, st, d_rays, d_tmax, nn, d_occ);
+    with_ray_features<~(F_MEDIA | F_MEDIA_G)>(ds, global_scene, [&](auto f, auto l) {
+        constexpr uint32_t F = decltype(f)::value;
+        constexpr bool L = decltype(l)::value;
+        if (opt(Opt::QueryAnySorted) != 0) launch_ray_kernel<k_occlude_rays<F, L, 1>, L>(ds, st, nn, ds.view, d_rays, d_tmax, nn, d_occ);
+        else launch_ray_kernel<k_occlude_rays<F, L, 2>, L>(ds, st, nn, ds.view, d_rays, d_tmax, nn, d_occ);
+    });
 }
 
 }  // namespace art

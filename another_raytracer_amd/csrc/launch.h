@@ -13,7 +13,7 @@ namespace art {
 // paths (k_paths: the fused LDS bounce loop in registers, one launch per pass), 4 = persistent paths over the HBM scene (k_paths_g).
 enum ExtendVariant { EXT_GLOBAL = 0, EXT_LDS = 1, EXT_FUSED = 2, EXT_MEGA = 3, EXT_MEGA_G = 4 };
 // The variant for this scene and these flags (RT_GLOBAL_SCENE / RT_SPLIT_SHADE / RT_WAVEFRONT force the general kernels).
-int extend_variant(const DeviceScene<double>& ds, int flags);
+int extend_variant(const DeviceScene& ds, int flags);
 // Which persistent-path kernel a render ran (rt_stats.kernel_*): k_paths_g<F, TF, LM>, or k_paths as LM 3
 struct KernelId {
     uint32_t f = 0, tf = 0;
@@ -24,27 +24,27 @@ struct KernelId {
 bool static_lds_is_zero(const void* kernel);
 int blocks_per_cu(const void* kernel, int block, size_t lds);
 KernelId launch_paths_g(uint32_t feat, bool tex_basic, bool tex_bary, bool codes16, uint32_t leaf_shift, int num_cu, hipStream_t st,
-                        const DevScene<double>& S, const PassGeom& g, const CameraRec<double>& cam, const Work<double>& w, uint32_t* next_slot);
-void bounce(const DeviceScene<double>& ds, int variant, int num_cu, hipStream_t st, const PassGeom& g, const CameraRec<double>& cam,
-            const Work<double>& w, int d, const std::function<void()>& mark);
-void launch_accum(hipStream_t st, const PassGeom& g, const Work<double>& w, double* qsum, uint32_t m);  // qsum: k_accum_images, or null
+                        const DevScene& S, const PassGeom& g, const CameraRec& cam, const Work& w, uint32_t* next_slot);
+void bounce(const DeviceScene& ds, int variant, int num_cu, hipStream_t st, const PassGeom& g, const CameraRec& cam,
+            const Work& w, int d, const std::function<void()>& mark);
+void launch_accum(hipStream_t st, const PassGeom& g, const Work& w, double* qsum, uint32_t m);  // qsum: k_accum_images, or null
 void launch_finalize(hipStream_t st, const double* acc, uint8_t* rgb, uint32_t n, int spp);
 void launch_adapt_corners(hipStream_t st, uint32_t* list, int W, int sqx, uint32_t nsq);
 void launch_adapt_store(hipStream_t st, const uint32_t* list, uint32_t n, const double* acc, int spp, int32_t* work);
-void launch_adapt_accum(hipStream_t st, const uint32_t* list, uint32_t cap, const ResRec<double>* res, uint32_t k, int spp, int32_t* work);
+void launch_adapt_accum(hipStream_t st, const uint32_t* list, uint32_t cap, const ResRec* res, uint32_t k, int spp, int32_t* work);
 void launch_adapt_level(hipStream_t st, int level, int32_t* work, int W, int sqx, uint32_t nsq, uint8_t* f0, uint8_t* f1, uint8_t* f2, uint32_t* list,
                         uint32_t* count);
 void launch_adapt_fill(hipStream_t st, int32_t* work, uint8_t* rgb, int W, int rows, int sqx, const uint8_t* f0, const uint8_t* f1, const uint8_t* f2);
-void launch_trace_rays(const DeviceScene<double>& ds, bool global_scene, hipStream_t st, const double* rays, uint32_t n, double* t_out, double* n_out);
+void launch_trace_rays(const DeviceScene& ds, bool global_scene, hipStream_t st, const double* rays, uint32_t n, double* t_out, double* n_out);
 // rt_query_rays: closest hits with the record (hits: n x 12) / occlusion bytes; t_max may be null (+inf)
-void launch_query_rays(const DeviceScene<double>& ds, bool global_scene, hipStream_t st, const double* rays, const double* t_max, uint32_t n,
+void launch_query_rays(const DeviceScene& ds, bool global_scene, hipStream_t st, const double* rays, const double* t_max, uint32_t n,
                        bool no_media, double* hits);
-void launch_occlude_rays(const DeviceScene<double>& ds, bool global_scene, hipStream_t st, const double* rays, const double* t_max, uint32_t n,
+void launch_occlude_rays(const DeviceScene& ds, bool global_scene, hipStream_t st, const double* rays, const double* t_max, uint32_t n,
                          uint8_t* occluded);
-void launch_guides(const DeviceScene<double>& ds, int flags, hipStream_t st, const GuideGeom& g, const CameraRec<double>& cam, double* guides,
+void launch_guides(const DeviceScene& ds, int flags, hipStream_t st, const GuideGeom& g, const CameraRec& cam, double* guides,
                    double* rays);
 // k_paths.hip
-void launch_paths(int num_cu, hipStream_t st, const DevScene<double>& S, const PassGeom& g, const CameraRec<double>& cam, const Work<double>& w,
+void launch_paths(int num_cu, hipStream_t st, const DevScene& S, const PassGeom& g, const CameraRec& cam, const Work& w,
                   uint32_t* next_slot);
 size_t pool_bytes(int variant, int num_cu);  // the path pools of `variant` (k_paths' PathPool, kPoolCap entries per wave; 0 for every other)
 

@@ -7,7 +7,8 @@
 //   * BVH          one flat array of 128-B four-child nodes (f32, conservatively rounded boxes) per scene
 //   * objects      the top-level hittable_list (world) as ObjRec: PRIM | BVH | XFORM (translate/rotate_y) | MEDIUM
 //   * materials    MatRec, textures TexRec, perlin tables, image texel pool
-// Every record exists in an f64 and an f32 instantiation (template R); the BVH is always f32.
+// Every record is f64 (the only arithmetic); the BVH is always f32.  The static_asserts pin the sizes the device
+// copies, the LDS carve-ups and the scene file rely on.
 #pragma once
 #include <cstdint>
 
@@ -29,53 +30,55 @@ ART_HD uint32_t primref_index(uint32_t ref) { return ref & kPrimIndexMask; }
 
 enum SphereFlags : uint32_t { SPH_MOVING = 1u };  // moving_sphere: centre lerp over [t0, t0+dt], no u,v
 
-template <class R>
 struct SphereRec {      // sphere.h / moving_sphere.h
-    R c[3];             // center (center0 for moving spheres)
-    R r;                // radius
-    R d[3];             // center1 - center0 (moving only)
-    R t0, dt;           // time0, time1 - time0 (moving only)
+    double c[3];        // center (center0 for moving spheres)
+    double r;           // radius
+    double d[3];        // center1 - center0 (moving only)
+    double t0, dt;      // time0, time1 - time0 (moving only)
     uint32_t mat;
     uint32_t flags;
 };
-template <class R>
+static_assert(sizeof(SphereRec) == 80, "SphereRec is 80 B");
 struct TriRec {         // triangle.h: pt1, pt2, pt3
-    R p[9];
+    double p[9];
     uint32_t mat;
     uint32_t pad;
 };
+static_assert(sizeof(TriRec) == 80, "TriRec is 80 B");
 // A leaf triangle with its plane precomputed on the host by the device's own operations (the LM 1 kernels'
 // LDS copy): n = cross(pt2 - pt1, pt3 - pt1) and dd = -dot(n, pt1), triangle.h:30-41
-template <class R>
 struct TriRec112 {
-    R p[9];
-    R n[3];
-    R dd;
+    double p[9];
+    double n[3];
+    double dd;
     uint32_t mat;
     uint32_t pad;
 };
+static_assert(sizeof(TriRec112) == 112, "TriRec112 is 112 B");
 // One primitive record of any type (SphereRec, TriRec, RectRec, BoxRec are all <= 80 B): the device copy of a prim
 // object's primitive, indexed by object (DevScene::obj_prims)
 struct alignas(16) PrimRec80 {
     uint8_t b[80];
 };
-template <class R>
 struct RectRec {        // aarect.h: axis 0 = xy_rect (k on z), 1 = xz_rect (k on y), 2 = yz_rect (k on x)
-    R a0, a1, b0, b1, k;
+    double a0, a1, b0, b1, k;
     uint32_t axis;
     uint32_t mat;
 };
-template <class R>
 struct BoxRec {         // box.cpp: six rects in a fixed order (face index 0..5 = box.cpp:8-17 order)
-    R mn[3], mx[3];
+    double mn[3], mx[3];
     uint32_t mat;
     uint32_t pad;
 };
+static_assert(sizeof(RectRec) == 48 && sizeof(BoxRec) == 56, "RectRec is 48 B, BoxRec 56 B");
+static_assert(sizeof(SphereRec) <= sizeof(PrimRec80) && sizeof(TriRec) <= sizeof(PrimRec80) && sizeof(RectRec) <= sizeof(PrimRec80) &&
+                  sizeof(BoxRec) <= sizeof(PrimRec80),
+              "PrimRec80 holds every record");
 
 // ---------------------------------------------------------------------------------------------- BVH
 // Four-child node, 128 B = two cache lines, fetched as eight 16-B loads; the four child boxes are stored SoA so one
 // node visit tests all four with float4 arithmetic.  Child boxes are rounded outward to f32 and padded, so f32
-// traversal is conservative; leaf tests run in R.
+// traversal is conservative; leaf tests run in f64.
 //   child >= 0 : inner node index;   child < 0 : leaf ~((count << 24) | first_primref_slot);   -1 : empty slot
 struct alignas(16) BvhNode {
     float lox[4], hix[4];
@@ -160,14 +163,14 @@ static_assert(kLdsImageBytes % 16 == 0, "LDS image is copied in 16-B pieces");
 
 // ---------------------------------------------------------------------------------------------- objects
 enum ObjKind : int32_t { OBJ_PRIM = 0, OBJ_BVH = 1, OBJ_TRANSLATE = 2, OBJ_ROTATE_Y = 3, OBJ_MEDIUM = 4 };
-template <class R>
 struct ObjRec {
     int32_t kind;
     int32_t a;      // PRIM: prim ref; BVH: root node; TRANSLATE/ROTATE_Y: child object; MEDIUM: boundary object
     int32_t b;      // MEDIUM: phase material; BVH: leaf code of its hoisted primitives (tested before the tree), or -1
     int32_t pad;
-    R p[4];         // TRANSLATE: offset xyz; ROTATE_Y: sin, cos; MEDIUM: neg_inv_density
+    double p[4];    // TRANSLATE: offset xyz; ROTATE_Y: sin, cos; MEDIUM: neg_inv_density
 };
+static_assert(sizeof(ObjRec) == 48, "ObjRec is 48 B");
 constexpr int kMaxXformChain = 2;  // translate(rotate_y(X)) is the deepest chain in the reference scenes
 // Scene features: kernels are instantiated for feature subsets (spheres only / meshes / everything).
 // F_MEDIA: constant_medium objects; F_MEDIA_G: one of them has a boundary that is not a sphere primitive (its two
@@ -193,15 +196,14 @@ constexpr int kNumMatTypes = 5;
 // upload): a lambertian / diffuse_light / isotropic whose texture is a solid colour, copied into `albedo` (which only
 // metal uses otherwise), so its texture value needs no second dependent load (device.h mat_tex_value)
 enum MatFlags : uint32_t { MATF_NEEDS_UV = 1u, MATF_SOLID = 2u };
-template <class R>
 struct MatRec {
     uint32_t type;
     int32_t tex;    // lambertian / diffuse_light / isotropic
     uint32_t flags;
     uint32_t pad;
-    R albedo[3];    // metal
-    R fuzz;         // metal (already clamped to <= 1, material.h:47)
-    R ir;           // dielectric
+    double albedo[3];  // metal
+    double fuzz;       // metal (already clamped to <= 1, material.h:47)
+    double ir;         // dielectric
 };
 enum TexType : uint32_t { TEX_SOLID = 0, TEX_CHECKER = 1, TEX_NOISE = 2, TEX_IMAGE = 3, TEX_BARY_IMAGE = 4 };
 // Texture kinds present (shade kernels are instantiated for "solid + checker" and "all").
@@ -212,20 +214,18 @@ constexpr uint32_t kTexBasic = TF_SOLID | TF_CHECKER;
 // but not get_sphere_uv's acos / atan2 (the capsule's kernel: 20 spilled VGPRs with TF_ALL)
 constexpr uint32_t TF_BARY = 16u;
 constexpr uint32_t kTexBary = kTexBasic | TF_BARY;
-template <class R>
 struct TexRec {
     uint32_t type;
     int32_t even, odd;   // checker children
     int32_t perlin;      // noise: perlin table index
     int32_t image;       // image / bary_image: image index
     int32_t pad;
-    R c[3];              // solid colour
-    R scale;             // noise scale
-    R uv[6];             // bary_image texcoords a, b, c
+    double c[3];         // solid colour
+    double scale;        // noise scale
+    double uv[6];        // bary_image texcoords a, b, c
 };
-template <class R>
 struct PerlinRec {       // perlin.h: 256 random unit vectors + 3 permutations
-    R ranvec[256][3];
+    double ranvec[256][3];
     int32_t perm[3][256];
 };
 struct ImageRec {
@@ -234,10 +234,9 @@ struct ImageRec {
 };
 
 // ---------------------------------------------------------------------------------------------- camera
-template <class R>
 struct CameraRec {       // camera.h: precomputed on the host in f64 exactly as camera::camera does
-    R origin[3], llc[3], horizontal[3], vertical[3], u[3], v[3];
-    R lens_radius, time0, time1;
+    double origin[3], llc[3], horizontal[3], vertical[3], u[3], v[3];
+    double lens_radius, time0, time1;
 };
 
 // ---------------------------------------------------------------------------------------------- band partition

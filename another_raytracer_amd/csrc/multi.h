@@ -34,7 +34,7 @@ public:
     // p.band_rows sets the band height; p.band_count / p.band_index are ignored (the devices are the bands).
     // stats: segments / primary summed over the devices, ms = host wall time of the whole call (renders + gather +
     // unpack + output copy).
-    void render(const CameraRec<double>& cam, const RenderParams& p, uint8_t* out_rgb, bool out_device, RenderStats& stats);
+    void render(const CameraRec& cam, const RenderParams& p, uint8_t* out_rgb, bool out_device, RenderStats& stats);
     int ngpus() const;
     size_t scene_bytes() const;  // scene bytes on each device
     // Stats of device k (devices[k]) in the last render: its segments, its own kernel times and launches, its rows.

@@ -295,7 +295,7 @@ bool MultiRenderer::device_stats(int k, RenderStats& out) const {
 }
 const MultiTimes& MultiRenderer::times() const { return impl_->times; }
 
-void MultiRenderer::render(const CameraRec<double>& cam, const RenderParams& p, uint8_t* out_rgb, bool out_device, RenderStats& stats) {
+void MultiRenderer::render(const CameraRec& cam, const RenderParams& p, uint8_t* out_rgb, bool out_device, RenderStats& stats) {
     Impl& I = *impl_;
     if (!I.broken.empty()) throw std::runtime_error("rt_multi unusable: " + I.broken + " (destroy and re-create it)");
     const int n = static_cast<int>(I.devices.size());

@@ -12,49 +12,19 @@ namespace art {
 
 // ------------------------------------------------------------------------------------------------ path records
 // One path = one AoS record so that a lane touching a scattered slot reads whole cache lines:
-//   f32: 64 B = {o.xyz, time} {d.xyz, -} {T.rgb, L.r} {L.gb, rng}
-//   f64: 128 B = line 0 {o.xyz, d.xyz, time, rng} (all extend reads) + line 1 {T.rgb, L.rgb}
-template <class R> struct PathRec;
-template <> struct PathRec<float> {
-    float4 ot, d, tl, lr;
-};
-template <> struct PathRec<double> {
+//   128 B = line 0 {o.xyz, d.xyz, time, rng} (all extend reads) + line 1 {T.rgb, L.rgb}
+struct PathRec {
     double2 a, b, c, e;  // line 0: (ox,oy) (oz,dx) (dy,dz) (tm,rng)
     double2 f, g, h, i;  // line 1: (Tr,Tg) (Tb,Lr) (Lg,Lb) (-,-)
 };
-template <class R>
+static_assert(sizeof(PathRec) == 128, "PathRec is two 64-B lines");
 struct PathState {
-    Ray<R> ray;
-    V3<R> T, L;
+    Ray ray;
+    V3 T, L;
     uint64_t rng;
 };
-__device__ __forceinline__ void load_path(const PathRec<float>* P, uint32_t q, PathState<float>& s, bool full) {
-    const PathRec<float>& p = P[q];
-    const float4 ot = p.ot, d = p.d;
-    s.ray.o = mk(ot.x, ot.y, ot.z);
-    s.ray.tm = ot.w;
-    s.ray.d = mk(d.x, d.y, d.z);
-    const float4 lr = p.lr;
-    s.rng = (static_cast<uint64_t>(__float_as_uint(lr.w)) << 32) | __float_as_uint(lr.z);
-    if (full) {
-        const float4 tl = p.tl;
-        s.T = mk(tl.x, tl.y, tl.z);
-        s.L = mk(tl.w, lr.x, lr.y);
-    }
-}
-__device__ __forceinline__ void store_path(PathRec<float>* P, uint32_t q, const PathState<float>& s) {
-    PathRec<float>& p = P[q];
-    p.ot = make_float4(s.ray.o.x, s.ray.o.y, s.ray.o.z, s.ray.tm);
-    p.d = make_float4(s.ray.d.x, s.ray.d.y, s.ray.d.z, 0.0f);
-    p.tl = make_float4(s.T.x, s.T.y, s.T.z, s.L.x);
-    p.lr = make_float4(s.L.y, s.L.z, __uint_as_float(static_cast<uint32_t>(s.rng)), __uint_as_float(static_cast<uint32_t>(s.rng >> 32)));
-}
-__device__ __forceinline__ void store_rng(PathRec<float>* P, uint32_t q, uint64_t rng) {
-    float2* p = reinterpret_cast<float2*>(&P[q].lr) + 1;
-    *p = make_float2(__uint_as_float(static_cast<uint32_t>(rng)), __uint_as_float(static_cast<uint32_t>(rng >> 32)));
-}
-__device__ __forceinline__ void load_path(const PathRec<double>* P, uint32_t q, PathState<double>& s, bool full) {
-    const PathRec<double>& p = P[q];
+__device__ __forceinline__ void load_path(const PathRec* P, uint32_t q, PathState& s, bool full) {
+    const PathRec& p = P[q];
     const double2 a = p.a, b = p.b, c = p.c, e = p.e;
     s.ray.o = mk(a.x, a.y, b.x);
     s.ray.d = mk(b.y, c.x, c.y);
@@ -66,8 +36,8 @@ __device__ __forceinline__ void load_path(const PathRec<double>* P, uint32_t q, 
         s.L = mk(g.y, h.x, h.y);
     }
 }
-__device__ __forceinline__ void store_path(PathRec<double>* P, uint32_t q, const PathState<double>& s) {
-    PathRec<double>& p = P[q];
+__device__ __forceinline__ void store_path(PathRec* P, uint32_t q, const PathState& s) {
+    PathRec& p = P[q];
     p.a = make_double2(s.ray.o.x, s.ray.o.y);
     p.b = make_double2(s.ray.o.z, s.ray.d.x);
     p.c = make_double2(s.ray.d.y, s.ray.d.z);
@@ -76,20 +46,18 @@ __device__ __forceinline__ void store_path(PathRec<double>* P, uint32_t q, const
     p.g = make_double2(s.T.z, s.L.x);
     p.h = make_double2(s.L.y, s.L.z);
 }
-__device__ __forceinline__ void store_rng(PathRec<double>* P, uint32_t q, uint64_t rng) {
+__device__ __forceinline__ void store_rng(PathRec* P, uint32_t q, uint64_t rng) {
     P[q].e.y = __longlong_as_double(static_cast<long long>(rng));
 }
 
-template <class R>
 struct HitRecD {  // extend -> shade hand-off, 16 B
-    R t;
+    double t;
     uint32_t prim, obj;
 };
+static_assert(sizeof(HitRecD) == 16, "HitRecD is 16 B");
 
-template <class R> struct ResRec;  // final per-slot radiance
-template <> struct ResRec<float> { float4 v; };
-template <> struct ResRec<double> { double x, y, z; };  // 24 B, unpadded: k_accum streams these at HBM rate
-__device__ __forceinline__ void store_res(ResRec<float>* res, uint32_t q, V3<float> L) { res[q].v = make_float4(L.x, L.y, L.z, 0.0f); }
+struct ResRec { double x, y, z; };  // final per-slot radiance; 24 B, unpadded: k_accum streams these at HBM rate
+static_assert(sizeof(ResRec) == 24, "ResRec is 24 B");
 // NT: non-temporal stores (read once, by k_accum after the pass), so the records do not evict k_paths' L2-resident
 // camera-ray rings.  Measured (r5c, profiles/r5c_write_traffic.txt, HBM bytes per segment vs the 24-B records' own):
 // each 8-B non-temporal store reaches HBM as its own partial write, 2.0x the record bytes (Next-Week final: 12.6 B
@@ -100,7 +68,7 @@ __device__ __forceinline__ void store_res(ResRec<float>* res, uint32_t q, V3<flo
 // not all in LDS (LM 0 / 2) store non-temporally after all: there the temporal records evict the L2-resident nodes
 // and leaf triangles (capsule +1.7 %, cow +0.8 %, profiles/r6i_ab_res_nt.txt).
 template <bool NT = true>
-__device__ __forceinline__ void store_res(ResRec<double>* res, uint32_t q, V3<double> L) {
+__device__ __forceinline__ void store_res(ResRec* res, uint32_t q, V3 L) {
     if constexpr (NT) {
         __builtin_nontemporal_store(L.x, &res[q].x);
         __builtin_nontemporal_store(L.y, &res[q].y);
@@ -111,11 +79,7 @@ __device__ __forceinline__ void store_res(ResRec<double>* res, uint32_t q, V3<do
         res[q].z = L.z;
     }
 }
-__device__ __forceinline__ void load_res(const ResRec<float>* res, uint32_t q, double& r, double& g, double& b) {
-    const float4 v = res[q].v;
-    r = v.x; g = v.y; b = v.z;
-}
-__device__ __forceinline__ void load_res(const ResRec<double>* res, uint32_t q, double& r, double& g, double& b) {
+__device__ __forceinline__ void load_res(const ResRec* res, uint32_t q, double& r, double& g, double& b) {
     r = res[q].x; g = res[q].y; b = res[q].z;
 }
 
@@ -172,11 +136,10 @@ struct PassGeom {
     // npix_pad = k then, and the persistent kernels take P = list[-1] * k and nlist = list[-1] at their start
     uint32_t list_mode;
 };
-template <class R>
 struct Work {
-    PathRec<R>* paths;
-    HitRecD<R>* hits;
-    ResRec<R>* res;
+    PathRec* paths;
+    HitRecD* hits;
+    ResRec* res;
     uint32_t* active[2];        // extend input of depth d: active[d & 1], kShards x cap
     uint32_t* mq;               // material queues: (m * kShards + s) * cap
     uint32_t* counters;         // [(depth * kQueueKinds + kind) * kShards + shard] * kCounterStride
@@ -184,8 +147,7 @@ struct Work {
     double* acc;                // local pixels * 3
     void* pool;                 // k_paths path pools: the paths a batch displaces, kPoolCap PoolRays per wave (path_pool.h)
 };
-template <class R>
-__host__ __device__ __forceinline__ uint32_t* counter(const Work<R>& w, int d, int kind, int s) {
+__host__ __device__ __forceinline__ uint32_t* counter(const Work& w, int d, int kind, int s) {
     return w.counters + (static_cast<size_t>((d * kQueueKinds + kind) * kShards + s)) * kCounterStride;
 }
 
@@ -231,8 +193,7 @@ __device__ __forceinline__ void wave_append(bool pred, uint32_t val, uint32_t* s
 
 // Appends every lane with mtype in [0, kNumMatTypes) to its material queue (this wave's shard) with ONE vector atomic:
 // lane m reserves the slots of material m, so the wave pays one atomic round trip instead of one per material.
-template <class R>
-__device__ __forceinline__ void append_by_material(int mtype, uint32_t q, const Work<R>& w, const PassGeom& g, int d, int shard) {
+__device__ __forceinline__ void append_by_material(int mtype, uint32_t q, const Work& w, const PassGeom& g, int d, int shard) {
     uint64_t masks[kNumMatTypes];
     uint64_t any = 0;
 #pragma unroll
@@ -289,35 +250,33 @@ __device__ __forceinline__ int find_segment(const uint32_t* pre, int n, uint32_t
 // ------------------------------------------------------------------------------------------------ camera rays, shading
 // engine.h:58-68 + camera.h:38-47 for sample j of the pass at local pixel (lx, ly) (slot_split).
 // Runs inside the depth-0 extend: the camera ray never round-trips through HBM.
-template <class R>
-__device__ __forceinline__ void cam_ray(const PassGeom& g, const CameraRec<R>& cam, uint32_t j, int lx, int ly, Ray<R>& ray, uint64_t& rng_out) {
+__device__ __forceinline__ void cam_ray(const PassGeom& g, const CameraRec& cam, uint32_t j, int lx, int ly, Ray& ray, uint64_t& rng_out) {
     const int gy = global_row(g, ly);
     const uint32_t pixel = static_cast<uint32_t>(gy) * static_cast<uint32_t>(g.W) + static_cast<uint32_t>(lx);
     uint64_t rng = splitmix64(((static_cast<uint64_t>(pixel) << 32) | (g.sample_base + j)) ^ g.seed_mix);  // == pcg_seed(g.seed, ...)
-    const R ru = uniform<R>(rng);
-    const R rv = uniform<R>(rng);
-    const R s = div_rcp(R(lx) + ru, R(g.W - 1), static_cast<R>(g.inv_w1));  // == (lx + ru) / (W - 1), same bits
-    const R t = div_rcp(R(g.H - 1 - gy) + rv, R(g.H - 1), static_cast<R>(g.inv_h1));
-    V3<R> p;
+    const double ru = uniform(rng);
+    const double rv = uniform(rng);
+    const double s = div_rcp(static_cast<double>(lx) + ru, static_cast<double>(g.W - 1), g.inv_w1);  // == (lx + ru) / (W - 1), same bits
+    const double t = div_rcp(static_cast<double>(g.H - 1 - gy) + rv, static_cast<double>(g.H - 1), g.inv_h1);
+    V3 p;
     for (;;) {  // random_in_unit_disk (vec3.h:137-143): x, then y
-        p.x = uniform_pm1<R>(rng);
-        p.y = uniform_pm1<R>(rng);
-        p.z = R(0);
-        if (len2(p) >= R(1)) continue;
+        p.x = uniform_pm1(rng);
+        p.y = uniform_pm1(rng);
+        p.z = 0.0;
+        if (len2(p) >= 1.0) continue;
         break;
     }
-    const V3<R> rd = cam.lens_radius * p;
-    const V3<R> offset = rd.x * ld3(cam.u) + rd.y * ld3(cam.v);
+    const V3 rd = cam.lens_radius * p;
+    const V3 offset = rd.x * ld3(cam.u) + rd.y * ld3(cam.v);
     ray.o = ld3(cam.origin) + offset;
     ray.d = ld3(cam.llc) + s * ld3(cam.horizontal) + t * ld3(cam.vertical) - ld3(cam.origin) - offset;
-    ray.tm = uniform<R>(rng, cam.time0, cam.time1);
+    ray.tm = uniform(rng, cam.time0, cam.time1);
     rng_out = rng;
 }
-template <class R>
-__device__ __forceinline__ void gen_ray(const PassGeom& g, const CameraRec<R>& cam, uint32_t j, int lx, int ly, PathState<R>& st) {
+__device__ __forceinline__ void gen_ray(const PassGeom& g, const CameraRec& cam, uint32_t j, int lx, int ly, PathState& st) {
     cam_ray(g, cam, j, lx, ly, st.ray, st.rng);
-    st.T = mk(R(1), R(1), R(1));
-    st.L = mk(R(0), R(0), R(0));
+    st.T = mk(1.0, 1.0, 1.0);
+    st.L = mk(0.0, 0.0, 0.0);
 }
 
 // material.h scatter() for one hit of material type M (compile time: one shade kernel per material type, so a wave
@@ -326,39 +285,39 @@ __device__ __forceinline__ void gen_ray(const PassGeom& g, const CameraRec<R>& c
 //   pre    the lane's random_in_unit_sphere() draw (coop_unit_sphere);
 //   unitv  unit_vector of that draw (lambertian) or of the ray direction (metal, dielectric);
 //   texc   the material's texture value at the hit (lambertian, isotropic).
-template <class R, uint32_t M, uint32_t TF>
-__device__ __forceinline__ bool scatter(const DevScene<R>& S, const MatRec<R>& m, const Surf<R>& s, PathState<R>& st, V3<R>& att, V3<R>& dir,
-                                        const V3<R>* pre = nullptr, const V3<R>* unitv = nullptr, const V3<R>* texc = nullptr) {
+template <uint32_t M, uint32_t TF>
+__device__ __forceinline__ bool scatter(const DevScene& S, const MatRec& m, const Surf& s, PathState& st, V3& att, V3& dir,
+                                        const V3* pre = nullptr, const V3* unitv = nullptr, const V3* texc = nullptr) {
     if (M == MAT_LAMBERTIAN) {  // material.h:20-43
-        const V3<R> rv = unitv ? *unitv : unit(pre ? *pre : in_unit_sphere<R>(st.rng));
+        const V3 rv = unitv ? *unitv : unit(pre ? *pre : in_unit_sphere(st.rng));
         dir = s.n + rv;
         if (near_zero(dir)) dir = s.n;
-        att = texc ? *texc : mat_tex_value<R, TF>(S, m, s.u, s.v, s.p);
+        att = texc ? *texc : mat_tex_value<TF>(S, m, s.u, s.v, s.p);
         return true;
     } else if (M == MAT_METAL) {  // material.h:45-61
-        const V3<R> reflected = reflect(unitv ? *unitv : unit(st.ray.d), s.n);
-        dir = reflected + m.fuzz * (pre ? *pre : in_unit_sphere<R>(st.rng));
+        const V3 reflected = reflect(unitv ? *unitv : unit(st.ray.d), s.n);
+        dir = reflected + m.fuzz * (pre ? *pre : in_unit_sphere(st.rng));
         att = ld3(m.albedo);
-        return dot(dir, s.n) > R(0);
+        return dot(dir, s.n) > 0.0;
     } else if (M == MAT_DIELECTRIC) {  // material.h:63-99
-        att = mk(R(1), R(1), R(1));
-        const R ratio = s.ff ? (R(1) / m.ir) : m.ir;
-        const V3<R> ud = unitv ? *unitv : unit(st.ray.d);
-        const R cos_theta = fmin(dot(-ud, s.n), R(1));
-        const R sin_theta = sqrt_rn(R(1) - cos_theta * cos_theta);
-        const bool cannot = ratio * sin_theta > R(1);
+        att = mk(1.0, 1.0, 1.0);
+        const double ratio = s.ff ? (1.0 / m.ir) : m.ir;
+        const V3 ud = unitv ? *unitv : unit(st.ray.d);
+        const double cos_theta = fmin(dot(-ud, s.n), 1.0);
+        const double sin_theta = sqrt_rn(1.0 - cos_theta * cos_theta);
+        const bool cannot = ratio * sin_theta > 1.0;
         bool refl = cannot;
         if (!cannot) {
-            R r0 = (R(1) - ratio) / (R(1) + ratio);
+            double r0 = (1.0 - ratio) / (1.0 + ratio);
             r0 = r0 * r0;
-            const R refl_p = r0 + (R(1) - r0) * pow5(R(1) - cos_theta);
-            refl = refl_p > uniform<R>(st.rng);
+            const double refl_p = r0 + (1.0 - r0) * pow5(1.0 - cos_theta);
+            refl = refl_p > uniform(st.rng);
         }
         dir = refl ? reflect(ud, s.n) : refract(ud, s.n, ratio);
         return true;
     } else if (M == MAT_ISOTROPIC) {  // material.h:120-135
-        dir = pre ? *pre : in_unit_sphere<R>(st.rng);
-        att = texc ? *texc : mat_tex_value<R, TF>(S, m, s.u, s.v, s.p);
+        dir = pre ? *pre : in_unit_sphere(st.rng);
+        att = texc ? *texc : mat_tex_value<TF>(S, m, s.u, s.v, s.p);
         return true;
     }
     return false;  // diffuse_light (material.h:106-110)
@@ -367,23 +326,22 @@ __device__ __forceinline__ bool scatter(const DevScene<R>& S, const MatRec<R>& m
 // Emission + scatter of one hit of the fused extend variant, read entirely from the LDS scene image: the surface
 // (sphere.h:57-63 via the slot's centre/radius/motion planes, which are the f64 values the hit test used) and the
 // material (the image's shading table, layout.h) -- no dependent global loads after a hit.  The arithmetic and the
-// draws are those of prim_surface + scatter<R, M, kTexBasic> (tex_value of a solid or solid/solid checker texture).
+// draws are those of prim_surface + scatter<M, kTexBasic> (tex_value of a solid or solid/solid checker texture).
 // Returns true when the path continues (st then holds the scattered ray and the updated throughput).
-__device__ __forceinline__ V3<double> lds_mat_color(const uint8_t* lds, uint32_t e) {
+__device__ __forceinline__ V3 lds_mat_color(const uint8_t* lds, uint32_t e) {
     const double2* m = reinterpret_cast<const double2*>(lds + kLdsOffMat) + 2 * e;
     const double2 a = m[0], b = m[1];
     return mk(a.x, a.y, b.x);
 }
 // pre_ps: the lane's random_in_unit_sphere() draw, already taken by the wave (coop_unit_sphere) when non-null.
-__device__ __forceinline__ bool shade_hit_lds(const uint8_t* lds, uint32_t slot, uint32_t mtype, double t, bool last, PathState<double>& st,
-                                              const V3<double>* pre_ps = nullptr) {
-    using R = double;
+__device__ __forceinline__ bool shade_hit_lds(const uint8_t* lds, uint32_t slot, uint32_t mtype, double t, bool last, PathState& st,
+                                              const V3* pre_ps = nullptr) {
     const double2* sp = reinterpret_cast<const double2*>(lds + kLdsOffSph) + slot;
     const double2 a = sp[0], b = sp[kLdsSlotCap];
     const uint32_t mi = reinterpret_cast<const uint16_t*>(lds + kLdsOffMatIdx)[slot];
-    V3<R> center{a.x, a.y, b.x};
+    V3 center{a.x, a.y, b.x};
     center.y = center.y + st.ray.tm * reinterpret_cast<const double*>(lds + kLdsOffMov)[slot];  // dy = -0: static
-    Surf<R> s;
+    Surf s;
     s.p = st.ray.at(t);
     set_face_normal(s, st.ray, reinterpret_cast<const double*>(lds + kLdsOffInvR)[slot] * (s.p - center));  // (p - c) / r
     const uint32_t e = mi & ~kLdsMatChecker;
@@ -399,11 +357,11 @@ __device__ __forceinline__ bool shade_hit_lds(const uint8_t* lds, uint32_t slot,
     // lambertian, of the ray direction for metal and dielectric), so the wave runs one rejection loop and one
     // sqrt + divide sequence instead of one per material present.
     const bool lamb = mtype == MAT_LAMBERTIAN;
-    V3<R> ps = mk(R(0), R(0), R(0));
+    V3 ps = mk(0.0, 0.0, 0.0);
     if (pre_ps) ps = *pre_ps;
-    else if (mtype != MAT_DIELECTRIC) ps = in_unit_sphere<R>(st.rng);
-    const V3<R> u = unit(lamb ? ps : st.ray.d);
-    V3<R> att, dir;
+    else if (mtype != MAT_DIELECTRIC) ps = in_unit_sphere(st.rng);
+    const V3 u = unit(lamb ? ps : st.ray.d);
+    V3 att, dir;
     if (lamb) {  // material.h:20-43
         dir = s.n + u;
         if (near_zero(dir)) dir = s.n;
@@ -413,22 +371,22 @@ __device__ __forceinline__ bool shade_hit_lds(const uint8_t* lds, uint32_t slot,
         const double2 ma = m[0], mb = m[1];
         dir = reflect(u, s.n) + mb.y * ps;
         att = mk(ma.x, ma.y, mb.x);
-        if (!(dot(dir, s.n) > R(0))) return false;
+        if (!(dot(dir, s.n) > 0.0)) return false;
     } else {  // dielectric, material.h:63-99
         // the table entry holds (1 / ir, r0 of the front face, r0 of the back face, ir), each computed on the host by
         // the same IEEE operations material.h:74 and :93-94 apply (lds_scene_image): no division per hit
         const double2* me = reinterpret_cast<const double2*>(lds + kLdsOffMat) + 2 * e;
         const double2 m0 = me[0], m1 = me[1];
-        att = mk(R(1), R(1), R(1));
-        const R ratio = s.ff ? m0.x : m1.y;  // front_face ? (1.0 / ir) : ir
-        const R cos_theta = fmin(dot(-u, s.n), R(1));
-        const R sin_theta = sqrt_rn(R(1) - cos_theta * cos_theta);
-        const bool cannot = ratio * sin_theta > R(1);
+        att = mk(1.0, 1.0, 1.0);
+        const double ratio = s.ff ? m0.x : m1.y;  // front_face ? (1.0 / ir) : ir
+        const double cos_theta = fmin(dot(-u, s.n), 1.0);
+        const double sin_theta = sqrt_rn(1.0 - cos_theta * cos_theta);
+        const bool cannot = ratio * sin_theta > 1.0;
         bool refl = cannot;
         if (!cannot) {
-            const R r0 = s.ff ? m0.y : m1.x;  // ((1 - ratio) / (1 + ratio))^2
-            const R refl_p = r0 + (R(1) - r0) * pow5(R(1) - cos_theta);
-            refl = refl_p > uniform<R>(st.rng);
+            const double r0 = s.ff ? m0.y : m1.x;  // ((1 - ratio) / (1 + ratio))^2
+            const double refl_p = r0 + (1.0 - r0) * pow5(1.0 - cos_theta);
+            refl = refl_p > uniform(st.rng);
         }
         dir = refl ? reflect(u, s.n) : refract(u, s.n, ratio);
     }
@@ -494,9 +452,9 @@ constexpr size_t kJumpBytes = sizeof(JumpEntry) * kJumpEntries;
 // path requires a world of at most kPathsWorldCap objects (lds_scene_image; after world merging the benchmark scene
 // has one).
 constexpr uint32_t kPathsWorldCap = 16;
-constexpr size_t kPathsWorldBytes = sizeof(int32_t) * kPathsWorldCap + sizeof(ObjRec<double>) * kPathsWorldCap;
+constexpr size_t kPathsWorldBytes = sizeof(int32_t) * kPathsWorldCap + sizeof(ObjRec) * kPathsWorldCap;
 __host__ __device__ constexpr size_t paths_lds_head(uint32_t stack) {
-    return ((kLdsImageBytes + paths_stack_bytes(stack) + kJumpBytes + sizeof(CameraRec<double>) + sizeof(PassGeom)) + 15u) & ~size_t(15);
+    return ((kLdsImageBytes + paths_stack_bytes(stack) + kJumpBytes + sizeof(CameraRec) + sizeof(PassGeom)) + 15u) & ~size_t(15);
 }
 __host__ __device__ constexpr size_t paths_lds_bytes(uint32_t stack) { return paths_lds_head(stack) + kPathsWorldBytes; }
 

@@ -44,7 +44,7 @@ public:
     Renderer& operator=(const Renderer&) = delete;
     // Uploads the scene to the device now (render and trace_rays otherwise do it at their first call).
     void upload();
-    void render(const CameraRec<double>& cam, const RenderParams& p, uint8_t* out_rgb, double* out_acc, RenderStats& stats);
+    void render(const CameraRec& cam, const RenderParams& p, uint8_t* out_rgb, double* out_acc, RenderStats& stats);
     // Closest hit of n rays (rays: n x {ox, oy, oz, dx, dy, dz, tm}) through the renderer's traversal: t (inf on a
     // miss) and the face normal (n x 3), host buffers; global_scene forces the HBM traversal on an LDS-image scene.
     void trace_rays(const double* rays, size_t n, bool global_scene, double* t_out, double* n_out);
@@ -56,11 +56,11 @@ public:
                     double* hits, uint8_t* occluded);
     // First-hit guide buffers of the local rows (k_guides): 10 doubles per pixel {albedo, normal, position, t} and,
     // when rays_out is non-NULL, the 7 doubles of every pixel-centre ray; host buffers, or device ones with RT_OUT_DEVICE.
-    void render_guides(const CameraRec<double>& cam, const RenderParams& p, double* guides, double* rays_out);
+    void render_guides(const CameraRec& cam, const RenderParams& p, double* guides, double* rays_out);
     // Noise-target rendering (rt_render_noise_target): p.spp is the per-pixel cap; every local pixel is traced until the
     // test of noise_target.hip retires it.  out_acc (3 f64), out_count (int32) and out_moments ({S1, S2} f64) per local
     // pixel are optional; host buffers, or device ones with RT_OUT_DEVICE.
-    void render_noise_target(const CameraRec<double>& cam, const RenderParams& p, const NoiseParams& np, uint8_t* out_rgb, double* out_acc,
+    void render_noise_target(const CameraRec& cam, const RenderParams& p, const NoiseParams& np, uint8_t* out_rgb, double* out_acc,
                              int32_t* out_count, double* out_moments, RenderStats& stats, NoiseResult& result);
     int device() const;
     size_t scene_bytes() const;

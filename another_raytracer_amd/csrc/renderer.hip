@@ -19,7 +19,7 @@ struct Renderer::Impl {
     int num_cu = 256;
     hipStream_t own_stream = nullptr;
     FlatScene flat;
-    DeviceScene<double> s64;
+    DeviceScene s64;
     bool up64 = false;
     // workspace (grow-only)
     void* ws = nullptr;
@@ -84,7 +84,7 @@ const FlatScene& Renderer::flat() const { return impl_->flat; }
 // What rt_render (render_impl) and rt_render_noise_target share.
 // The geometry of the nrows local rows (band_local_rows) in 8x8-tile order; the per-pass fields (k, sample_base, P,
 // live, cap, chunk, the pixel list) are the caller's.
-static PassGeom make_pass_geom(const RenderParams& p, int nrows, const DeviceScene<double>& ds) {
+static PassGeom make_pass_geom(const RenderParams& p, int nrows, const DeviceScene& ds) {
     PassGeom g{};
     g.W = p.width;
     g.H = p.height;
@@ -124,8 +124,8 @@ static uint32_t samples_per_pass(const Renderer::Impl& I, const RenderParams& p,
 }
 static size_t al(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }  // workspace offsets: 256-B aligned
 // One pass of g through the scene's persistent kernel; `counter` is the pass's slot counter.
-static KernelId launch_persistent(int variant, const DeviceScene<double>& ds, const Renderer::Impl& I, hipStream_t stream, PassGeom g,
-                                  const CameraRec<double>& cam, const Work<double>& w, uint32_t* counter) {
+static KernelId launch_persistent(int variant, const DeviceScene& ds, const Renderer::Impl& I, hipStream_t stream, PassGeom g,
+                                  const CameraRec& cam, const Work& w, uint32_t* counter) {
     g.chunk = path_chunk(g.P, I.num_cu);
     if (variant == EXT_MEGA) {
         launch_paths(I.num_cu, stream, ds.view, g, cam, w, counter);
@@ -149,7 +149,7 @@ static void fill_stats(RenderStats& stats, const Renderer::Impl& I, int passes, 
     stats.primary = primary;
 }
 
-static void render_impl(Renderer::Impl& I, DeviceScene<double>& ds, const CameraRec<double>& cam, const RenderParams& p, uint8_t* out_rgb,
+static void render_impl(Renderer::Impl& I, DeviceScene& ds, const CameraRec& cam, const RenderParams& p, uint8_t* out_rgb,
                         double* out_acc, RenderStats& stats) {
     hipStream_t stream = p.stream ? static_cast<hipStream_t>(p.stream) : I.own_stream;
     for (int a = 0; a < 3; ++a) ds.view.bg[a] = p.background[a];  // engine::set_scene's background
@@ -161,7 +161,7 @@ static void render_impl(Renderer::Impl& I, DeviceScene<double>& ds, const Camera
     KernelId kid;  // the persistent kernel the passes ran (stays {0, 0, -1} for the wavefront variants)
     const bool mega = variant == EXT_MEGA || variant == EXT_MEGA_G;
     // (persistent paths keep the path state in registers: a slot is its radiance record only)
-    const size_t slot_bytes = mega ? sizeof(ResRec<double>) : sizeof(PathRec<double>) + sizeof(HitRecD<double>) + sizeof(ResRec<double>) + 4u * (2u + kNumMatTypes) + 8u;
+    const size_t slot_bytes = mega ? sizeof(ResRec) : sizeof(PathRec) + sizeof(HitRecD) + sizeof(ResRec) + 4u * (2u + kNumMatTypes) + 8u;
     // samples traced per pixel: spp, or parallel_images' 4 * (spp / 4) (engine.h:411-414)
     const bool images = (p.flags & RT_PARALLEL_IMAGES) != 0;
     const int spp_t = images ? 4 * (p.spp / 4) : p.spp;
@@ -176,9 +176,9 @@ static void render_impl(Renderer::Impl& I, DeviceScene<double>& ds, const Camera
 
     size_t off = 0;
     const size_t wf = mega ? 0u : 1u;  // wavefront-only buffers
-    const size_t o_paths = off; off += wf * al(sizeof(PathRec<double>) * Pmax);
-    const size_t o_hits = off; off += wf * al(sizeof(HitRecD<double>) * Pmax);
-    const size_t o_res = off; off += al(sizeof(ResRec<double>) * Pmax);
+    const size_t o_paths = off; off += wf * al(sizeof(PathRec) * Pmax);
+    const size_t o_hits = off; off += wf * al(sizeof(HitRecD) * Pmax);
+    const size_t o_res = off; off += al(sizeof(ResRec) * Pmax);
     const size_t o_a0 = off; off += wf * al(4ull * kShards * g.cap);
     const size_t o_a1 = off; off += wf * al(4ull * kShards * g.cap);
     const size_t o_mq = off; off += wf * al(4ull * kMatSegs * g.cap);
@@ -206,10 +206,10 @@ static void render_impl(Renderer::Impl& I, DeviceScene<double>& ds, const Camera
     uint8_t* ad_f2 = ad_f1 + 4 * nsq_ws;
     uint32_t* ad_count = reinterpret_cast<uint32_t*>(base + o_adc);
 
-    Work<double> w{};
-    w.paths = reinterpret_cast<PathRec<double>*>(base + o_paths);
-    w.hits = reinterpret_cast<HitRecD<double>*>(base + o_hits);
-    w.res = reinterpret_cast<ResRec<double>*>(base + o_res);
+    Work w{};
+    w.paths = reinterpret_cast<PathRec*>(base + o_paths);
+    w.hits = reinterpret_cast<HitRecD*>(base + o_hits);
+    w.res = reinterpret_cast<ResRec*>(base + o_res);
     w.active[0] = reinterpret_cast<uint32_t*>(base + o_a0);
     w.active[1] = reinterpret_cast<uint32_t*>(base + o_a1);
     w.mq = reinterpret_cast<uint32_t*>(base + o_mq);
@@ -293,7 +293,7 @@ static void render_impl(Renderer::Impl& I, DeviceScene<double>& ds, const Camera
 #endif
     HIP_OK(hipEventRecord(I.ev[0], stream));
     HIP_OK(hipMemsetAsync(w.segments, 0, sizeof(unsigned long long), stream));
-    if (p.max_depth == 0) HIP_OK(hipMemsetAsync(w.res, 0, sizeof(ResRec<double>) * Pmax, stream));  // engine.h:451-452
+    if (p.max_depth == 0) HIP_OK(hipMemsetAsync(w.res, 0, sizeof(ResRec) * Pmax, stream));  // engine.h:451-452
     uint64_t traced = local_pix;
     uint32_t ad_counts[4] = {0, 0, 0, 0};  // the device-counted levels' entry counts (read back with the frame)
     bool dev_counted = false;
@@ -440,7 +440,7 @@ void Renderer::upload() {
 
 void Renderer::trace_rays(const double* rays, size_t n, bool global_scene, double* t_out, double* n_out) {
     upload();
-    const DeviceScene<double>& ds = impl_->s64;
+    const DeviceScene& ds = impl_->s64;
     if (n == 0) return;
     if (n > (1u << 30)) throw std::runtime_error("too many rays");
     hipStream_t st = impl_->own_stream;
@@ -461,7 +461,7 @@ void Renderer::query_rays(const double* rays, const double* t_max, size_t n, boo
                           void* stream, double* hits, uint8_t* occluded) {
     upload();
     Impl& I = *impl_;
-    const DeviceScene<double>& ds = I.s64;
+    const DeviceScene& ds = I.s64;
     if (n == 0) return;
     if (n > (1u << 30)) throw std::runtime_error("too many rays");
     hipStream_t st = (device && stream) ? static_cast<hipStream_t>(stream) : I.own_stream;
@@ -489,10 +489,10 @@ void Renderer::query_rays(const double* rays, const double* t_max, size_t n, boo
     HIP_OK(hipStreamSynchronize(st));
 }
 
-void Renderer::render_guides(const CameraRec<double>& cam, const RenderParams& p, double* guides, double* rays_out) {
+void Renderer::render_guides(const CameraRec& cam, const RenderParams& p, double* guides, double* rays_out) {
     upload();
     Impl& I = *impl_;
-    const DeviceScene<double>& ds = I.s64;
+    const DeviceScene& ds = I.s64;
     hipStream_t st = p.stream ? static_cast<hipStream_t>(p.stream) : I.own_stream;
     GuideGeom g{p.width, p.height, band_local_rows(p.height, p.band_rows, p.band_count, p.band_index), p.band_rows, p.band_count, p.band_index};
     if (g.rows == 0) return;
@@ -515,7 +515,7 @@ void Renderer::render_guides(const CameraRec<double>& cam, const RenderParams& p
     HIP_OK(hipStreamSynchronize(st));
 }
 
-void Renderer::render(const CameraRec<double>& cam, const RenderParams& p, uint8_t* out_rgb, double* out_acc, RenderStats& stats) {
+void Renderer::render(const CameraRec& cam, const RenderParams& p, uint8_t* out_rgb, double* out_acc, RenderStats& stats) {
     if (p.fp_mode != RT_FP64) throw std::runtime_error("fp_mode must be RT_FP64");
     upload();
     render_impl(*impl_, impl_->s64, cam, p, out_rgb, out_acc, stats);
@@ -528,12 +528,12 @@ void Renderer::render(const CameraRec<double>& cam, const RenderParams& p, uint8
 // has the same count.  Every sum is continued in sample order, so a pixel with n samples equals rt_render's at spp = n.
 // The host reads the 4-byte entry count back once per round: it ends the loop, and sizes g.P, path_chunk, the grids and
 // the split of a round that exceeds the pass workspace into sub-passes by sample range.
-void Renderer::render_noise_target(const CameraRec<double>& cam, const RenderParams& p, const NoiseParams& np, uint8_t* out_rgb, double* out_acc,
+void Renderer::render_noise_target(const CameraRec& cam, const RenderParams& p, const NoiseParams& np, uint8_t* out_rgb, double* out_acc,
                                    int32_t* out_count, double* out_moments, RenderStats& stats, NoiseResult& result) {
     if (p.fp_mode != RT_FP64) throw std::runtime_error("fp_mode must be RT_FP64");
     upload();
     Impl& I = *impl_;
-    DeviceScene<double>& ds = I.s64;
+    DeviceScene& ds = I.s64;
     hipStream_t stream = p.stream ? static_cast<hipStream_t>(p.stream) : I.own_stream;
     for (int a = 0; a < 3; ++a) ds.view.bg[a] = p.background[a];
     const int nrows = band_local_rows(p.height, p.band_rows, p.band_count, p.band_index);
@@ -546,14 +546,14 @@ void Renderer::render_noise_target(const CameraRec<double>& cam, const RenderPar
     if (variant != EXT_MEGA && variant != EXT_MEGA_G) throw std::runtime_error("internal: noise-target rendering needs a persistent-path kernel");
     KernelId kid;
     // samples per whole-image pass (a slot is its radiance record); not spread evenly: the base pass traces min_spp
-    const uint32_t k = samples_per_pass(I, p, g, sizeof(ResRec<double>), p.spp);
+    const uint32_t k = samples_per_pass(I, p, g, sizeof(ResRec), p.spp);
     const uint32_t Pmax = k * tile_pad;  // <= kMaxPassSlots
     g.cap = shard_cap(Pmax);
     const size_t local_pix = static_cast<size_t>(nrows) * p.width;
     const uint32_t npix = static_cast<uint32_t>(local_pix);
 
     size_t off = 0;
-    const size_t o_res = off; off += al(sizeof(ResRec<double>) * Pmax);
+    const size_t o_res = off; off += al(sizeof(ResRec) * Pmax);
     const size_t o_cnt = off; off += al(4ull * kCounterStride);
     const size_t o_seg = off; off += al(sizeof(unsigned long long));
     const size_t o_acc = off; off += al(sizeof(double) * 3 * local_pix);
@@ -567,8 +567,8 @@ void Renderer::render_noise_target(const CameraRec<double>& cam, const RenderPar
     const size_t o_pool = off; off += al(pool_bytes(variant, I.num_cu));
     char* base = static_cast<char*>(I.workspace(off));
 
-    Work<double> w{};
-    w.res = reinterpret_cast<ResRec<double>*>(base + o_res);
+    Work w{};
+    w.res = reinterpret_cast<ResRec*>(base + o_res);
     w.counters = reinterpret_cast<uint32_t*>(base + o_cnt);
     w.segments = reinterpret_cast<unsigned long long*>(base + o_seg);
     w.acc = reinterpret_cast<double*>(base + o_acc);
@@ -610,7 +610,7 @@ void Renderer::render_noise_target(const CameraRec<double>& cam, const RenderPar
 
     HIP_OK(hipEventRecord(I.ev[0], stream));
     HIP_OK(hipMemsetAsync(w.segments, 0, sizeof(unsigned long long), stream));
-    if (p.max_depth == 0) HIP_OK(hipMemsetAsync(w.res, 0, sizeof(ResRec<double>) * Pmax, stream));
+    if (p.max_depth == 0) HIP_OK(hipMemsetAsync(w.res, 0, sizeof(ResRec) * Pmax, stream));
     HIP_OK(hipMemsetAsync(w.acc, 0, sizeof(double) * 3 * local_pix, stream));
     HIP_OK(hipMemsetAsync(mom, 0, sizeof(double) * 2 * local_pix, stream));
     HIP_OK(hipMemsetAsync(flag, 0, local_pix, stream));

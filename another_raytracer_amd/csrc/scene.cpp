@@ -704,7 +704,7 @@ struct Compiler {
         switch (n.type) {
             case N_SPHERE:
             case N_MOVING_SPHERE: {
-                SphereRec<double> s{};
+                SphereRec s{};
                 for (int a = 0; a < 3; ++a) s.c[a] = n.a[a];
                 s.r = n.r;
                 s.mat = static_cast<uint32_t>(n.mat);
@@ -719,7 +719,7 @@ struct Compiler {
                 return make_primref(PRIM_SPHERE, static_cast<uint32_t>(f.spheres.size() - 1));
             }
             case N_TRIANGLE: {
-                TriRec<double> t{};
+                TriRec t{};
                 for (int a = 0; a < 3; ++a) {
                     t.p[a] = n.a[a];
                     t.p[3 + a] = n.b[a];
@@ -730,12 +730,12 @@ struct Compiler {
                 return make_primref(PRIM_TRIANGLE, static_cast<uint32_t>(f.tris.size() - 1));
             }
             case N_RECT: {
-                RectRec<double> r{n.a0, n.a1, n.b0, n.b1, n.k, static_cast<uint32_t>(n.axis), static_cast<uint32_t>(n.mat)};
+                RectRec r{n.a0, n.a1, n.b0, n.b1, n.k, static_cast<uint32_t>(n.axis), static_cast<uint32_t>(n.mat)};
                 f.rects.push_back(r);
                 return make_primref(PRIM_RECT, static_cast<uint32_t>(f.rects.size() - 1));
             }
             case N_BOX: {
-                BoxRec<double> b{};
+                BoxRec b{};
                 for (int a = 0; a < 3; ++a) {
                     b.mn[a] = n.a[a];
                     b.mx[a] = n.b[a];
@@ -761,7 +761,7 @@ struct Compiler {
             throw std::runtime_error("instances and media inside a bvh/list below the top level are not supported");
         }
     }
-    int add_obj(const ObjRec<double>& o) {
+    int add_obj(const ObjRec& o) {
         f.objs.push_back(o);
         return static_cast<int>(f.objs.size()) - 1;
     }
@@ -771,7 +771,7 @@ struct Compiler {
         std::vector<AABBd> boxes;
         for (int it : items) gather(it, refs, boxes);
         int depth = 0, stack = 0;
-        ObjRec<double> o{};
+        ObjRec o{};
         o.kind = OBJ_BVH;
         // Hoisted primitives (layout.h ObjRec): a primitive whose box is as large as the whole BVH's (the random
         // scene's r = 1000 ground sphere, scene_manager.cpp:18) is met by nearly every ray, so it leaves the tree and
@@ -806,7 +806,7 @@ struct Compiler {
                 out = slab;
                 return true;
             }
-            const TriRec<double>& t = f.tris[primref_index(ref)];
+            const TriRec& t = f.tris[primref_index(ref)];
             Vec3 poly[8], next[8];
             int np = 3;
             for (int v = 0; v < 3; ++v) poly[v] = Vec3(t.p[3 * v], t.p[3 * v + 1], t.p[3 * v + 2]);
@@ -857,7 +857,7 @@ struct Compiler {
     }
     int obj(int idx) {
         const Node& n = g.nodes[idx];
-        ObjRec<double> o{};
+        ObjRec o{};
         if (is_prim(n.type)) {
             AABBd b;
             o.kind = OBJ_PRIM;
@@ -983,7 +983,7 @@ FlatScene compile_scene(const SceneGraph& g) {
         return false;
     };
     for (const Material& m : g.materials) {
-        MatRec<double> r{};
+        MatRec r{};
         r.type = m.type;
         r.tex = m.tex;
         r.flags = uses_uv(m.tex) ? MATF_NEEDS_UV : 0u;
@@ -993,7 +993,7 @@ FlatScene compile_scene(const SceneGraph& g) {
         f.mats.push_back(r);
     }
     for (const Texture& t : g.textures) {
-        TexRec<double> r{};
+        TexRec r{};
         r.type = t.type;
         r.even = t.even;
         r.odd = t.odd;
@@ -1005,7 +1005,7 @@ FlatScene compile_scene(const SceneGraph& g) {
         f.texs.push_back(r);
     }
     for (const Perlin& p : g.perlins) {
-        PerlinRec<double> r{};
+        PerlinRec r{};
         for (int i = 0; i < 256; ++i)
             for (int a = 0; a < 3; ++a) r.ranvec[i][a] = p.ranvec[i][a];
         for (int k = 0; k < 3; ++k)
@@ -1030,7 +1030,7 @@ FlatScene compile_scene(const SceneGraph& g) {
     for (const auto& o : f.objs) {
         if (o.kind == OBJ_TRANSLATE || o.kind == OBJ_ROTATE_Y) f.features |= F_XFORM;
         if (o.kind == OBJ_MEDIUM) {
-            const ObjRec<double>& b = f.objs[o.a];
+            const ObjRec& b = f.objs[o.a];
             if (!(b.kind == OBJ_PRIM && primref_type(static_cast<uint32_t>(b.a)) == PRIM_SPHERE)) f.features |= F_MEDIA_G;
         }
     }
@@ -1038,7 +1038,7 @@ FlatScene compile_scene(const SceneGraph& g) {
     return f;
 }
 
-CameraRec<double> make_camera(const double lookfrom[3], const double lookat[3], const double vup_[3], double vfov, double aspect,
+CameraRec make_camera(const double lookfrom[3], const double lookat[3], const double vup_[3], double vfov, double aspect,
                               double aperture, double focus_dist, double time0, double time1) {
     // camera.h:8-36, the reference's own operation order.
     Vec3 from(lookfrom[0], lookfrom[1], lookfrom[2]), at(lookat[0], lookat[1], lookat[2]), vup(vup_[0], vup_[1], vup_[2]);
@@ -1052,7 +1052,7 @@ CameraRec<double> make_camera(const double lookfrom[3], const double lookat[3], 
     Vec3 horizontal = focus_dist * vw * u;
     Vec3 vertical = focus_dist * vh * v;
     Vec3 llc = from - horizontal / 2 - vertical / 2 - focus_dist * w;
-    CameraRec<double> c{};
+    CameraRec c{};
     for (int a = 0; a < 3; ++a) {
         c.origin[a] = from[a];
         c.llc[a] = llc[a];

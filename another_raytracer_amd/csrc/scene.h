@@ -152,17 +152,17 @@ uint64_t reference_bvh_nodes(uint64_t n);
 
 // ---------------------------------------------------------------------------------------------- compiled scene
 struct FlatScene {
-    std::vector<SphereRec<double>> spheres;
-    std::vector<TriRec<double>> tris;
-    std::vector<RectRec<double>> rects;
-    std::vector<BoxRec<double>> boxes;
+    std::vector<SphereRec> spheres;
+    std::vector<TriRec> tris;
+    std::vector<RectRec> rects;
+    std::vector<BoxRec> boxes;
     std::vector<uint32_t> primrefs;      // leaf ranges of all BVHs
     std::vector<BvhNode> nodes;
-    std::vector<ObjRec<double>> objs;
+    std::vector<ObjRec> objs;
     std::vector<int32_t> world;          // top-level objects, in hittable_list order
-    std::vector<MatRec<double>> mats;
-    std::vector<TexRec<double>> texs;
-    std::vector<PerlinRec<double>> perlins;
+    std::vector<MatRec> mats;
+    std::vector<TexRec> texs;
+    std::vector<PerlinRec> perlins;
     std::vector<ImageRec> images;
     std::vector<uint8_t> texels;
     double background[3] = {0, 0, 0};
@@ -174,7 +174,7 @@ struct FlatScene {
 FlatScene compile_scene(const SceneGraph& g);
 
 // camera.h:8-36 in f64 (the reference's own arithmetic).
-CameraRec<double> make_camera(const double lookfrom[3], const double lookat[3], const double vup[3], double vfov, double aspect,
+CameraRec make_camera(const double lookfrom[3], const double lookat[3], const double vup[3], double vfov, double aspect,
                               double aperture, double focus_dist, double time0, double time1);
 
 }  // namespace art

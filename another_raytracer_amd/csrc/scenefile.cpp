@@ -35,9 +35,9 @@ struct FileHeader {
 
 template <class T>
 constexpr uint32_t rec() { return static_cast<uint32_t>(sizeof(T)); }
-const uint32_t kRecordBytes[kArrays] = {rec<SphereRec<double>>(), rec<TriRec<double>>(), rec<RectRec<double>>(), rec<BoxRec<double>>(),
-                                        rec<uint32_t>(),          rec<BvhNode>(),        rec<ObjRec<double>>(),  rec<int32_t>(),
-                                        rec<MatRec<double>>(),    rec<TexRec<double>>(), rec<PerlinRec<double>>(), rec<ImageRec>(),
+const uint32_t kRecordBytes[kArrays] = {rec<SphereRec>(), rec<TriRec>(), rec<RectRec>(), rec<BoxRec>(),
+                                        rec<uint32_t>(),          rec<BvhNode>(),        rec<ObjRec>(),  rec<int32_t>(),
+                                        rec<MatRec>(),    rec<TexRec>(), rec<PerlinRec>(), rec<ImageRec>(),
                                         rec<uint8_t>()};
 
 uint64_t fnv1a(const uint8_t* p, size_t n) {
@@ -156,7 +156,7 @@ void validate(const std::string& path, FlatScene& f) {
     uint32_t feat = (nsph ? F_SPHERE : 0u) | (ntri ? F_TRI : 0u) | (nrect ? F_RECT : 0u) | (nbox ? F_BOX : 0u);
     std::vector<int> chain(nobj, 0);
     for (size_t k = 0; k < nobj; ++k) {
-        const ObjRec<double>& o = f.objs[k];
+        const ObjRec& o = f.objs[k];
         switch (o.kind) {
             case OBJ_PRIM:
                 if (!ref_ok(static_cast<uint32_t>(o.a))) bad(path, "primitive object out of range");
@@ -180,7 +180,7 @@ void validate(const std::string& path, FlatScene& f) {
             case OBJ_MEDIUM: {
                 if (o.a < 0 || static_cast<size_t>(o.a) >= k) bad(path, "medium boundary out of range");
                 if (o.b < 0 || static_cast<size_t>(o.b) >= nmat) bad(path, "medium phase material out of range");
-                const ObjRec<double>& b = f.objs[o.a];
+                const ObjRec& b = f.objs[o.a];
                 if (b.kind == OBJ_MEDIUM) bad(path, "medium boundary is a medium");
                 if (!(b.kind == OBJ_PRIM && primref_type(static_cast<uint32_t>(b.a)) == PRIM_SPHERE)) feat |= F_MEDIA_G;
                 f.has_media = true;

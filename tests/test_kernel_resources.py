@@ -93,3 +93,25 @@ def test_lm1_code16_kernels_do_not_spill(ks):
     assert (189, 15, 1) in pg  # the final scene's kernel (scene 8: all features, all textures, LDS BVH)
     spills = {key: k.get(".vgpr_spill_count", 0) for key, k in pg.items() if key[2] == 1 and key[0] & F_CODE16}
     assert spills and all(v <= SPILL_ALLOWED.get(key, 0) for key, v in spills.items()), spills
+
+
+def test_kernel_identity_pairs_kernels_by_name_and_template_arguments():
+    """tools/kernel_identity.py pairs the kernels of two builds by name and template arguments: a leading scalar-type
+    argument and the parameter list do not tell kernels apart, any other template argument does."""
+    from kernel_identity import pair_key
+
+    tail = "NS_8PassGeomENS_9CameraRec{0}ENS_4Work{0}EPj"
+    with_scalar = "_ZN3art9k_paths_gILj167ELj3ELi2EEEvNS_8DevSceneIdEE" + tail.format("IdE")
+    without = "_ZN3art9k_paths_gILj167ELj3ELi2EEEvNS_8DevSceneE" + tail.format("")
+    assert pair_key(with_scalar) == pair_key(without) == "art::k_paths_g<Lj167E,Lj3E,Li2E>"
+    assert pair_key("_ZN3art9k_paths_gILj167ELj3ELi1EEEvNS_8DevSceneE" + tail.format("")) != pair_key(without)
+    # k_accum<double>(PassGeom, Work<double>) against the plain function k_accum(PassGeom, Work)
+    assert pair_key("_ZN3art7k_accumIdEEvNS_8PassGeomENS_4WorkIT_EE") == pair_key("_ZN3art7k_accumENS_8PassGeomENS_4WorkE") == "art::k_accum"
+    assert pair_key("_ZN3art7k_accumENS_8PassGeomENS_4WorkE") != pair_key("_ZN3art14k_accum_imagesENS_8PassGeomENS_4WorkEPdj")
+    # a scalar type leads k_extend<double, 1, true, false>'s arguments; the others stay
+    assert pair_key("_ZN3art8k_extendIdLj1ELb1ELb0EEEvNS_8DevSceneIT_EE") == pair_key("_ZN3art8k_extendILj1ELb1ELb0EEEvNS_8DevSceneE")
+    a16 = "_ZN3art12_GLOBAL__N_111k_dn_atrousILi16EEEviiPKdS3_S3_PdS4_ddi"
+    a1 = "_ZN3art12_GLOBAL__N_111k_dn_atrousILi1EEEviiPKdS3_S3_PdS4_ddi"
+    lds1 = "_ZN3art12_GLOBAL__N_115k_dn_atrous_ldsILi1EEEviiPKdS3_S3_PdS4_ddi"
+    assert len({pair_key(a16), pair_key(a1), pair_key(lds1)}) == 3
+    assert pair_key("_ZN3art14k_unpack_bandsEPKhPhiiiiii") == "art::k_unpack_bands"

@@ -20,7 +20,7 @@
 __global__ void k_log(double* ocml, double* restated, uint32_t n) {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
-    const double x = static_cast<double>(k) * 0x1p-24;  // the uniform<double> value of the kernels (device.h)
+    const double x = static_cast<double>(k) * 0x1p-24;  // the uniform() value of the kernels (device.h)
     ocml[k] = log(x);
     restated[k] = art::glibc_log(x);
 }
