@@ -31,6 +31,7 @@ struct rt_scene {
     art::SceneView view;         // scene_manager::build's lookfrom / lookat / vfov / aperture
     int device = 0;
     std::unique_ptr<art::Renderer> renderer;  // created on first render (scene build/dump works without a GPU)
+    art::Renderer& device_renderer() { return renderer ? *renderer : *(renderer = std::make_unique<art::Renderer>(flat, device)); }
 };
 struct rt_graph {
     art::SceneGraph g;
@@ -294,9 +295,8 @@ int rt_render(rt_scene* s, const rt_camera* cam, const rt_params* p, uint8_t* ou
         if (out_accum) return fail(RT_E_INVALID, "adaptive mode has no per-pixel radiance sums: out_accum must be NULL");
     }
     return guard(RT_E_DEVICE, [&] {
-        if (!s->renderer) s->renderer = std::make_unique<art::Renderer>(s->flat, s->device);
         art::RenderStats st;
-        s->renderer->render(camera_of(cam), render_params(p), out_rgb8, out_accum, st);
+        s->device_renderer().render(camera_of(cam), render_params(p), out_rgb8, out_accum, st);
         fill_stats(st, stats);
         return RT_OK;
     });
@@ -310,13 +310,12 @@ int rt_render_progressive(rt_scene* s, const rt_camera* cam, const rt_params* p,
     if (p->flags & (RT_ADAPTIVE | RT_PARALLEL_IMAGES))
         return fail(RT_E_INVALID, "progressive rendering traces whole frames of consecutive samples (no RT_ADAPTIVE or RT_PARALLEL_IMAGES)");
     return guard(RT_E_DEVICE, [&] {
-        if (!s->renderer) s->renderer = std::make_unique<art::Renderer>(s->flat, s->device);
         art::RenderParams rp = render_params(p);
         if (rp.samples_per_pass <= 0) rp.samples_per_pass = (rp.spp + 7) / 8;
         const int spp = rp.spp;
         rp.on_pass = [&](int done) { return cb(user, done, spp, out_rgb8, out_accum) == 0; };
         art::RenderStats st;
-        s->renderer->render(camera_of(cam), rp, out_rgb8, out_accum, st);
+        s->device_renderer().render(camera_of(cam), rp, out_rgb8, out_accum, st);
         fill_stats(st, stats);
         return RT_OK;
     });
@@ -325,9 +324,8 @@ int rt_render_progressive(rt_scene* s, const rt_camera* cam, const rt_params* p,
 int rt_trace_rays(rt_scene* s, const double* rays, int64_t n, int32_t flags, double* t_out, double* normal_out) {
     if (!s || n < 0 || (n > 0 && (!rays || !t_out))) return fail(RT_E_INVALID, "scene, rays and t_out must be non-NULL, n >= 0");
     return guard(RT_E_DEVICE, [&] {
-        if (!s->renderer) s->renderer = std::make_unique<art::Renderer>(s->flat, s->device);
         std::vector<double> nrm(normal_out ? 0 : 3 * static_cast<size_t>(n));
-        s->renderer->trace_rays(rays, static_cast<size_t>(n), (flags & RT_GLOBAL_SCENE) != 0, t_out, normal_out ? normal_out : nrm.data());
+        s->device_renderer().trace_rays(rays, static_cast<size_t>(n), (flags & RT_GLOBAL_SCENE) != 0, t_out, normal_out ? normal_out : nrm.data());
         return RT_OK;
     });
 }
@@ -345,9 +343,8 @@ int rt_query_rays(rt_scene* s, const rt_query_params* q, const double* rays, con
     if (n == 0) return RT_OK;
     if (!rays) return fail(RT_E_INVALID, "rt_query_rays: rays is NULL");
     return guard(RT_E_DEVICE, [&] {
-        if (!s->renderer) s->renderer = std::make_unique<art::Renderer>(s->flat, s->device);
-        s->renderer->query_rays(rays, t_max, static_cast<size_t>(n), (q->flags & RT_OUT_DEVICE) != 0, (q->flags & RT_GLOBAL_SCENE) != 0, any_hit,
-                                (q->flags & RT_Q_NO_MEDIA) != 0, q->stream, hits, occluded);
+        s->device_renderer().query_rays(rays, t_max, static_cast<size_t>(n), (q->flags & RT_OUT_DEVICE) != 0, (q->flags & RT_GLOBAL_SCENE) != 0, any_hit,
+                                        (q->flags & RT_Q_NO_MEDIA) != 0, q->stream, hits, occluded);
         return RT_OK;
     });
 }
@@ -362,8 +359,7 @@ int rt_render_guides(rt_scene* s, const rt_camera* cam, const rt_params* p, doub
     if (!valid_params(&q, why)) return fail(RT_E_INVALID, why);
     if (p->flags & ~(RT_OUT_DEVICE | RT_GLOBAL_SCENE)) return fail(RT_E_INVALID, "rt_render_guides takes RT_OUT_DEVICE and RT_GLOBAL_SCENE only");
     return guard(RT_E_DEVICE, [&] {
-        if (!s->renderer) s->renderer = std::make_unique<art::Renderer>(s->flat, s->device);
-        s->renderer->render_guides(camera_of(cam), render_params(&q), guides, rays_out);
+        s->device_renderer().render_guides(camera_of(cam), render_params(&q), guides, rays_out);
         return RT_OK;
     });
 }
@@ -422,7 +418,7 @@ int rt_render_denoised(rt_scene* s, const rt_camera* cam, const rt_params* p, co
     if (!d.stream) d.stream = p->stream;
     return guard(RT_E_DEVICE, [&] {
         const auto t0 = std::chrono::steady_clock::now();
-        if (!s->renderer) s->renderer = std::make_unique<art::Renderer>(s->flat, s->device);
+        art::Renderer& renderer = s->device_renderer();
         const art::DenoiseFrame fb = art::denoise_reserve(s->device, p->width, p->height);
         art::RenderParams rp = render_params(p);
         rp.spp = p->spp / 2;
@@ -430,11 +426,11 @@ int rt_render_denoised(rt_scene* s, const rt_camera* cam, const rt_params* p, co
         art::RenderStats st[2];
         for (int half = 0; half < 2; ++half) {
             rp.seed = p->seed + static_cast<uint64_t>(half);
-            s->renderer->render(camera_of(cam), rp, nullptr, half ? fb.accum_b : fb.accum_a, st[half]);
+            renderer.render(camera_of(cam), rp, nullptr, half ? fb.accum_b : fb.accum_a, st[half]);
         }
         art::RenderParams gp = rp;
         gp.flags = RT_OUT_DEVICE | (p->flags & RT_GLOBAL_SCENE);
-        s->renderer->render_guides(camera_of(cam), gp, fb.guides, nullptr);
+        renderer.render_guides(camera_of(cam), gp, fb.guides, nullptr);
         art::denoise_reserved(s->device, d, rp.spp, out_color, out_rgb8, (p->flags & RT_OUT_DEVICE) != 0, nullptr);
         art::RenderStats sum = st[1];
         sum.segments += st[0].segments;
@@ -475,10 +471,9 @@ int rt_render_noise_target(rt_scene* s, const rt_camera* cam, const rt_params* p
     if (np.dilate && p->band_count > 1)
         return fail(RT_E_INVALID, "dilate = 1 needs the whole frame (band_count 1): a pixel's 3x3 neighbourhood would depend on the partition");
     return guard(RT_E_DEVICE, [&] {
-        if (!s->renderer) s->renderer = std::make_unique<art::Renderer>(s->flat, s->device);
         art::RenderStats st;
         art::NoiseResult nr;
-        s->renderer->render_noise_target(camera_of(cam), render_params(p), np, out_rgb8, out_accum, out_count, out_moments, st, nr);
+        s->device_renderer().render_noise_target(camera_of(cam), render_params(p), np, out_rgb8, out_accum, out_count, out_moments, st, nr);
         fill_stats(st, stats);
         if (result) {
             result->rounds = nr.rounds;

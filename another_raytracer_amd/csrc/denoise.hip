@@ -16,6 +16,7 @@
 #include "denoise.h"
 #include "hip_check.h"
 #include "options.h"
+#include "workspace.h"
 
 namespace art {
 namespace {
@@ -265,38 +266,13 @@ void dn_allow_lds(const void* kernel, size_t lds) {
     d = true;
 }
 
-// Per-device state: a grow-only workspace under the renderer's rule (the old buffer is released before the larger one
-// is allocated, a refused growth leaves {nullptr, 0}; option test.fault_workspace_bytes refuses growth beyond N bytes as
-// a failed hipMalloc would), a stream and two events.  It lives until the process ends.
+// Per-device state: the grow-only workspace (workspace.h, with the test.fault_workspace_bytes fault point), a stream and
+// two events.  It lives until the process ends.
 struct DnDevice {
     std::mutex mtx;  // one denoise call at a time per device
-    void* ws = nullptr;
-    size_t ws_bytes = 0;
+    DeviceBuffer ws{true};
     hipStream_t own_stream = nullptr;
     hipEvent_t ev[2] = {nullptr, nullptr};
-
-    void* workspace(size_t bytes) {
-        const double lim = opt(Opt::FaultWorkspaceBytes);
-        if (bytes > ws_bytes) {
-            if (lim > 0 && static_cast<double>(bytes) > lim) {
-                if (ws) (void)hipFree(ws);
-                ws = nullptr;
-                ws_bytes = 0;
-                throw std::runtime_error("workspace allocation of " + std::to_string(bytes) + " bytes refused (test.fault_workspace_bytes)");
-            }
-            if (ws) {
-                void* old = ws;
-                ws = nullptr;
-                ws_bytes = 0;
-                HIP_OK(hipFree(old));
-            }
-            void* p = nullptr;
-            HIP_OK(hipMalloc(&p, bytes));
-            ws = p;
-            ws_bytes = bytes;
-        }
-        return ws;
-    }
 };
 DnDevice& dn_device(int device) {
     static std::mutex mtx;
@@ -309,37 +285,38 @@ DnDevice& dn_device(int device) {
     return *d;
 }
 
-// Workspace layout of a W x H frame.  The frame part (inputs, result) is used when the caller's buffers are host
-// memory and by rt_render_denoised; it comes first, so a reserved frame stays where it is.
+// Workspace layout of a W x H frame over `base`.  The frame part (inputs, result) is used when the caller's buffers are
+// host memory and by rt_render_denoised; it comes first, so a reserved frame stays where it is.
 struct DnLayout {
-    size_t o_a, o_b, o_g, o_out, o_rgb, o_l0, o_l1, o_v0, o_v1, o_gp, total;
+    double *a, *b, *g, *out;
+    uint8_t* rgb;
+    double *L[2], *V[2], *G;  // G: normal, position, t planes
+    size_t total;
 };
-DnLayout dn_layout(size_t npix, bool frame) {
-    auto al = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
+DnLayout dn_layout(void* base, size_t npix, bool frame) {
+    Carver c(base);
     DnLayout l{};
-    size_t off = 0;
-    const size_t f = frame ? 1u : 0u;
-    l.o_a = off; off += f * al(sizeof(double) * 3 * npix);
-    l.o_b = off; off += f * al(sizeof(double) * 3 * npix);
-    l.o_g = off; off += f * al(sizeof(double) * kGuide * npix);
-    l.o_out = off; off += f * al(sizeof(double) * 3 * npix);
-    l.o_rgb = off; off += f * al(3 * npix);
-    l.o_l0 = off; off += al(sizeof(double) * 3 * npix);
-    l.o_l1 = off; off += al(sizeof(double) * 3 * npix);
-    l.o_v0 = off; off += al(sizeof(double) * npix);
-    l.o_v1 = off; off += al(sizeof(double) * npix);
-    l.o_gp = off; off += al(sizeof(double) * 7 * npix);  // normal, position, t planes
-    l.total = off;
+    l.a = c.take<double>(3 * npix, frame);
+    l.b = c.take<double>(3 * npix, frame);
+    l.g = c.take<double>(kGuide * npix, frame);
+    l.out = c.take<double>(3 * npix, frame);
+    l.rgb = c.take<uint8_t>(3 * npix, frame);
+    for (auto& p : l.L) p = c.take<double>(3 * npix);
+    for (auto& p : l.V) p = c.take<double>(npix);
+    l.G = c.take<double>(7 * npix);
+    l.total = c.total();
     return l;
+}
+// The layout in D's workspace, grown to hold it.
+DnLayout dn_workspace(DnDevice& D, size_t npix, bool frame) {
+    return dn_layout(D.ws.reserve(dn_layout(nullptr, npix, frame).total), npix, frame);
 }
 
 // prepare -> iterations x a-trous (L / V ping-pong) -> finish, on `st`; all pointers are device memory.
-void run_filter(DnDevice& D, hipStream_t st, const DenoiseParams& p, char* base, const DnLayout& l, const double* d_a, const double* d_b, int spp_each,
+void run_filter(DnDevice& D, hipStream_t st, const DenoiseParams& p, const DnLayout& l, const double* d_a, const double* d_b, int spp_each,
                 const double* d_g, double* d_out, uint8_t* d_rgb) {
     const uint32_t n = static_cast<uint32_t>(static_cast<size_t>(p.width) * p.height);
-    double* L[2] = {reinterpret_cast<double*>(base + l.o_l0), reinterpret_cast<double*>(base + l.o_l1)};
-    double* V[2] = {reinterpret_cast<double*>(base + l.o_v0), reinterpret_cast<double*>(base + l.o_v1)};
-    double* G = reinterpret_cast<double*>(base + l.o_gp);
+    double *const *L = l.L, *const *V = l.V, *G = l.G;
     const int demod = p.demodulate ? 1 : 0;
     for (auto& e : D.ev)
         if (!e) HIP_OK(hipEventCreate(&e));
@@ -392,22 +369,16 @@ void denoise(int device, const DenoiseParams& p, const double* accum_a, const do
     HIP_OK(hipSetDevice(device));
     hipStream_t st = dn_stream(D, p);
     const size_t npix = static_cast<size_t>(p.width) * p.height;
-    const DnLayout l = dn_layout(npix, !device_ptrs);
-    char* base = static_cast<char*>(D.workspace(l.total));
+    const DnLayout l = dn_workspace(D, npix, !device_ptrs);
     if (device_ptrs) {
-        run_filter(D, st, p, base, l, accum_a, accum_b, spp_each, guides, out_color, out_rgb8);
+        run_filter(D, st, p, l, accum_a, accum_b, spp_each, guides, out_color, out_rgb8);
     } else {
-        double* d_a = reinterpret_cast<double*>(base + l.o_a);
-        double* d_b = reinterpret_cast<double*>(base + l.o_b);
-        double* d_g = reinterpret_cast<double*>(base + l.o_g);
-        double* d_out = reinterpret_cast<double*>(base + l.o_out);
-        uint8_t* d_rgb = reinterpret_cast<uint8_t*>(base + l.o_rgb);
-        HIP_OK(hipMemcpyAsync(d_a, accum_a, sizeof(double) * 3 * npix, hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(d_b, accum_b, sizeof(double) * 3 * npix, hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(d_g, guides, sizeof(double) * kGuide * npix, hipMemcpyHostToDevice, st));
-        run_filter(D, st, p, base, l, d_a, d_b, spp_each, d_g, d_out, out_rgb8 ? d_rgb : nullptr);
-        HIP_OK(hipMemcpyAsync(out_color, d_out, sizeof(double) * 3 * npix, hipMemcpyDeviceToHost, st));
-        if (out_rgb8) HIP_OK(hipMemcpyAsync(out_rgb8, d_rgb, 3 * npix, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(l.a, accum_a, sizeof(double) * 3 * npix, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(l.b, accum_b, sizeof(double) * 3 * npix, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(l.g, guides, sizeof(double) * kGuide * npix, hipMemcpyHostToDevice, st));
+        run_filter(D, st, p, l, l.a, l.b, spp_each, l.g, l.out, out_rgb8 ? l.rgb : nullptr);
+        HIP_OK(hipMemcpyAsync(out_color, l.out, sizeof(double) * 3 * npix, hipMemcpyDeviceToHost, st));
+        if (out_rgb8) HIP_OK(hipMemcpyAsync(out_rgb8, l.rgb, 3 * npix, hipMemcpyDeviceToHost, st));
     }
     HIP_OK(hipStreamSynchronize(st));
     elapsed(D, ms);
@@ -417,9 +388,8 @@ DenoiseFrame denoise_reserve(int device, int width, int height) {
     DnDevice& D = dn_device(device);
     std::lock_guard<std::mutex> lock(D.mtx);
     HIP_OK(hipSetDevice(device));
-    const DnLayout l = dn_layout(static_cast<size_t>(width) * height, true);
-    char* base = static_cast<char*>(D.workspace(l.total));
-    return DenoiseFrame{reinterpret_cast<double*>(base + l.o_a), reinterpret_cast<double*>(base + l.o_b), reinterpret_cast<double*>(base + l.o_g)};
+    const DnLayout l = dn_workspace(D, static_cast<size_t>(width) * height, true);
+    return DenoiseFrame{l.a, l.b, l.g};
 }
 
 void denoise_reserved(int device, const DenoiseParams& p, int spp_each, double* out_color, uint8_t* out_rgb8, bool device_ptrs, double* ms) {
@@ -428,16 +398,12 @@ void denoise_reserved(int device, const DenoiseParams& p, int spp_each, double* 
     HIP_OK(hipSetDevice(device));
     hipStream_t st = dn_stream(D, p);
     const size_t npix = static_cast<size_t>(p.width) * p.height;
-    const DnLayout l = dn_layout(npix, true);
-    if (D.ws_bytes < l.total) throw std::runtime_error("internal: denoise_reserved without denoise_reserve");
-    char* base = static_cast<char*>(D.ws);
-    double* d_out = reinterpret_cast<double*>(base + l.o_out);
-    uint8_t* d_rgb = reinterpret_cast<uint8_t*>(base + l.o_rgb);
-    run_filter(D, st, p, base, l, reinterpret_cast<double*>(base + l.o_a), reinterpret_cast<double*>(base + l.o_b), spp_each,
-               reinterpret_cast<double*>(base + l.o_g), d_out, out_rgb8 ? d_rgb : nullptr);
+    const DnLayout l = dn_layout(D.ws.data(), npix, true);
+    if (D.ws.size() < l.total) throw std::runtime_error("internal: denoise_reserved without denoise_reserve");
+    run_filter(D, st, p, l, l.a, l.b, spp_each, l.g, l.out, out_rgb8 ? l.rgb : nullptr);
     const hipMemcpyKind kind = device_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (out_color) HIP_OK(hipMemcpyAsync(out_color, d_out, sizeof(double) * 3 * npix, kind, st));
-    if (out_rgb8) HIP_OK(hipMemcpyAsync(out_rgb8, d_rgb, 3 * npix, kind, st));
+    if (out_color) HIP_OK(hipMemcpyAsync(out_color, l.out, sizeof(double) * 3 * npix, kind, st));
+    if (out_rgb8) HIP_OK(hipMemcpyAsync(out_rgb8, l.rgb, 3 * npix, kind, st));
     HIP_OK(hipStreamSynchronize(st));
     elapsed(D, ms);
 }

@@ -17,6 +17,7 @@
 #include "hip_check.h"
 #include "multi.h"
 #include "options.h"
+#include "workspace.h"
 
 namespace art {
 
@@ -69,31 +70,18 @@ void unpack_bands(const uint8_t* recv, uint8_t* frame, int W, int H, int band_ro
         }
 }
 
-struct DeviceBuf {
+struct DeviceBuf {  // a grow-only buffer (workspace.h) that makes its device current before it allocates or frees
     int device = 0;
-    void* p = nullptr;
-    size_t bytes = 0;
+    DeviceBuffer buf;
+    void* p() const { return buf.data(); }
     void ensure(size_t want) {
-        if (want <= bytes) return;
+        if (want <= buf.size()) return;
         HIP_OK(hipSetDevice(device));
-        if (p) {
-            void* old = p;
-            p = nullptr;
-            bytes = 0;
-            HIP_OK(hipFree(old));
-        }
-        void* q = nullptr;
-        HIP_OK(hipMalloc(&q, want));
-        p = q;
-        bytes = want;
+        buf.reserve(want);
     }
     void release() {
-        if (p) {
-            (void)hipSetDevice(device);
-            (void)hipFree(p);
-        }
-        p = nullptr;
-        bytes = 0;
+        if (buf.data()) (void)hipSetDevice(device);
+        buf.release();
     }
 };
 
@@ -326,7 +314,7 @@ void MultiRenderer::render(const CameraRec& cam, const RenderParams& p, uint8_t*
                 pk.band_index = k;
                 pk.flags |= RT_OUT_DEVICE;
                 pk.stream = nullptr;  // the renderer's own stream on its device
-                I.renderers[k]->render(cam, pk, static_cast<uint8_t*>(I.send[k].p), nullptr, st[k]);
+                I.renderers[k]->render(cam, pk, static_cast<uint8_t*>(I.send[k].p()), nullptr, st[k]);
                 rms[k] = std::chrono::duration<double, std::milli>(clock::now() - a).count();
             } catch (...) {
                 err[k] = std::current_exception();
@@ -354,7 +342,7 @@ void MultiRenderer::render(const CameraRec& cam, const RenderParams& p, uint8_t*
         RcclGroup group;
         for (int k = 0; k < n; ++k) {
             HIP_OK(hipSetDevice(I.devices[k]));
-            RCCL_ISSUE(ncclGather(I.send[k].p, k == 0 ? I.recv.p : nullptr, block, ncclUint8, 0, I.comms[k], I.streams[k]));
+            RCCL_ISSUE(ncclGather(I.send[k].p(), k == 0 ? I.recv.p() : nullptr, block, ncclUint8, 0, I.comms[k], I.streams[k]));
             if (k == n - 1 && opt(Opt::FaultRcclGroup) == 2)  // fault point (tests): an error inside the gather group
                 throw std::runtime_error("ncclGather: injected failure inside the group (test.fault_rccl_group = 2)");
         }
@@ -377,9 +365,9 @@ void MultiRenderer::render(const CameraRec& cam, const RenderParams& p, uint8_t*
     tm.wait_ms = std::chrono::duration<double, std::milli>(clock::now() - tw).count();
     // phase 3: the root places every row and hands the frame over
     HIP_OK(hipSetDevice(I.devices[0]));
-    uint8_t* dst = out_device ? out_rgb : static_cast<uint8_t*>(I.frame.p);
-    launch_unpack(static_cast<const uint8_t*>(I.recv.p), dst, W, H, band_rows, n, max_rows, I.streams[0]);
-    if (!out_device) HIP_OK(hipMemcpyAsync(out_rgb, I.frame.p, row_bytes * H, hipMemcpyDeviceToHost, I.streams[0]));
+    uint8_t* dst = out_device ? out_rgb : static_cast<uint8_t*>(I.frame.p());
+    launch_unpack(static_cast<const uint8_t*>(I.recv.p()), dst, W, H, band_rows, n, max_rows, I.streams[0]);
+    if (!out_device) HIP_OK(hipMemcpyAsync(out_rgb, I.frame.p(), row_bytes * H, hipMemcpyDeviceToHost, I.streams[0]));
     HIP_OK(hipEventRecord(I.ev[2], I.streams[0]));
     HIP_OK(hipStreamSynchronize(I.streams[0]));
     const auto t1 = clock::now();

@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "device.h"
+#include "pass_plan.h"
 
 namespace art {
 
@@ -93,7 +94,6 @@ constexpr int kShards = 32;
 constexpr int kCounterStride = 32;                   // words between counters (128 B)
 constexpr int kQueueKinds = 1 + kNumMatTypes;        // 0: active (extend input), 1..5: material queues
 constexpr int kMatSegs = kNumMatTypes * kShards;     // shade input segments
-constexpr uint64_t kMaxPassSlots = 1ull << 31;       // slot ids and batch offsets stay well inside u32
 // + 2 batches per material kernel: the kNumMatTypes shade launches of one depth all append to the same next-queue shards
 __host__ __device__ inline uint32_t shard_cap(uint32_t P) { return 64u * ((((P + 63u) / 64u) + kShards - 1) / kShards + 2 * kNumMatTypes); }
 
