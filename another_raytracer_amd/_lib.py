@@ -85,6 +85,11 @@ class rt_query_params(ctypes.Structure):  # zero-initialised = closest hit, host
     _fields_ = [("flags", ctypes.c_int32), ("reserved", ctypes.c_int32), ("stream", ctypes.c_void_p)]
 
 
+class rt_radiance_params(ctypes.Structure):  # zero-initialised + max_depth = host buffers, seed 0, spp 1
+    _fields_ = [("flags", ctypes.c_int32), ("spp", ctypes.c_int32), ("max_depth", ctypes.c_int32), ("sample_base", ctypes.c_uint32),
+                ("seed", ctypes.c_uint64), ("id_base", ctypes.c_uint64), ("stream", ctypes.c_void_p), ("background", ctypes.c_double * 3)]
+
+
 class rt_multi_times(ctypes.Structure):
     _fields_ = [("total_ms", ctypes.c_double), ("render_ms_max", ctypes.c_double), ("render_ms_min", ctypes.c_double),
                 ("gather_ms", ctypes.c_double), ("unpack_ms", ctypes.c_double), ("wait_ms", ctypes.c_double),
@@ -118,6 +123,8 @@ SIGNATURES = {
                                    ctypes.POINTER(rt_stats)]),
     "rt_trace_rays": (_I, [_P, _P, ctypes.c_int64, ctypes.c_int32, _P, _P]),
     "rt_query_rays": (_I, [_P, ctypes.POINTER(rt_query_params), _P, _P, ctypes.c_int64, _P, _P]),
+    "rt_radiance_rays": (_I, [_P, ctypes.POINTER(rt_radiance_params), _P, _P, ctypes.c_int64, _P, ctypes.POINTER(rt_stats)]),
+    "rt_camera_rays": (_I, [ctypes.POINTER(rt_camera), ctypes.POINTER(rt_params), ctypes.c_uint32, _I, _P, _P]),
     "rt_render_guides": (_I, [_P, ctypes.POINTER(rt_camera), ctypes.POINTER(rt_params), _P, _P]),
     "rt_denoise": (_I, [_I, ctypes.POINTER(rt_denoise_params), _P, _P, ctypes.c_int32, _P, _P, _P, _DP]),
     "rt_render_denoised": (_I, [_P, ctypes.POINTER(rt_camera), ctypes.POINTER(rt_params), ctypes.POINTER(rt_denoise_params), _P, _P,

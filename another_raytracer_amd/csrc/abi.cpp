@@ -18,6 +18,7 @@
 #include "scenefile.h"
 #include "objmesh.h"
 #include "options.h"
+#include "pass_plan.h"
 #include "scene.h"
 
 namespace art {
@@ -345,6 +346,59 @@ int rt_query_rays(rt_scene* s, const rt_query_params* q, const double* rays, con
     return guard(RT_E_DEVICE, [&] {
         s->device_renderer().query_rays(rays, t_max, static_cast<size_t>(n), (q->flags & RT_OUT_DEVICE) != 0, (q->flags & RT_GLOBAL_SCENE) != 0, any_hit,
                                         (q->flags & RT_Q_NO_MEDIA) != 0, q->stream, hits, occluded);
+        return RT_OK;
+    });
+}
+
+int rt_radiance_rays(rt_scene* s, const rt_radiance_params* q, const double* rays, const uint64_t* rng, int64_t n, double* radiance,
+                     rt_stats* stats) {
+    if (!s || !q) return fail(RT_E_INVALID, "rt_radiance_rays: scene and params must be non-NULL");
+    if (n < 0 || n > (int64_t(1) << 30)) return fail(RT_E_INVALID, "rt_radiance_rays: n must be in [0, 2^30]");
+    if (q->flags & ~(RT_OUT_DEVICE | RT_GLOBAL_SCENE)) return fail(RT_E_INVALID, "rt_radiance_rays takes RT_OUT_DEVICE and RT_GLOBAL_SCENE only");
+    if (q->spp < 0) return fail(RT_E_INVALID, "rt_radiance_rays: spp must be >= 1 (0 is taken as 1)");
+    if (q->max_depth < 1) return fail(RT_E_INVALID, "rt_radiance_rays: max_depth must be >= 1");
+    if (q->stream && !(q->flags & RT_OUT_DEVICE)) return fail(RT_E_INVALID, "rt_radiance_rays: stream needs RT_OUT_DEVICE (host buffers run on the scene's own stream)");
+    const int64_t spp = q->spp > 0 ? q->spp : 1;
+    if (static_cast<uint64_t>(n) * static_cast<uint64_t>(spp) > art::kMaxPassSlots)
+        return fail(RT_E_INVALID, "rt_radiance_rays: n * spp = " + std::to_string(n * spp) + " exceeds kMaxPassSlots = 2^31 paths per call: chunk the "
+                                  "rays with id_base, or the samples with sample_base");
+    if (!rng && (q->id_base > (uint64_t(1) << 32) || q->id_base + static_cast<uint64_t>(n) > (uint64_t(1) << 32)))
+        return fail(RT_E_INVALID, "rt_radiance_rays: id_base + n must be <= 2^32 (stream ids are 32 bits)");
+    if (n == 0) return RT_OK;
+    if (!rays || !radiance) return fail(RT_E_INVALID, "rt_radiance_rays: rays and radiance must be non-NULL");
+    return guard(RT_E_DEVICE, [&] {
+        art::RadianceParams rp;
+        rp.spp = static_cast<int>(spp), rp.max_depth = q->max_depth, rp.sample_base = q->sample_base;
+        rp.seed = q->seed, rp.id_base = rng ? 0 : q->id_base;
+        rp.device = (q->flags & RT_OUT_DEVICE) != 0, rp.global_scene = (q->flags & RT_GLOBAL_SCENE) != 0;
+        rp.stream = q->stream;
+        for (int c = 0; c < 3; ++c) rp.background[c] = q->background[c];
+        art::RenderStats st;
+        s->device_renderer().radiance_rays(rp, rays, rng, static_cast<size_t>(n), radiance, stats ? &st : nullptr);
+        if (stats) {
+            fill_stats(st, stats);
+            stats->extend_variant = stats->kernel_lds_mode = -1;  // neither an extend variant nor a k_paths_g instantiation
+        }
+        return RT_OK;
+    });
+}
+
+int rt_camera_rays(const rt_camera* cam, const rt_params* p, uint32_t sample_base, int device, double* rays_out, uint64_t* rng_out) {
+    std::string why;
+    if (!cam || !rays_out) return fail(RT_E_INVALID, "rt_camera_rays: camera and rays_out must be non-NULL");
+    if (!p) return fail(RT_E_INVALID, "params is NULL");
+    if (device < 0) return fail(RT_E_INVALID, "device must be >= 0");
+    rt_params q = *p;  // max_depth, samples_per_pass and background are ignored
+    q.max_depth = 0;
+    if (!valid_params(&q, why)) return fail(RT_E_INVALID, why);
+    if (p->flags & ~RT_OUT_DEVICE) return fail(RT_E_INVALID, "rt_camera_rays takes RT_OUT_DEVICE only");
+    if (p->stream && !(p->flags & RT_OUT_DEVICE)) return fail(RT_E_INVALID, "rt_camera_rays: stream needs RT_OUT_DEVICE");
+    const uint64_t rows = static_cast<uint64_t>(art::band_local_rows(p->height, p->band_rows, p->band_count, p->band_index));
+    const uint64_t npix_pad = static_cast<uint64_t>((p->width + 7) / 8) * ((rows + 7) / 8) * 64u;  // 8x8 tiles, as rt_render's slots
+    if (npix_pad * static_cast<uint64_t>(p->spp) > art::kMaxPassSlots)
+        return fail(RT_E_INVALID, "rt_camera_rays: padded local pixels * spp exceeds kMaxPassSlots = 2^31 per call: fewer samples per call, with sample_base");
+    return guard(RT_E_DEVICE, [&] {
+        art::Renderer::camera_rays(device, camera_of(cam), render_params(&q), sample_base, rays_out, rng_out);
         return RT_OK;
     });
 }

@@ -3,5 +3,6 @@
 #include "kernels.hip"
 #include "k_paths.hip"
 #include "k_paths_g_mesh.hip"
+#include "radiance_rays.hip"
 #include "device_scene.hip"
 #include "renderer.hip"

@@ -43,6 +43,27 @@ void launch_occlude_rays(const DeviceScene& ds, bool global_scene, hipStream_t s
                          uint8_t* occluded);
 void launch_guides(const DeviceScene& ds, int flags, hipStream_t st, const GuideGeom& g, const CameraRec& cam, double* guides,
                    double* rays);
+// radiance_rays.hip
+// One rt_radiance_rays call as its kernels see it.  Path p = i * spp + s (ray i, sample s) of P = n * spp <= kMaxPassSlots.
+struct RadianceJob {
+    const double* rays;            // n x 7
+    const uint64_t* rng;           // P PCG states, or null: pcg_seed(seed, id_base + i, sample_base + s)
+    double* radiance;              // n x 3; written by k_radiance_rays itself when res is null (spp == 1)
+    ResRec* res;                   // P per-path records for k_radiance_sum (spp > 1), or null
+    uint32_t* next;                // the claim counter, zeroed before the launch
+    unsigned long long* segments;  // zeroed before the launch
+    uint32_t P, spp, chunk;        // chunk: paths per claim (path_chunk)
+    uint32_t sample_base, id_base;
+    uint32_t stack;                // LDS traversal stack rows per lane (stack_rows)
+    int32_t max_depth;
+    uint64_t seed_mix;             // splitmix64(seed), as PassGeom::seed_mix
+    FastDiv fd_spp;                // / spp
+};
+// The persistent path kernel over the job's paths with `background` on a miss (flags: RT_GLOBAL_SCENE), then the per-ray
+// sums when job.res is set.
+void launch_radiance_rays(const DeviceScene& ds, int flags, int num_cu, hipStream_t st, const RadianceJob& job, uint32_t n, const double background[3]);
+// rt_camera_rays: entry (ly * W + lx) * g.k + j = cam_ray of local pixel (lx, ly), sample g.sample_base + j (rng may be null)
+void launch_camera_rays(hipStream_t st, const PassGeom& g, const CameraRec& cam, double* rays, uint64_t* rng);
 // k_paths.hip
 void launch_paths(int num_cu, hipStream_t st, const DevScene& S, const PassGeom& g, const CameraRec& cam, const Work& w,
                   uint32_t* next_slot);

@@ -35,6 +35,15 @@ struct RenderStats {
     int kernel_lds_mode = -1;
 };
 
+struct RadianceParams {  // rt_radiance_params, checked (art.h)
+    int spp = 1, max_depth = 50;
+    uint32_t sample_base = 0;
+    uint64_t seed = 0, id_base = 0;
+    bool device = false, global_scene = false;
+    void* stream = nullptr;
+    double background[3] = {0, 0, 0};
+};
+
 class Renderer {
 public:
     struct Impl;
@@ -54,6 +63,15 @@ public:
     // Host buffers: workspace, copies and a wait, as trace_rays.
     void query_rays(const double* rays, const double* t_max, size_t n, bool device, bool global_scene, bool any_hit, bool no_media, void* stream,
                     double* hits, uint8_t* occluded);
+    // rt_radiance_rays: radiance[i] = the in-order f64 sum of p.spp paths from ray i (rng: n * spp PCG states, or null).
+    // device: the four buffers are device pointers used in place on `stream` (null: the scene's own, and the call waits);
+    // the claim counter and the per-path records come from the workspace either way.  stats (may be null: then a device
+    // call on the caller's stream returns once enqueued) receives segments, primary and ms.
+    void radiance_rays(const RadianceParams& p, const double* rays, const uint64_t* rng, size_t n, double* radiance, RenderStats* stats);
+    // rt_camera_rays: cam_ray (path_work.h) of every local pixel of p's frame and band partition, samples
+    // [sample_base, sample_base + p.spp), entry (ly * W + lx) * p.spp + j; host buffers, or device ones on `device` with
+    // RT_OUT_DEVICE (p.stream; null: the default stream).  rng_out may be null.  Needs no scene.  Blocking.
+    static void camera_rays(int device, const CameraRec& cam, const RenderParams& p, uint32_t sample_base, double* rays_out, uint64_t* rng_out);
     // First-hit guide buffers of the local rows (k_guides): 10 doubles per pixel {albedo, normal, position, t} and,
     // when rays_out is non-NULL, the 7 doubles of every pixel-centre ray; host buffers, or device ones with RT_OUT_DEVICE.
     void render_guides(const CameraRec& cam, const RenderParams& p, double* guides, double* rays_out);

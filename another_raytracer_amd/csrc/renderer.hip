@@ -1,5 +1,6 @@
 // renderer.hip — Renderer (renderer.h): the workspace, the pass loops of rt_render and rt_render_noise_target, ray
-// queries and guide buffers.  Host code only: every kernel is launched through launch.h / noise_target.h.
+// queries, radiance along caller-given rays, camera rays and guide buffers.  Host code only: every kernel is launched
+// through launch.h / noise_target.h.
 //
 // The workspace is one grow-only DeviceBuffer that every entry point carves (workspace.h).  rt_render and
 // rt_render_noise_target share a Frame: begin_frame sets it up (geometry, variant, the samples per pass of pass_plan.h,
@@ -62,7 +63,7 @@ const FlatScene& Renderer::flat() const { return impl_->flat; }
 // What rt_render (render_impl) and rt_render_noise_target share.
 // The geometry of the nrows local rows (band_local_rows) in 8x8-tile order; the per-pass fields (k, sample_base, P,
 // live, cap, chunk, the pixel list) are the caller's.
-static PassGeom make_pass_geom(const RenderParams& p, int nrows, const DeviceScene& ds) {
+static PassGeom make_pass_geom(const RenderParams& p, int nrows, uint32_t stack) {
     PassGeom g{};
     g.W = p.width;
     g.H = p.height;
@@ -82,7 +83,7 @@ static PassGeom make_pass_geom(const RenderParams& p, int nrows, const DeviceSce
     g.fd_npix = FastDiv::make(g.npix_pad);
     g.inv_w1 = 1.0 / static_cast<double>(p.width - 1);
     g.inv_h1 = 1.0 / static_cast<double>(p.height - 1);
-    g.stack = stack_rows(ds.max_stack);
+    g.stack = stack;
     return g;
 }
 // The wavefront variants' queue counters: a line per depth (at least 4: the device-counted adaptive levels take one each)
@@ -195,7 +196,7 @@ static bool begin_frame(Frame& f, RenderStats& stats, int spp, bool spread, int 
     f.nrows = band_local_rows(p.height, p.band_rows, p.band_count, p.band_index);
     stats.local_rows = f.nrows;
     if (f.nrows == 0) return false;
-    f.g = make_pass_geom(p, f.nrows, f.ds);
+    f.g = make_pass_geom(p, f.nrows, stack_rows(f.ds.max_stack));
     f.variant = extend_variant(f.ds, p.flags);
     f.mega = f.variant == EXT_MEGA || f.variant == EXT_MEGA_G;
     const size_t slot_bytes = f.mega ? sizeof(ResRec) : sizeof(PathRec) + sizeof(HitRecD) + sizeof(ResRec) + 4u * (2u + kNumMatTypes) + 8u;
@@ -520,6 +521,96 @@ void Renderer::render_guides(const CameraRec& cam, const RenderParams& p, double
         if (rays_out) HIP_OK(hipMemcpyAsync(rays_out, d_r, r_b, hipMemcpyDeviceToHost, st));
     }
     HIP_OK(hipStreamSynchronize(st));
+}
+
+void Renderer::radiance_rays(const RadianceParams& p, const double* rays, const uint64_t* rng, size_t n, double* radiance, RenderStats* stats) {
+    upload();
+    Impl& I = *impl_;
+    const DeviceScene& ds = I.s64;
+    if (n == 0) return;
+    const uint32_t spp = static_cast<uint32_t>(std::max(1, p.spp));
+    const uint64_t P = static_cast<uint64_t>(n) * spp;
+    if (n > (1u << 30) || P > kMaxPassSlots) throw std::runtime_error("too many rays or paths");
+    hipStream_t st = (p.device && p.stream) ? static_cast<hipStream_t>(p.stream) : I.own_stream;
+    // workspace: the claim counter's line, the segment count, the per-path records (spp > 1) and, for host buffers,
+    // the device copies of the caller's
+    RadianceJob job{};
+    double *d_rays = nullptr, *d_rad = nullptr;
+    uint64_t* d_rng = nullptr;
+    auto carve = [&](Carver& c) {
+        job.next = c.take<uint32_t>(kCounterStride);
+        job.segments = c.take<unsigned long long>(1);
+        job.res = c.take<ResRec>(P, spp > 1);
+        d_rays = c.take<double>(7 * n, !p.device);
+        d_rng = c.take<uint64_t>(P, !p.device && rng);
+        d_rad = c.take<double>(3 * n, !p.device);
+    };
+    Carver size(nullptr);
+    carve(size);
+    Carver parts(I.ws.reserve(size.total()));
+    carve(parts);
+    if (spp == 1) job.res = nullptr;
+    job.rays = p.device ? rays : d_rays;
+    job.rng = !rng ? nullptr : (p.device ? rng : d_rng);
+    job.radiance = p.device ? radiance : d_rad;
+    job.P = static_cast<uint32_t>(P), job.spp = spp, job.chunk = path_chunk(job.P, I.num_cu);
+    job.sample_base = p.sample_base, job.id_base = static_cast<uint32_t>(p.id_base);
+    job.stack = stack_rows(ds.max_stack);
+    job.max_depth = p.max_depth;
+    job.seed_mix = splitmix64(p.seed);
+    job.fd_spp = FastDiv::make(spp);
+    if (stats)
+        for (auto& e : I.ev)
+            if (!e) HIP_OK(hipEventCreate(&e));
+    if (!p.device) {
+        HIP_OK(hipMemcpyAsync(d_rays, rays, sizeof(double) * 7 * n, hipMemcpyHostToDevice, st));
+        if (rng) HIP_OK(hipMemcpyAsync(d_rng, rng, sizeof(uint64_t) * P, hipMemcpyHostToDevice, st));
+    }
+    HIP_OK(hipMemsetAsync(job.next, 0, sizeof(uint32_t), st));
+    HIP_OK(hipMemsetAsync(job.segments, 0, sizeof(unsigned long long), st));
+    if (stats) HIP_OK(hipEventRecord(I.ev[0], st));
+    launch_radiance_rays(ds, p.global_scene ? RT_GLOBAL_SCENE : 0, I.num_cu, st, job, static_cast<uint32_t>(n), p.background);
+    HIP_OK(hipGetLastError());
+    if (stats) HIP_OK(hipEventRecord(I.ev[1], st));
+    if (!p.device) HIP_OK(hipMemcpyAsync(radiance, d_rad, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, st));
+    unsigned long long segs = 0;
+    if (stats) HIP_OK(hipMemcpyAsync(&segs, job.segments, sizeof segs, hipMemcpyDeviceToHost, st));
+    // a device call on the caller's stream without stats returns here, enqueued; every other waits
+    if (!p.device || !p.stream || stats) HIP_OK(hipStreamSynchronize(st));
+    if (stats) {
+        float ms = 0;
+        HIP_OK(hipEventElapsedTime(&ms, I.ev[0], I.ev[1]));
+        *stats = RenderStats{};
+        stats->segments = segs, stats->primary = P, stats->ms = ms;
+        stats->passes = 1, stats->samples_per_pass = static_cast<int>(spp);
+    }
+}
+
+void Renderer::camera_rays(int device, const CameraRec& cam, const RenderParams& p, uint32_t sample_base, double* rays_out, uint64_t* rng_out) {
+    HIP_OK(hipSetDevice(device));
+    const int nrows = band_local_rows(p.height, p.band_rows, p.band_count, p.band_index);
+    if (nrows == 0) return;
+    PassGeom g = make_pass_geom(p, nrows, 0);  // rt_render's geometry; no traversal, no stack
+    const uint32_t k = static_cast<uint32_t>(p.spp);
+    if (static_cast<uint64_t>(k) * g.npix_pad > kMaxPassSlots) throw std::runtime_error("too many camera rays for one call");
+    g.k = k, g.sample_base = sample_base, g.P = k * g.npix_pad;
+    const size_t ne = static_cast<size_t>(nrows) * static_cast<size_t>(p.width) * k;
+    g.live = static_cast<uint32_t>(ne);
+    if (p.flags & RT_OUT_DEVICE) {
+        hipStream_t st = static_cast<hipStream_t>(p.stream);
+        launch_camera_rays(st, g, cam, rays_out, rng_out);
+        HIP_OK(hipGetLastError());
+        if (!st) HIP_OK(hipStreamSynchronize(st));
+        return;
+    }
+    DeviceBuffer tmp;  // no scene, so no renderer workspace: freed on return
+    Carver c(tmp.reserve(sizeof(double) * 7 * ne + (rng_out ? sizeof(uint64_t) * ne : 0)), 1);
+    double* d_rays = c.take<double>(7 * ne);
+    uint64_t* d_rng = rng_out ? c.take<uint64_t>(ne) : nullptr;
+    launch_camera_rays(nullptr, g, cam, d_rays, d_rng);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpy(rays_out, d_rays, sizeof(double) * 7 * ne, hipMemcpyDeviceToHost));
+    if (rng_out) HIP_OK(hipMemcpy(rng_out, d_rng, sizeof(uint64_t) * ne, hipMemcpyDeviceToHost));
 }
 
 // Noise-target rendering (rt_render_noise_target; the kernels in noise_target.hip).  The base pass traces samples

@@ -5,6 +5,9 @@ rays through the renderer's own BVH traversal -- the closest hit with the whole 
     hits = art.query_rays(world.objects, rays)                       # (n, 12) records; hits.t, hits.point, hits.prim ...
     blocked = art.query_rays(world.objects, shadow_rays, t_max=dist, any_hit=True)   # (n,) uint8
 
+    L = art.radiance_rays(world, rays, spp=64)                       # (n, 3): the path-traced radiance sums along the rays
+    rays, rng = art.camera_rays(cam, W, H, spp)                      # the renderer's own camera rays and RNG states
+
 Buffers are numpy arrays (host path: the call copies and blocks) or contiguous float64 torch tensors on the scene's device
 (used in place, on torch's current stream, without waiting: the result tensor is ordered after the query on that stream
 like any torch operation).
@@ -13,7 +16,8 @@ import ctypes
 
 import numpy as np
 
-from ._lib import RT_GLOBAL_SCENE, RT_HIT_DOUBLES, RT_OUT_DEVICE, RT_Q_ANY_HIT, RT_Q_NO_MEDIA, check, lib, rt_query_params
+from ._lib import (RT_FP64, RT_GLOBAL_SCENE, RT_HIT_DOUBLES, RT_OUT_DEVICE, RT_Q_ANY_HIT, RT_Q_NO_MEDIA, check, lib, rt_params, rt_query_params,
+                   rt_radiance_params, rt_scene_info, rt_stats)
 from .scene import _SceneHandle, hittable_list, scene
 
 # columns of a hit record (RT_HIT_DOUBLES = 12)
@@ -137,3 +141,128 @@ def query_rays(objects, rays, t_max=None, any_hit=False, no_media=False, global_
     check(lib.rt_query_rays(handle, ctypes.byref(q), ctypes.c_void_p(rays_ptr), None if tmax_ptr is None else ctypes.c_void_p(tmax_ptr),
                             n, hits_arg, occ_arg), "query_rays")
     return out if any_hit else HitRecords(out)
+
+
+def _u64_buffer(buf, count, what, dev, device_index):
+    """Address of `count` 64-bit PCG states: a uint64 numpy array, or a torch.int64 / torch.uint64 tensor on the device."""
+    if isinstance(buf, np.ndarray):
+        if dev:
+            raise ValueError(f"{what} must be a torch tensor on the scene's device, as rays is")
+        if buf.dtype != np.uint64 or not buf.flags.c_contiguous or tuple(buf.shape) != (count,):
+            raise ValueError(f"{what} must be a C-contiguous uint64 array of shape ({count},)")
+        return buf.ctypes.data
+    if _is_tensor(buf):
+        if not dev:
+            raise ValueError(f"{what} must be a numpy array, as rays is")
+        if str(buf.dtype) not in ("torch.int64", "torch.uint64") or not buf.is_contiguous() or tuple(buf.shape) != (count,):
+            raise ValueError(f"{what} must be a contiguous int64 or uint64 tensor of shape ({count},)")
+        if buf.device.type == "cpu" or (buf.device.index or 0) != device_index:
+            raise ValueError(f"{what} must live on the scene's device (cuda:{device_index})")
+        return buf.data_ptr()
+    raise TypeError(f"{what} must be a numpy array or a torch tensor")
+
+
+def _stream_handle(stream, device):
+    """The raw hipStream_t of `stream` (a torch stream or a handle; None: torch's current stream on `device`).  The null
+    handle means "the library's own stream, and wait": torch's default stream is then drained first, so the inputs are
+    complete when the call is made."""
+    import torch
+    if stream is None:
+        stream = torch.cuda.current_stream(device)
+    handle = getattr(stream, "cuda_stream", stream)
+    if not handle:
+        torch.cuda.default_stream(device).synchronize()
+    return handle
+
+
+def radiance_rays(objects, rays, spp=1, max_depth=50, seed=0, sample_base=0, id_base=0, rng=None, background=None, global_scene=False,
+                  out=None, stream=None, stats=False):
+    """rt_radiance_rays over a compiled scene (a scene_manager().build(...) scene, its .objects, or what compile_world
+    returns): the path-traced radiance that arrives along caller-given rays -- other camera models, light probes,
+    lightmap texels, several cameras in one launch.
+
+    rays: (n, 7) float64 {ox, oy, oz, dx, dy, dz, time}.  Ray i starts spp paths; path (i, s) runs the renderer's
+    _ray_color (miss: background; diffuse_light: emission; otherwise scatter while depth + 1 < max_depth) on the PCG state
+    rng[i * spp + s] when rng is given (n * spp states: a uint64 array, or an int64 / uint64 device tensor), else on the
+    stream keyed (seed, id_base + i, sample_base + s).  Returns the (n, 3) float64 sums over the samples, in sample order
+    from +0.0 (`out`, or a new array / tensor) -- sums as engine.run's accum, not means; with stats=True, (sums, dict)
+    with segments, primary and ms.  background None: the scene's own.  Buffers are numpy arrays (the call copies and
+    blocks), or contiguous tensors on the scene's device, used in place on `stream` (a torch stream or a raw
+    hipStream_t; default: torch's current stream) -- the call then returns without waiting unless stats is asked for.
+    Calls on one scene share its workspace: order them on one stream, or synchronise between them.  With camera_rays'
+    rays and states, the in-order sum over a pixel's samples equals engine.run's accum bit for bit."""
+    if background is None and isinstance(objects, scene):
+        background = objects.background
+    handle = _native_scene(objects)
+    dev = _is_tensor(rays)
+    if not dev and not isinstance(rays, np.ndarray):
+        raise TypeError("rays must be a numpy array or a torch tensor")
+    if len(rays.shape) != 2 or int(rays.shape[1]) != 7:
+        raise ValueError("rays must have shape (n, 7): origin, direction, time")
+    n = int(rays.shape[0])
+    spp = int(spp)
+    if spp < 1:
+        raise ValueError("spp must be >= 1")
+    rays_ptr = _f64_buffer(rays, (n, 7), "rays", dev, handle.device)
+    rng_ptr = None if rng is None else _u64_buffer(rng, n * spp, "rng", dev, handle.device)
+    if out is None:
+        if dev:
+            import torch
+            out = torch.empty((n, 3), dtype=torch.float64, device=rays.device)
+        else:
+            out = np.empty((n, 3), np.float64)
+    out_ptr = _f64_buffer(out, (n, 3), "out", dev, handle.device)
+    if background is None:
+        info = rt_scene_info()
+        check(lib.rt_scene_info_get(handle, ctypes.byref(info)), "rt_scene_info_get")
+        background = tuple(info.background)
+    q = rt_radiance_params()
+    q.flags = (RT_OUT_DEVICE if dev else 0) | (RT_GLOBAL_SCENE if global_scene else 0)
+    q.spp, q.max_depth, q.sample_base, q.seed, q.id_base = spp, int(max_depth), int(sample_base), int(seed), int(id_base)
+    for c in range(3):
+        q.background[c] = float(background[c])
+    if dev:
+        q.stream = _stream_handle(stream, rays.device)
+    elif stream is not None:
+        raise ValueError("stream applies to device tensors only: the host path runs on the scene's own stream and blocks")
+    st = rt_stats()
+    check(lib.rt_radiance_rays(handle, ctypes.byref(q), ctypes.c_void_p(rays_ptr), None if rng_ptr is None else ctypes.c_void_p(rng_ptr), n,
+                               ctypes.c_void_p(out_ptr), ctypes.byref(st) if stats else None), "radiance_rays")
+    return (out, {"segments": st.segments, "primary": st.primary, "ms": st.ms}) if stats else out
+
+
+def camera_rays(cam, width, height, spp, seed=0, sample_base=0, bands=None, device=None, stream=None):
+    """rt_camera_rays: the renderer's own camera rays as data.  Returns (rays, rng): entry (ly * width + lx) * spp + j of
+    rays ((local_pixels * spp, 7) float64) and rng ((local_pixels * spp,) PCG states) holds the ray engine.run starts at
+    local pixel (lx, ly) for sample sample_base + j with `seed`, and the generator state after the camera's draws.
+    bands: (band_rows, band_count, band_index), or None for the whole frame.  device None: numpy arrays (uint64 states;
+    computed on GPU 0); a device index or torch device: tensors there (int64 states: torch's 64-bit integer type), written
+    on `stream` (default: torch's current stream) without waiting.  Needs no scene."""
+    if not hasattr(cam, "c"):
+        raise TypeError("cam must be an art.camera")
+    p = rt_params()
+    p.width, p.height, p.spp, p.seed, p.fp_mode = int(width), int(height), int(spp), int(seed), RT_FP64
+    p.band_rows, p.band_count, p.band_index = (int(height), 1, 0) if bands is None else (int(b) for b in bands)
+    rows = check(lib.rt_local_rows(ctypes.byref(p), None), "rt_local_rows")
+    if p.spp < 1:
+        raise ValueError("spp must be >= 1")
+    ne = rows * p.width * p.spp
+    if device is None:
+        if stream is not None:
+            raise ValueError("stream applies to device tensors only")
+        rays, rng = np.empty((ne, 7), np.float64), np.empty((ne,), np.uint64)
+        rays_ptr, rng_ptr, index = rays.ctypes.data, rng.ctypes.data, 0
+    else:
+        import torch
+        tdev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        if tdev.type != "cuda":
+            raise ValueError("device must be a GPU (an index or a cuda torch.device), or None for numpy arrays")
+        index = tdev.index or 0
+        rays = torch.empty((ne, 7), dtype=torch.float64, device=tdev)
+        rng = torch.empty((ne,), dtype=torch.int64, device=tdev)
+        rays_ptr, rng_ptr = rays.data_ptr(), rng.data_ptr()
+        p.flags = RT_OUT_DEVICE
+        p.stream = _stream_handle(stream, tdev)
+    check(lib.rt_camera_rays(ctypes.byref(cam.c), ctypes.byref(p), int(sample_base), index, ctypes.c_void_p(rays_ptr), ctypes.c_void_p(rng_ptr)),
+          "camera_rays")
+    return rays, rng

@@ -62,7 +62,8 @@ extern "C" {
  * Additive since ABI 5 (the version stays 5): rt_render_guides, rt_denoise, rt_render_denoised, rt_denoise_params,
  * RT_GUIDE_DOUBLES, RT_DN_NO_DEMODULATE; rt_render_noise_target, rt_noise_params, rt_noise_result; rt_query_rays,
  * rt_query_params, RT_Q_ANY_HIT, RT_Q_NO_MEDIA, RT_HIT_DOUBLES (ray queries with the hit record, a per-ray t_max, occlusion
- * queries, device buffers and a caller's stream), option query.any_sorted. */
+ * queries, device buffers and a caller's stream), option query.any_sorted; rt_radiance_rays, rt_radiance_params (path-traced
+ * radiance along caller-given rays), rt_camera_rays (the renderer's camera rays and post-camera RNG states as data). */
 #define RT_ABI_VERSION 5
 
 /* return codes */
@@ -257,6 +258,53 @@ typedef struct rt_query_params { /* zero-initialised = closest hit, host buffers
 } rt_query_params;
 int rt_query_rays(rt_scene* scene, const rt_query_params* q, const double* rays, const double* t_max, int64_t n, double* hits,
                   uint8_t* occluded);
+/* rt_radiance_rays (additive since ABI 5): the path-traced radiance that arrives along n caller-given rays (rays as
+ * rt_trace_rays takes them) -- another camera model, light probes, lightmap texels, several cameras in one launch.
+ * Paths: path (i, s), s in [0, spp), has index p = i * spp + s.  It starts at ray i with throughput 1 and runs _ray_color
+ *   (engine.h:447-466) exactly as rt_render's persistent kernels do: a miss returns throughput * background; a
+ *   diffuse_light hit returns its emission and ends the path; any other hit scatters while depth + 1 < max_depth (the
+ *   path returns 0 once max_depth segments are traced).
+ * RNG: the PCG state of path p is rng[p] when rng is given (n * spp states; seed, id_base and sample_base are then
+ *   ignored), else the stream keyed (seed, pixel id_base + i, sample sample_base + s) -- rt_render's key, with the ray's
+ *   stream id in the place of the global pixel.
+ * Output: radiance[i] = +0.0 + L(i, 0) + L(i, 1) + ..., an f64 sum in sample order -- a sum like rt_render's out_accum, not
+ *   a mean.  With rt_camera_rays (below): rt_render's out_accum of a pixel equals the in-order sum over its samples of
+ *   rt_radiance_rays of its camera rays and states, bit for bit, and the segment counts are equal.
+ * stats (may be NULL): segments counts world.hit calls as rt_render does, primary = n * spp, ms = HIP events around the
+ *   kernel launches, passes = 1, samples_per_pass = spp; the other fields are 0 (extend_variant and kernel_lds_mode -1).
+ * Limits: n <= 2^30 and n * spp <= 2^31 (kMaxPassSlots: path indices are 32 bits) per call; beyond that RT_E_INVALID.
+ *   A caller with more work chunks the rays (id_base) or the samples (sample_base).
+ * Buffers: host pointers; the call copies through the scene's workspace and blocks, as rt_query_rays.  With RT_OUT_DEVICE
+ *   rays, rng, radiance are device pointers on the scene's device, used in place on q->stream (NULL: the scene's own
+ *   stream, and the call waits; rays and rng must then be complete when the call is made).  On a caller's stream the call
+ *   returns once the work is enqueued when stats is NULL; with stats it waits, because the segment count is read back.
+ *   In both modes the claim counter and (spp > 1) the per-path records live in the scene's grow-only workspace, which
+ *   every call on the scene shares: calls on one scene (rt_render, rt_query_rays on host buffers, this one) must be
+ *   ordered by the caller -- the same stream, or a synchronisation between them.  The first call uploads the scene.
+ * RT_E_INVALID, before any device work: scene or q NULL; n < 0 or above the limits; rays or radiance NULL with n > 0;
+ *   max_depth < 1; spp < 0; a flag bit other than RT_OUT_DEVICE | RT_GLOBAL_SCENE; stream without RT_OUT_DEVICE;
+ *   id_base + n > 2^32 when rng is NULL.  n = 0 is RT_OK and touches nothing. */
+typedef struct rt_radiance_params { /* zero-initialised + max_depth = host buffers, seed 0, spp 1 */
+    int32_t flags;              /* RT_OUT_DEVICE | RT_GLOBAL_SCENE, nothing else */
+    int32_t spp;                /* samples per ray, >= 1 (0 is taken as 1) */
+    int32_t max_depth;          /* >= 1, as rt_params.max_depth */
+    uint32_t sample_base;       /* first sample index */
+    uint64_t seed;
+    uint64_t id_base;           /* stream id of ray 0; ray i has id_base + i; id_base + n <= 2^32 */
+    void* stream;               /* hipStream_t (RT_OUT_DEVICE only), or NULL for the scene's own stream */
+    double background[3];       /* returned on a miss, as rt_params.background */
+} rt_radiance_params;
+int rt_radiance_rays(rt_scene* scene, const rt_radiance_params* q, const double* rays, const uint64_t* rng, int64_t n, double* radiance,
+                     rt_stats* stats);
+/* rt_camera_rays (additive since ABI 5): rt_render's own camera rays as data -- the starting point of a custom camera, and
+ * what makes rt_radiance_rays checkable against rt_render.  Entry (ly * width + lx) * k + j of rays_out (7 doubles) and
+ * rng_out (one PCG state; may be NULL) holds the ray of local pixel (lx, ly), sample sample_base + j, and the generator's
+ * state after the camera's draws (engine.h:58-68, camera.h:38-47: pixel jitter, lens disk, shutter time), with k =
+ * params->spp; local rows and the band partition as in rt_render.  Reads width, height (both >= 2), spp, seed, the band
+ * fields, flags (RT_OUT_DEVICE only) and stream; needs no scene.  Host buffers (blocking), or with RT_OUT_DEVICE device
+ * buffers on `device`, written on params->stream (the call returns once enqueued; NULL: the default stream, and the call
+ * waits).  RT_E_INVALID also when the padded local pixels (8x8 tiles) times k exceed 2^31: fewer samples per call. */
+int rt_camera_rays(const rt_camera* cam, const rt_params* params, uint32_t sample_base, int device, double* rays_out, uint64_t* rng_out);
 /* Number of rows a band partition owns, and optionally their global indices (rows_out may be NULL).  Global row y
  * belongs to band set (y / band_rows) % band_count; local row ly of set r is global row
  * (ly / band_rows) * band_rows * band_count + r * band_rows + ly % band_rows. */

@@ -149,6 +149,47 @@ inline void occluded_rays(const scene& world, const double* rays, const double* 
     check(rt_query_rays(world.objects.get(), &q, rays, t_max, n, nullptr, occluded), "occluded_rays");
 }
 
+// Path-traced radiance along caller-given rays (rt_radiance_rays): radiance receives n * 3 doubles, the f64 sums over
+// o.spp paths per ray in sample order (sums, like the renderer's per-pixel sums; not means).  Path (i, s) runs
+// engine::_ray_color (engine.h:447-466) on the PCG state rng[i * spp + s] when rng is given, else on the stream keyed
+// (seed, id_base + i, sample_base + s).  flags: RT_GLOBAL_SCENE, and RT_OUT_DEVICE with `stream` for device buffers.
+struct radiance_options {
+    int spp = 1, max_depth = 50;
+    std::uint64_t seed = 0, id_base = 0;
+    std::uint32_t sample_base = 0;
+    color background;
+    std::int32_t flags = 0;
+    void* stream = nullptr;
+};
+inline void radiance_rays(const scene& world, const double* rays, std::int64_t n, double* radiance, const radiance_options& o = {},
+                          const std::uint64_t* rng = nullptr, rt_stats* stats = nullptr) {
+    rt_radiance_params q{};
+    q.flags = o.flags;
+    q.spp = o.spp;
+    q.max_depth = o.max_depth;
+    q.sample_base = o.sample_base;
+    q.seed = o.seed;
+    q.id_base = o.id_base;
+    q.stream = o.stream;
+    for (int k = 0; k < 3; ++k) q.background[k] = o.background.e[k];
+    check(rt_radiance_rays(world.objects.get(), &q, rays, rng, n, radiance, stats), "radiance_rays");
+}
+// The renderer's own camera rays as data (rt_camera_rays): entry (y * width + x) * k + j of rays_out (7 doubles) and
+// rng_out (may be nullptr) is the ray render_engine starts at pixel (x, y) for sample sample_base + j with `seed`, and the
+// PCG state after the camera's draws -- so the in-order sum of radiance_rays over a pixel's entries is that pixel's sum.
+inline void camera_rays(const camera& cam, int width, int height, int k, double* rays_out, std::uint64_t* rng_out, std::uint32_t sample_base = 0,
+                        std::uint64_t seed = 0, int device = 0) {
+    rt_params p{};
+    p.width = width;
+    p.height = height;
+    p.spp = k;
+    p.seed = seed;
+    p.fp_mode = RT_FP64;
+    p.band_rows = height;
+    p.band_count = 1;
+    check(rt_camera_rays(&cam.raw(), &p, sample_base, device, rays_out, rng_out), "camera_rays");
+}
+
 // The engine with a runtime image size (the reference fixes W, H, C at compile time: engine<W,H,C> below); samples
 // per pixel and max depth are the reference's tracer_constants (tracer_constants.h:12-13) as arguments with the same
 // defaults.
