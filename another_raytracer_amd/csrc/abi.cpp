@@ -383,6 +383,38 @@ int rt_radiance_rays(rt_scene* s, const rt_radiance_params* q, const double* ray
     });
 }
 
+int rt_render_views(rt_scene* s, const rt_camera* cams, const uint64_t* seeds, int32_t nviews, const rt_params* p, uint8_t* out_rgb8,
+                    double* out_accum, rt_stats* stats) {
+    if (!s || !cams || !p) return fail(RT_E_INVALID, "rt_render_views: scene, cams and params must be non-NULL");
+    if (nviews < 0) return fail(RT_E_INVALID, "rt_render_views: nviews must be >= 0");
+    if (p->flags & ~(RT_OUT_DEVICE | RT_GLOBAL_SCENE)) return fail(RT_E_INVALID, "rt_render_views takes RT_OUT_DEVICE and RT_GLOBAL_SCENE only");
+    if (p->width < 2 || p->height < 2) return fail(RT_E_INVALID, "rt_render_views: width and height must be >= 2 (u = (i + r)/(W-1), engine.h:62-63)");
+    if (p->spp < 1) return fail(RT_E_INVALID, "rt_render_views: spp must be >= 1");
+    if (p->max_depth < 1) return fail(RT_E_INVALID, "rt_render_views: max_depth must be >= 1");
+    if (p->fp_mode != RT_FP64) return fail(RT_E_INVALID, "fp_mode must be RT_FP64 (0): the reference's double arithmetic is the only mode");
+    if (p->band_count != 1 || p->band_index != 0)
+        return fail(RT_E_INVALID, "rt_render_views renders whole frames: band_count must be 1 (and band_index 0)");
+    if (p->stream && !(p->flags & RT_OUT_DEVICE))
+        return fail(RT_E_INVALID, "rt_render_views: stream needs RT_OUT_DEVICE (host buffers run on the scene's own stream)");
+    const uint64_t view_paths = static_cast<uint64_t>(p->width) * static_cast<uint64_t>(p->height) * static_cast<uint64_t>(p->spp);
+    if (view_paths > art::kMaxPassSlots)
+        return fail(RT_E_INVALID, "rt_render_views: one view of width * height * spp = " + std::to_string(view_paths) + " paths exceeds kMaxPassSlots = "
+                                  "2^31 paths per launch: render such frames with rt_render, which splits a frame into passes");
+    if (nviews == 0) return RT_OK;
+    if (!out_rgb8) return fail(RT_E_INVALID, "rt_render_views: out_rgb8 must be non-NULL");
+    return guard(RT_E_DEVICE, [&] {
+        std::vector<art::CameraRec> recs(static_cast<size_t>(nviews));
+        for (int32_t v = 0; v < nviews; ++v) recs[static_cast<size_t>(v)] = camera_of(&cams[v]);
+        art::RenderStats st;
+        s->device_renderer().render_views(recs.data(), seeds, static_cast<size_t>(nviews), render_params(p), out_rgb8, out_accum, stats ? &st : nullptr);
+        if (stats) {
+            fill_stats(st, stats);
+            stats->extend_variant = stats->kernel_lds_mode = -1;  // neither an extend variant nor a k_paths_g instantiation
+        }
+        return RT_OK;
+    });
+}
+
 int rt_camera_rays(const rt_camera* cam, const rt_params* p, uint32_t sample_base, int device, double* rays_out, uint64_t* rng_out) {
     std::string why;
     if (!cam || !rays_out) return fail(RT_E_INVALID, "rt_camera_rays: camera and rays_out must be non-NULL");

@@ -62,6 +62,30 @@ struct RadianceJob {
 // The persistent path kernel over the job's paths with `background` on a miss (flags: RT_GLOBAL_SCENE), then the per-ray
 // sums when job.res is set.
 void launch_radiance_rays(const DeviceScene& ds, int flags, int num_cu, hipStream_t st, const RadianceJob& job, uint32_t n, const double background[3]);
+// One launch of rt_render_views as its kernels see it: a group of whole views of one W x H x spp frame.  Path
+// p = ((v * npix + pixel) * spp + s) of P = views * npix * spp <= kMaxPassSlots, pixel = ly * W + lx (row-major: p is
+// also the index of the path's record, and p / spp the pixel's place in the group's sums).
+struct ViewRec {  // a view of the table: its camera and splitmix64(its seed), PassGeom::seed_mix per view
+    CameraRec cam;
+    uint64_t seed_mix;
+};
+struct ViewsJob {
+    const ViewRec* views;          // the group's views
+    double* radiance;              // the group's pixels x 3; written by k_radiance_views itself when res is null (spp == 1)
+    ResRec* res;                   // P per-path records for k_radiance_sum (spp > 1), or null
+    uint32_t* next;                // the claim counter, zeroed before the launch
+    unsigned long long* segments;  // the kernel adds its segments: zeroed before the first group
+    uint32_t P, spp, chunk;
+    uint32_t npix;                 // W * H
+    uint32_t stack;
+    int32_t max_depth;
+    int32_t W, H;
+    double inv_w1, inv_h1;         // PassGeom's: RN(1 / (W - 1)), RN(1 / (H - 1))
+    FastDiv fd_spp, fd_npix, fd_w;  // / spp, / npix, / W
+};
+// The persistent path kernel over the job's paths with `background` on a miss (flags: RT_GLOBAL_SCENE), then the sums
+// of the job's npixels = views * npix pixels when job.res is set.
+void launch_radiance_views(const DeviceScene& ds, int flags, int num_cu, hipStream_t st, const ViewsJob& job, uint32_t npixels, const double background[3]);
 // rt_camera_rays: entry (ly * W + lx) * g.k + j = cam_ray of local pixel (lx, ly), sample g.sample_base + j (rng may be null)
 void launch_camera_rays(hipStream_t st, const PassGeom& g, const CameraRec& cam, double* rays, uint64_t* rng);
 // k_paths.hip

@@ -30,6 +30,8 @@ enum class Opt : int {
                            // LDS-tile kernel instead of the direct-load one (0..2; same result either way, A/B)
     QueryAnySorted,  // query.any_sorted: rt_query_rays' any-hit walk visits a node's children in node order without the
                      // sorting network (0, default: measured faster) or nearest first (1); the same answers either way (A/B)
+    ViewsMaxPaths,   // views.max_paths: cap on the paths of one rt_render_views launch, i.e. on the views of a group (0,
+                     // default: off; a group is never less than one view; diagnostic: the results do not depend on it)
     // multi-GPU
     MultiTimeoutMs,  // multi.timeout_ms: deadline of RCCL init / gather waits (unset: ART_MULTI_TIMEOUT_MS, else 120000;
                      // inf, or anything beyond ~292 years, means no deadline)

@@ -1,7 +1,8 @@
-// radiance_rays.hip — rt_radiance_rays and rt_camera_rays: path-traced radiance along caller-given rays, and the
-// renderer's own camera rays as data.  The kernels and their launchers (launch.h) in an object of their own, so that no
-// kernel of kernels.hip, k_paths.hip or k_paths_g_mesh.hip moves.
+// radiance_rays.hip — rt_radiance_rays, rt_render_views and rt_camera_rays: path-traced radiance along caller-given rays
+// or from a table of cameras, and the renderer's own camera rays as data.  The kernels and their launchers (launch.h) in
+// an object of their own, so that no kernel of kernels.hip, k_paths.hip or k_paths_g_mesh.hip moves.
 #include <algorithm>
+#include <type_traits>
 
 #include "art.h"
 #include "path_work.h"
@@ -14,161 +15,78 @@ namespace art {
 // Next-Week final: 4.94 against 3.90 Gsegments/s at 2; cow, whose form fits either way, +-0.
 constexpr int kRadianceWaves = 3;
 
-// Dynamic LDS of a k_radiance_rays block: [scene image (L)][traversal stacks: `stack` rows x B lanes][jump table][job]
+// Dynamic LDS of a k_radiance_rays / k_radiance_views block: [scene image (L)][traversal stacks: `stack` rows x B lanes]
+// [jump table][job]
 __host__ __device__ constexpr size_t radiance_jump_offset(bool L, uint32_t stack) {
     return L ? kLdsImageBytes + paths_stack_bytes(stack) : sizeof(int32_t) * stack * kBlock;
 }
-__host__ __device__ constexpr size_t radiance_lds_bytes(bool L, uint32_t stack) { return radiance_jump_offset(L, stack) + kJumpBytes + sizeof(RadianceJob); }
+template <class Job>
+__host__ __device__ constexpr size_t radiance_lds_bytes(bool L, uint32_t stack) { return radiance_jump_offset(L, stack) + kJumpBytes + sizeof(Job); }
 
-// Persistent paths from caller-given rays (rt_radiance_rays): path p = i * spp + s starts at ray i with throughput 1 and
+// cam_ray (path_work.h) for sample s at pixel (lx, ly) of a whole W x H frame -- band fields (H, 1, 0): the global row is
+// the local one -- with the view's own camera and seed: the same operations in the same order.  Restated, not shared:
+// a cam_ray that forwards to a core taking the seed apart moved k_paths and k_paths_g (other code for equal results).
+__device__ __forceinline__ void view_cam_ray(const ViewsJob& job, const ViewRec& view, uint32_t s, int lx, int ly, Ray& ray, uint64_t& rng_out) {
+    const CameraRec& cam = view.cam;
+    const uint32_t pixel = static_cast<uint32_t>(ly) * static_cast<uint32_t>(job.W) + static_cast<uint32_t>(lx);
+    uint64_t rng = splitmix64(((static_cast<uint64_t>(pixel) << 32) | s) ^ view.seed_mix);  // == pcg_seed(seed of the view, pixel, s)
+    const double ru = uniform(rng);
+    const double rv = uniform(rng);
+    const double su = div_rcp(static_cast<double>(lx) + ru, static_cast<double>(job.W - 1), job.inv_w1);
+    const double tv = div_rcp(static_cast<double>(job.H - 1 - ly) + rv, static_cast<double>(job.H - 1), job.inv_h1);
+    V3 p;
+    for (;;) {  // random_in_unit_disk (vec3.h:137-143): x, then y
+        p.x = uniform_pm1(rng);
+        p.y = uniform_pm1(rng);
+        p.z = 0.0;
+        if (len2(p) >= 1.0) continue;
+        break;
+    }
+    const V3 rd = cam.lens_radius * p;
+    const V3 offset = rd.x * ld3(cam.u) + rd.y * ld3(cam.v);
+    Ray r;
+    r.o = ld3(cam.origin) + offset;
+    r.d = ld3(cam.llc) + su * ld3(cam.horizontal) + tv * ld3(cam.vertical) - ld3(cam.origin) - offset;
+    r.tm = uniform(rng, cam.time0, cam.time1);
+    // The ray and the state enter the path's registers as eight opaque values, as the memory source's enter as loads.
+    // Without this the register coalescer joins the arithmetic above with the path state (whose origin is also the hit
+    // point that scatter writes), and k_radiance_views<127, false, 3 / 19> park a 16-byte value of world_surface at 12
+    // places (.vgpr_spill_count 48 against their siblings' 2 / 3); with it every form has its sibling's VGPRs (the first
+    // of the two one more) and spills what its sibling does, or less.
+    __asm__ volatile("" : "+v"(r.o.x), "+v"(r.o.y), "+v"(r.o.z), "+v"(r.d.x), "+v"(r.d.y), "+v"(r.d.z), "+v"(r.tm), "+v"(rng));
+    ray = r;
+    rng_out = rng;
+}
+
+// The persistent path kernel (radiance_loop.inc), built once per path source: k_radiance_rays and k_radiance_views.
+// RadianceJob, paths from caller-given rays (rt_radiance_rays): path p = i * spp + s starts at ray i with throughput 1 and
 // the RNG state job.rng[p], or pcg_seed(seed, id_base + i, sample_base + s), and runs _ray_color (engine.h:447-466) as
 // k_paths_g's loop runs it -- the same trace_world, world_surface, wave-cooperative sphere draw and scatter calls in the
 // same order, so a path started from cam_ray's ray and state ends with rt_render's bits.  Waves claim job.chunk path
 // indices per atomic from one counter, and a lane whose path ended takes the wave's next index by ballot rank
 // (k_paths_g's ring-free path start with the ray read from memory instead of generated); the path stays in registers.
+// ViewsJob, paths from a table of cameras (rt_render_views): p = (v * npix + ly * W + lx) * spp + s starts at cam_ray's
+// ray and post-camera state of view v's camera and seed (job.views[v], read at the path's start) for pixel (lx, ly),
+// sample s of the whole W x H frame -- cam_ray's arithmetic (view_cam_ray) with the ray in registers -- so the path ends
+// with the bits rt_render gives that view.  Row-major pixels: with a pixel's samples on consecutive indices a wave's 64
+// claimed indices are 64 / spp neighbouring pixels of a row in tile order as well (from 8 samples up), and p is at once
+// the index of the path's record and, over spp, of the pixel's sums: no padded slots, nothing to carry to the path's end.
 // F / L as the other ray kernels (ray_launch.h), TF as k_guides.  L: the scene image at LDS address 0, no static LDS.
-template <uint32_t F, bool L, uint32_t TF>
-__global__ __launch_bounds__(L ? kBlockL : kBlock, L ? 1 : kRadianceWaves) void k_radiance_rays(DevScene S, RadianceJob job0) {
-    constexpr int B = L ? kBlockL : kBlock;
-    extern __shared__ __align__(16) uint8_t smem[];
-    StackT<L>* stk = reinterpret_cast<StackT<L>*>(smem + (L ? kLdsImageBytes : 0u)) + B + stack_column<L>(threadIdx.x);
-    stk[-B] = static_cast<StackT<L>>(kNodeEmpty);
-    JumpEntry* jt = reinterpret_cast<JumpEntry*>(smem + radiance_jump_offset(L, job0.stack));
-    if (threadIdx.x < static_cast<uint32_t>(kJumpEntries)) jt[threadIdx.x] = pcg_jump(3u * threadIdx.x);
-    // the job is read from LDS where a path starts or ends, as k_paths_g reads its pass geometry: held in SGPRs for the
-    // whole loop beside the scene view, the kernel arguments spill into VGPR lanes
-    const RadianceJob& job = *reinterpret_cast<const RadianceJob*>(jt + kJumpEntries);
-    if (threadIdx.x == 0) *reinterpret_cast<RadianceJob*>(jt + kJumpEntries) = job0;
-    if constexpr (L) load_lds_image<B>(S.lds_image, smem);
-    __syncthreads();
-    const uint8_t* lds = L ? smem : nullptr;
-    const uint32_t lane = __lane_id();
-    const uint64_t below = (1ull << lane) - 1ull;
-    const V3 bg = mk(S.bg[0], S.bg[1], S.bg[2]);
-    const int max_depth = job0.max_depth;
-    uint32_t cur = 0, end = 0;  // this wave's claimed path indices [cur, end): wave-uniform
-    bool busy = false, drained = false;
-    uint32_t q = 0;
-    int depth = 0;
-    PathState st;
-    uint32_t segs = 0;  // this lane's segments (32 bits: a register less in the loop; summed in 64)
-    for (;;) {
-        const uint64_t idle = __ballot(!busy && !drained);
-        if (idle) {
-            const uint32_t n = static_cast<uint32_t>(__popcll(idle));
-            const uint32_t rank = static_cast<uint32_t>(__popcll(idle & below));
-            uint32_t p;
-            if (cur + n > end) {
-                uint32_t nb = 0;
-                if (lane == 0) nb = atomicAdd(job.next, job.chunk);
-                nb = __shfl(nb, 0);
-                const uint32_t left = end - cur;
-                p = rank < left ? cur + rank : nb + (rank - left);
-                cur = nb + (n - left);
-                end = nb + job.chunk;
-            } else {
-                p = cur + rank;
-                cur += n;
-            }
-            if (!busy && !drained) {
-                __asm__ volatile("" ::: "memory");  // keep the LDS job loads here
-                if (p >= job.P) {
-                    drained = true;
-                } else {
-                    const uint32_t i = job.fd_spp.div(p), s = p - i * job.spp;
-                    const double* r = job.rays + 7 * static_cast<size_t>(i);
-                    st.ray.o = mk(r[0], r[1], r[2]);
-                    st.ray.d = mk(r[3], r[4], r[5]);
-                    st.ray.tm = r[6];
-                    st.rng = job.rng ? job.rng[p]
-                                     : splitmix64(((static_cast<uint64_t>(job.id_base + i) << 32) | (job.sample_base + s)) ^ job.seed_mix);
-                    st.T = mk(1.0, 1.0, 1.0);
-                    q = p;
-                    busy = true;
-                    depth = 0;
-                }
-            }
-        }
-        if (__ballot(busy) == 0) {
-            if (__ballot(!drained) == 0) break;
-            continue;
-        }
-        double t;
-        HitOut h{0, 0, kMatUnknown};
-        bool hitw = false;
-        Surf s;
-        uint32_t mtype = MAT_LIGHT;
-        if (busy) {
-            ++segs;
-            hitw = trace_world<F, B, L>(S, lds, st.ray, stk, st.rng, t, h);
-            if (hitw) {
-                world_surface<F, (TF & TF_IMAGE) != 0, (TF & (TF_IMAGE | TF_BARY)) != 0>(S, h, st.ray, t, s, uv_table(S));
-                mtype = S.mats[s.mat].type;
-            }
-        }
-        // the whole wave draws random_in_unit_sphere for its lambertian, metal and isotropic hits, as k_paths_g does
-        const bool need = busy && hitw && (mtype == MAT_LAMBERTIAN || mtype == MAT_METAL || mtype == MAT_ISOTROPIC) && depth + 1 < max_depth;
-        const V3 ps = coop_unit_sphere(need, st.rng, jt);
-        const V3* pre = &ps;
-        if (busy) {
-            bool cont = false;
-            // a live path's radiance is zero: only a miss or a light adds to it, and both end the path
-            st.L = mk(0.0, 0.0, 0.0);
-            if (hitw) {
-                const MatRec& mat = S.mats[s.mat];
-                // the steps several materials share, once for the wave (k_paths_g.h: kernels with noise or image textures)
-                constexpr bool kShared = (TF & (TF_NOISE | TF_IMAGE)) != 0;
-                V3 texc = mk(0.0, 0.0, 0.0), uv = mk(0.0, 0.0, 0.0);
-                if constexpr (kShared) {
-                    const bool scat = depth + 1 < max_depth;
-                    if (mat.type == MAT_LIGHT || (scat && (mat.type == MAT_LAMBERTIAN || mat.type == MAT_ISOTROPIC)))
-                        texc = mat_tex_value<TF>(S, mat, s.u, s.v, s.p);
-                    if (scat && (mat.type == MAT_LAMBERTIAN || mat.type == MAT_METAL || mat.type == MAT_DIELECTRIC))
-                        uv = unit(mat.type == MAT_LAMBERTIAN ? *pre : st.ray.d);
-                }
-                const V3* texp = kShared ? &texc : nullptr;
-                const V3* uvp = kShared ? &uv : nullptr;
-                if (mat.type == MAT_LIGHT) {  // material.h:114-116; diffuse_light never scatters
-                    st.L = st.L + st.T * (texp ? *texp : mat_tex_value<TF>(S, mat, s.u, s.v, s.p));
-                } else if (depth + 1 < max_depth) {
-                    V3 att, dir;
-                    bool sc = false;
-                    switch (mat.type) {
-                        case MAT_LAMBERTIAN: sc = scatter<MAT_LAMBERTIAN, TF>(S, mat, s, st, att, dir, pre, uvp, texp); break;
-                        case MAT_METAL: sc = scatter<MAT_METAL, TF>(S, mat, s, st, att, dir, pre, uvp); break;
-                        case MAT_DIELECTRIC: sc = scatter<MAT_DIELECTRIC, TF>(S, mat, s, st, att, dir, nullptr, uvp); break;
-                        case MAT_ISOTROPIC: sc = scatter<MAT_ISOTROPIC, TF>(S, mat, s, st, att, dir, pre, nullptr, texp); break;
-                        default: break;
-                    }
-                    if (sc) {
-                        st.T = st.T * att;
-                        st.ray.o = s.p;
-                        st.ray.d = dir;
-                        cont = true;
-                    }
-                }
-            } else {  // engine.h:455-456: miss -> background
-                st.L = st.L + st.T * bg;
-            }
-            if (cont) {
-                ++depth;
-            } else {
-                if (job.res) {
-                    store_res<false>(job.res, q, st.L);
-                } else {  // spp == 1: path q is ray q; the sum of one sample from +0.0
-                    double* o = job.radiance + 3 * static_cast<size_t>(q);
-                    o[0] = 0.0 + st.L.x;
-                    o[1] = 0.0 + st.L.y;
-                    o[2] = 0.0 + st.L.z;
-                }
-                busy = false;
-            }
-        }
-    }
-    unsigned long long wsegs = segs;
-    for (int off = 32; off > 0; off >>= 1) wsegs += __shfl_xor(wsegs, off);
-    if (lane == 0) atomicAdd(job0.segments, wsegs);
-}
+// rt_render_views' kernel has the same nine (F, L, TF) forms, the LDS-image one with one 1024-lane block per CU.
+#define RADIANCE_KERNEL k_radiance_rays
+#define RADIANCE_JOB RadianceJob
+#define RADIANCE_CAMERAS 0
+#include "radiance_loop.inc"
+#undef RADIANCE_KERNEL
+#undef RADIANCE_JOB
+#undef RADIANCE_CAMERAS
+#define RADIANCE_KERNEL k_radiance_views
+#define RADIANCE_JOB ViewsJob
+#define RADIANCE_CAMERAS 1
+#include "radiance_loop.inc"
+#undef RADIANCE_KERNEL
+#undef RADIANCE_JOB
+#undef RADIANCE_CAMERAS
 
 // radiance[i] = +0.0 + L(i, 0) + L(i, 1) + ...: ray i's spp records in sample order (k_accum's order from a zeroed sum)
 __global__ __launch_bounds__(256) void k_radiance_sum(const ResRec* res, uint32_t n, uint32_t spp, double* radiance) {
@@ -208,11 +126,15 @@ __global__ __launch_bounds__(256) void k_camera_rays(PassGeom g, CameraRec cam, 
     if (rng) rng[e] = state;
 }
 
-template <uint32_t F, bool L, uint32_t TF>
-static void launch_radiance_ft(const DeviceScene& ds, int num_cu, hipStream_t st, const DevScene& S, const RadianceJob& job) {
-    const void* kernel = reinterpret_cast<const void*>(k_radiance_rays<F, L, TF>);
+template <uint32_t F, bool L, uint32_t TF, class Job>
+static void launch_radiance_ft(const DeviceScene& ds, int num_cu, hipStream_t st, const DevScene& S, const Job& job) {
+    const auto kfn = [] {
+        if constexpr (std::is_same<Job, ViewsJob>::value) return &k_radiance_views<F, L, TF>;
+        else return &k_radiance_rays<F, L, TF>;
+    }();
+    const void* kernel = reinterpret_cast<const void*>(kfn);
     constexpr int B = L ? kBlockL : kBlock;
-    const size_t lds = radiance_lds_bytes(L, job.stack);
+    const size_t lds = radiance_lds_bytes<Job>(L, job.stack);
     if constexpr (L) {
         static const bool checked = static_lds_is_zero(kernel);
         (void)checked;
@@ -220,11 +142,13 @@ static void launch_radiance_ft(const DeviceScene& ds, int num_cu, hipStream_t st
     // a persistent grid: every block the CUs hold at once, or fewer when the job has fewer paths than their lanes
     const uint64_t full = static_cast<uint64_t>(blocks_per_cu(kernel, B, lds)) * static_cast<uint64_t>(num_cu);
     const uint64_t need = (static_cast<uint64_t>(job.P) + B - 1) / B;
-    hipLaunchKernelGGL((k_radiance_rays<F, L, TF>), dim3(static_cast<uint32_t>(std::min(full, need))), dim3(B), lds, st, S, job);
+    hipLaunchKernelGGL(kfn, dim3(static_cast<uint32_t>(std::min(full, need))), dim3(B), lds, st, S, job);
     (void)ds;
 }
 
-void launch_radiance_rays(const DeviceScene& ds, int flags, int num_cu, hipStream_t st, const RadianceJob& job, uint32_t n, const double background[3]) {
+// The path kernel of either job type, then the sums of its n rays / pixels when job.res is set
+template <class Job>
+static void launch_radiance_job(const DeviceScene& ds, int flags, int num_cu, hipStream_t st, const Job& job, uint32_t n, const double background[3]) {
     DevScene S = ds.view;
     for (int a = 0; a < 3; ++a) S.bg[a] = background[a];
     // The LDS scene image only with solid / checker textures: with noise or image textures the 1024-lane block's 128
@@ -242,6 +166,13 @@ void launch_radiance_rays(const DeviceScene& ds, int flags, int num_cu, hipStrea
         }
     });
     if (job.res) hipLaunchKernelGGL(k_radiance_sum, dim3((n + 255) / 256), dim3(256), 0, st, job.res, n, job.spp, job.radiance);
+}
+
+void launch_radiance_rays(const DeviceScene& ds, int flags, int num_cu, hipStream_t st, const RadianceJob& job, uint32_t n, const double background[3]) {
+    launch_radiance_job(ds, flags, num_cu, st, job, n, background);
+}
+void launch_radiance_views(const DeviceScene& ds, int flags, int num_cu, hipStream_t st, const ViewsJob& job, uint32_t npixels, const double background[3]) {
+    launch_radiance_job(ds, flags, num_cu, st, job, npixels, background);
 }
 
 void launch_camera_rays(hipStream_t st, const PassGeom& g, const CameraRec& cam, double* rays, uint64_t* rng) {

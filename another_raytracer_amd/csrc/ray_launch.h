@@ -1,5 +1,5 @@
 // ray_launch.h — what the objects with ray kernels share on the host side (kernels.hip: k_trace_rays, k_guides,
-// k_query_rays, k_occlude_rays; radiance_rays.hip: k_radiance_rays): the choice of instantiation and the launch of a
+// k_query_rays, k_occlude_rays; radiance_rays.hip: k_radiance_rays, k_radiance_views): the choice of instantiation and the launch of a
 // one-thread-per-item kernel.  Host templates only; included by .hip files.
 #pragma once
 #include <type_traits>

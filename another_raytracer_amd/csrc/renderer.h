@@ -68,6 +68,14 @@ public:
     // the claim counter and the per-path records come from the workspace either way.  stats (may be null: then a device
     // call on the caller's stream returns once enqueued) receives segments, primary and ms.
     void radiance_rays(const RadianceParams& p, const double* rays, const uint64_t* rng, size_t n, double* radiance, RenderStats* stats);
+    // rt_render_views: nviews whole frames of p's width x height x spp, view v through cams[v] with seed seeds[v] (seeds
+    // null: p.seed), each equal to render()'s bit for bit.  out_rgb (nviews x H x W x 3 bytes) and out_acc (optional, the
+    // f64 sums) are host buffers, or with RT_OUT_DEVICE device buffers written in place on p.stream; the camera table,
+    // the claim counters, the per-path records of the largest group (view_plan.h) and whatever the caller's buffers do
+    // not hold come from the workspace.  stats (may be null: then a device call on the caller's stream returns once
+    // enqueued) receives segments, primary, ms and passes = the launches of the path kernel.
+    void render_views(const CameraRec* cams, const uint64_t* seeds, size_t nviews, const RenderParams& p, uint8_t* out_rgb, double* out_acc,
+                      RenderStats* stats);
     // rt_camera_rays: cam_ray (path_work.h) of every local pixel of p's frame and band partition, samples
     // [sample_base, sample_base + p.spp), entry (ly * W + lx) * p.spp + j; host buffers, or device ones on `device` with
     // RT_OUT_DEVICE (p.stream; null: the default stream).  rng_out may be null.  Needs no scene.  Blocking.

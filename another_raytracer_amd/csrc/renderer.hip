@@ -1,6 +1,6 @@
 // renderer.hip — Renderer (renderer.h): the workspace, the pass loops of rt_render and rt_render_noise_target, ray
-// queries, radiance along caller-given rays, camera rays and guide buffers.  Host code only: every kernel is launched
-// through launch.h / noise_target.h.
+// queries, radiance along caller-given rays, many views of a scene in one launch, camera rays and guide buffers.  Host
+// code only: every kernel is launched through launch.h / noise_target.h.
 //
 // The workspace is one grow-only DeviceBuffer that every entry point carves (workspace.h).  rt_render and
 // rt_render_noise_target share a Frame: begin_frame sets it up (geometry, variant, the samples per pass of pass_plan.h,
@@ -18,6 +18,7 @@
 #include "launch.h"
 #include "options.h"
 #include "pass_plan.h"
+#include "view_plan.h"
 #include "workspace.h"
 
 namespace art {
@@ -31,6 +32,7 @@ struct Renderer::Impl {
     bool up64 = false;
     DeviceBuffer ws{true};  // the workspace, with the test.fault_workspace_bytes fault point
     hipEvent_t ev[2] = {nullptr, nullptr};
+    std::vector<ViewRec> view_table;  // rt_render_views: the camera table of the last call, as uploaded
 
     ~Impl() {
         s64.release();
@@ -583,6 +585,97 @@ void Renderer::radiance_rays(const RadianceParams& p, const double* rays, const 
         *stats = RenderStats{};
         stats->segments = segs, stats->primary = P, stats->ms = ms;
         stats->passes = 1, stats->samples_per_pass = static_cast<int>(spp);
+    }
+}
+
+void Renderer::render_views(const CameraRec* cams, const uint64_t* seeds, size_t nviews, const RenderParams& p, uint8_t* out_rgb, double* out_acc,
+                            RenderStats* stats) {
+    upload();
+    Impl& I = *impl_;
+    const DeviceScene& ds = I.s64;
+    if (nviews == 0) return;
+    const bool device = (p.flags & RT_OUT_DEVICE) != 0;
+    hipStream_t st = (device && p.stream) ? static_cast<hipStream_t>(p.stream) : I.own_stream;
+    const uint32_t spp = static_cast<uint32_t>(p.spp);
+    const uint64_t npix = static_cast<uint64_t>(p.width) * static_cast<uint64_t>(p.height);
+    const uint64_t view_paths = npix * spp;
+    // the groups (view_plan.h): a launch's records within half of the free HBM (plus the workspace this renderer already
+    // owns: a fixed point, as begin_frame's slot target), within kMaxPassSlots and within views.max_paths
+    size_t free_b = 0, total_b = 0;
+    HIP_OK(hipMemGetInfo(&free_b, &total_b));
+    ViewPlan plan{};
+    if (!plan_views(nviews, view_paths, (free_b + I.ws.size()) / 2 / sizeof(ResRec), static_cast<uint64_t>(opt(Opt::ViewsMaxPaths)), plan))
+        throw std::runtime_error("a view has more paths than one launch holds (kMaxPassSlots)");
+    const uint64_t group_paths = static_cast<uint64_t>(plan.per_group) * view_paths;
+    const size_t pixels = static_cast<size_t>(nviews) * static_cast<size_t>(npix);
+    // workspace: a claim counter's line per group, the segment count, the camera table, the largest group's per-path
+    // records (spp > 1) and the frames' sums and bytes unless the caller's device buffers take them
+    uint32_t* next = nullptr;
+    unsigned long long* segments = nullptr;
+    ViewRec* table = nullptr;
+    ResRec* res = nullptr;
+    double* d_acc = nullptr;
+    uint8_t* d_rgb = nullptr;
+    auto carve = [&](Carver& c) {
+        next = c.take<uint32_t>(static_cast<size_t>(plan.ngroups) * kCounterStride);
+        segments = c.take<unsigned long long>(1);
+        table = c.take<ViewRec>(nviews);
+        res = c.take<ResRec>(group_paths, spp > 1);
+        d_acc = c.take<double>(3 * pixels, !(device && out_acc));
+        d_rgb = c.take<uint8_t>(3 * pixels, !device);
+    };
+    Carver size(nullptr);
+    carve(size);
+    Carver parts(I.ws.reserve(size.total()));
+    carve(parts);
+    double* acc = (device && out_acc) ? out_acc : d_acc;
+    uint8_t* rgb = device ? out_rgb : d_rgb;
+    // the table's host copy lives in the renderer until the next call: the upload may still read it when a call on the
+    // caller's stream returns
+    I.view_table.resize(nviews);
+    for (size_t v = 0; v < nviews; ++v) I.view_table[v] = ViewRec{cams[v], splitmix64(seeds ? seeds[v] : p.seed)};
+    if (stats)
+        for (auto& e : I.ev)
+            if (!e) HIP_OK(hipEventCreate(&e));
+    HIP_OK(hipMemcpyAsync(table, I.view_table.data(), sizeof(ViewRec) * nviews, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemsetAsync(next, 0, sizeof(uint32_t) * plan.ngroups * kCounterStride, st));
+    HIP_OK(hipMemsetAsync(segments, 0, sizeof(unsigned long long), st));
+    if (stats) HIP_OK(hipEventRecord(I.ev[0], st));
+    ViewsJob job{};
+    job.segments = segments;
+    job.spp = spp, job.npix = static_cast<uint32_t>(npix);
+    job.stack = stack_rows(ds.max_stack);
+    job.max_depth = p.max_depth;
+    job.W = p.width, job.H = p.height;
+    job.inv_w1 = 1.0 / static_cast<double>(p.width - 1), job.inv_h1 = 1.0 / static_cast<double>(p.height - 1);  // make_pass_geom's
+    job.fd_spp = FastDiv::make(spp), job.fd_npix = FastDiv::make(job.npix), job.fd_w = FastDiv::make(static_cast<uint32_t>(p.width));
+    for (uint32_t g = 0; g < plan.ngroups; ++g) {
+        const size_t v0 = static_cast<size_t>(g) * plan.per_group, nv = std::min<size_t>(plan.per_group, nviews - v0);
+        const uint32_t gpix = static_cast<uint32_t>(nv * npix);  // <= group_paths <= kMaxPassSlots
+        job.views = table + v0;
+        job.radiance = acc + 3 * v0 * npix;
+        job.res = spp > 1 ? res : nullptr;
+        job.next = next + static_cast<size_t>(g) * kCounterStride;
+        job.P = static_cast<uint32_t>(nv * view_paths), job.chunk = path_chunk(job.P, I.num_cu);
+        launch_radiance_views(ds, p.flags, I.num_cu, st, job, gpix, p.background);
+        launch_finalize(st, job.radiance, rgb + 3 * v0 * npix, gpix, p.spp);
+    }
+    HIP_OK(hipGetLastError());
+    if (stats) HIP_OK(hipEventRecord(I.ev[1], st));
+    if (!device) {
+        HIP_OK(hipMemcpyAsync(out_rgb, d_rgb, 3 * pixels, hipMemcpyDeviceToHost, st));
+        if (out_acc) HIP_OK(hipMemcpyAsync(out_acc, d_acc, sizeof(double) * 3 * pixels, hipMemcpyDeviceToHost, st));
+    }
+    unsigned long long segs = 0;
+    if (stats) HIP_OK(hipMemcpyAsync(&segs, segments, sizeof segs, hipMemcpyDeviceToHost, st));
+    // a device call on the caller's stream without stats returns here, enqueued; every other waits
+    if (!device || !p.stream || stats) HIP_OK(hipStreamSynchronize(st));
+    if (stats) {
+        float ms = 0;
+        HIP_OK(hipEventElapsedTime(&ms, I.ev[0], I.ev[1]));
+        *stats = RenderStats{};
+        stats->segments = segs, stats->primary = static_cast<uint64_t>(nviews) * view_paths, stats->ms = ms;
+        stats->passes = static_cast<int>(plan.ngroups), stats->samples_per_pass = p.spp;
     }
 }
 

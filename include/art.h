@@ -27,6 +27,12 @@
  *   hittable_list::hit(r, 0.001, inf, rec)   hittable_list.cpp:5 rt_trace_rays(scene, rays, n, flags, t, normals)
  *   hittable_list::hit(r, t_min, t_max, rec)  hittable_list.cpp:5 rt_query_rays(scene, &q, rays, t_max, n, hits, occluded): the
  *     with the full hit_record                hittable.h:9-23       whole record per ray (t_min = 0.001), or any-hit occlusion
+ *   _ray_color(r, background, world, depth)  engine.h:447-466    rt_radiance_rays(scene, &q, rays, rng, n, radiance, stats): the
+ *     for a ray the caller made                                      recursion along caller-given rays, summed over spp samples
+ *   _stochastic_sample's camera draws and     engine.h:58-68,     rt_camera_rays(&cam, &params, sample_base, device, rays, rng): the
+ *     camera::get_ray                         camera.h:38-47        renderer's camera rays and post-camera RNG states as data
+ *   one engine::run per camera of a scene     main.cpp:29-46      rt_render_views(scene, cams, seeds, nviews, &params, rgb8, accum,
+ *     (an orbit, a cube map, a light field)                          stats): every view in one persistent launch, rt_render's bits
  *   (scene construction every run)           scene_manager.cpp,  rt_scene_save / rt_scene_load (flat-scene files)
  *                                            mesh.h, bvh.cpp
  *   (none: engine_mode::adaptive interpolates     engine.h:96-333  rt_render_guides + rt_denoise, or rt_render_denoised
@@ -63,7 +69,8 @@ extern "C" {
  * RT_GUIDE_DOUBLES, RT_DN_NO_DEMODULATE; rt_render_noise_target, rt_noise_params, rt_noise_result; rt_query_rays,
  * rt_query_params, RT_Q_ANY_HIT, RT_Q_NO_MEDIA, RT_HIT_DOUBLES (ray queries with the hit record, a per-ray t_max, occlusion
  * queries, device buffers and a caller's stream), option query.any_sorted; rt_radiance_rays, rt_radiance_params (path-traced
- * radiance along caller-given rays), rt_camera_rays (the renderer's camera rays and post-camera RNG states as data). */
+ * radiance along caller-given rays), rt_camera_rays (the renderer's camera rays and post-camera RNG states as data);
+ * rt_render_views (many cameras of one scene in one persistent launch), option views.max_paths. */
 #define RT_ABI_VERSION 5
 
 /* return codes */
@@ -170,6 +177,8 @@ int rt_device_count(void);
  *   LDS tile instead of loading each directly; 0..2, the result is identical either way);
  *   query.any_sorted (0; rt_query_rays' any-hit walk takes a node's children in node order, without the closest search's
  *   sorting network; 1 = nearest first; the answers are identical either way, DESIGN.md 4.7 measured both);
+ *   views.max_paths (0 = off; N caps the paths of one rt_render_views launch, so the views run in groups of
+ *   floor(N / (width * height * spp)) views, at least one; diagnostic: the frames are identical either way);
  *   multi.timeout_ms (the RCCL deadline; inf = none), multi.rccl_blocking (0; 1 = blocking communicators, diagnosis:
  *   gives up the deadline and the error-path protection);
  *   test.fault_workspace_bytes (0 = off; N refuses workspace growth beyond N bytes), test.fault_gather_abort (0; 1 = the
@@ -305,6 +314,37 @@ int rt_radiance_rays(rt_scene* scene, const rt_radiance_params* q, const double*
  * buffers on `device`, written on params->stream (the call returns once enqueued; NULL: the default stream, and the call
  * waits).  RT_E_INVALID also when the padded local pixels (8x8 tiles) times k exceed 2^31: fewer samples per call. */
 int rt_camera_rays(const rt_camera* cam, const rt_params* params, uint32_t sample_base, int device, double* rays_out, uint64_t* rng_out);
+/* rt_render_views (additive since ABI 5): nviews whole frames of one scene in one call -- an orbit of a mesh, the six faces of
+ * a cube map, a light field -- where a loop of rt_render pays a workspace reset, a launch per pass, the accumulation, a
+ * host wait and a copy per frame.  Every view has params->width x height, spp, max_depth and background; view v looks
+ * through cams[v] with seed seeds[v] (seeds NULL: params->seed for every view).
+ * Contract: view v's out_rgb8 and out_accum equal, bit for bit, what rt_render(scene, &cams[v], params with seed =
+ *   seeds[v], ...) writes, and stats->segments / primary equal the sums over those nviews calls.
+ * Output: out_rgb8 is nviews x height x width x 3 bytes, view-major, row 0 of a view at the top; out_accum (optional) is
+ *   nviews x height x width x 3 f64 radiance sums.
+ * How: one persistent path kernel (rt_radiance_rays') whose path p = ((v * width * height + pixel) * spp + s) takes its
+ *   camera ray from view v's camera in registers.  The views are cut into groups of whole views, one launch per group,
+ *   so that a group's paths fit kMaxPassSlots = 2^31, half of the free device memory (24 bytes per path) and option
+ *   views.max_paths; small views run as one launch.
+ * stats (may be NULL): segments and primary as above, ms = HIP events around the device work, passes = launches of the
+ *   path kernel, samples_per_pass = spp; the other fields are 0 (extend_variant and kernel_lds_mode -1).
+ * Reads width, height, spp, max_depth, seed, background, flags (RT_OUT_DEVICE | RT_GLOBAL_SCENE, nothing else), stream and
+ *   fp_mode; band_count must be 1 (the whole frame; band_rows is not read); samples_per_pass is ignored.
+ * Buffers: host pointers; the call copies through the scene's workspace and blocks.  With RT_OUT_DEVICE out_rgb8 and
+ *   out_accum are device pointers on the scene's device, written in place on params->stream (NULL: the scene's own
+ *   stream, and the call waits).  On a caller's stream the call returns once the work is enqueued when stats is NULL;
+ *   with stats it waits, because the segment count is read back.  In both modes the camera table, the claim counters
+ *   and (spp > 1) the per-path records live in the scene's grow-only workspace, which every call on the scene shares:
+ *   calls on one scene (rt_render, rt_radiance_rays, rt_query_rays on host buffers, this one) must be ordered by the
+ *   caller -- the same stream, or a synchronisation between them.  The first call uploads the scene.
+ * RT_E_INVALID, before any device work: scene, cams or params NULL; nviews < 0; out_rgb8 NULL with nviews > 0; width or
+ *   height < 2; spp < 1; max_depth < 1; band_count != 1; a flag bit other than the two named; stream without
+ *   RT_OUT_DEVICE; width * height * spp of one view above 2^31 (render such a frame with rt_render, which splits it into
+ *   passes).  nviews = 0 is RT_OK and touches nothing.
+ * For many small frames: 64 views of 128 x 128 x 16 take 0.13-0.19 of the time of 64 rt_render calls.  Large frames gain
+ * nothing (1920 x 1080 x 16: 0.94-1.24 of the loop's time): render those with rt_render. */
+int rt_render_views(rt_scene* scene, const rt_camera* cams, const uint64_t* seeds, int32_t nviews, const rt_params* params, uint8_t* out_rgb8,
+                    double* out_accum, rt_stats* stats);
 /* Number of rows a band partition owns, and optionally their global indices (rows_out may be NULL).  Global row y
  * belongs to band set (y / band_rows) % band_count; local row ly of set r is global row
  * (ly / band_rows) * band_rows * band_count + r * band_rows + ly % band_rows. */

@@ -190,6 +190,41 @@ inline void camera_rays(const camera& cam, int width, int height, int k, double*
     check(rt_camera_rays(&cam.raw(), &p, sample_base, device, rays_out, rng_out), "camera_rays");
 }
 
+// Many cameras of one scene in one call (rt_render_views): out_rgb8 receives cams.size() frames of width x height x 3
+// bytes, view-major, each equal to render_engine's frame for that camera bit for bit; out_accum (may be nullptr) the f64
+// sums.  seeds: one per view, or empty for o.seed in every view.  flags: RT_GLOBAL_SCENE, and RT_OUT_DEVICE with `stream`
+// for device buffers.  Every view has the same size, samples and depth; frames of more than 2^31 paths take render_engine.
+struct views_options {
+    int spp = 100, max_depth = 50;
+    std::uint64_t seed = 0;
+    color background;
+    std::int32_t flags = 0;
+    void* stream = nullptr;
+};
+inline void render_views(const scene& world, const std::vector<camera>& cams, int width, int height, std::uint8_t* out_rgb8,
+                         const views_options& o = {}, const std::vector<std::uint64_t>& seeds = {}, double* out_accum = nullptr,
+                         rt_stats* stats = nullptr) {
+    if (!seeds.empty() && seeds.size() != cams.size()) throw std::invalid_argument("render_views: one seed per camera, or none");
+    std::vector<rt_camera> raw;
+    raw.reserve(cams.size());
+    for (const camera& c : cams) raw.push_back(c.raw());
+    rt_params p{};
+    p.width = width;
+    p.height = height;
+    p.spp = o.spp;
+    p.max_depth = o.max_depth;
+    p.seed = o.seed;
+    p.fp_mode = RT_FP64;
+    p.band_rows = height;
+    p.band_count = 1;
+    p.flags = o.flags;
+    p.stream = o.stream;
+    for (int k = 0; k < 3; ++k) p.background[k] = o.background.e[k];
+    check(rt_render_views(world.objects.get(), raw.data(), seeds.empty() ? nullptr : seeds.data(), static_cast<std::int32_t>(raw.size()), &p, out_rgb8,
+                          out_accum, stats),
+          "render_views");
+}
+
 // The engine with a runtime image size (the reference fixes W, H, C at compile time: engine<W,H,C> below); samples
 // per pixel and max depth are the reference's tracer_constants (tracer_constants.h:12-13) as arguments with the same
 // defaults.
