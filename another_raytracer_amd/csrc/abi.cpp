@@ -415,6 +415,22 @@ int rt_render_views(rt_scene* s, const rt_camera* cams, const uint64_t* seeds, i
     });
 }
 
+int rt_tile_candidates(rt_scene* s, const rt_camera* cam, const rt_params* p, uint16_t* counts_out, int64_t cap) {
+    std::string why;
+    if (!s || !cam) return fail(RT_E_INVALID, "rt_tile_candidates: scene and camera must be non-NULL");
+    if (!valid_params(p, why)) return fail(RT_E_INVALID, why);
+    if (counts_out && cap < 0) return fail(RT_E_INVALID, "rt_tile_candidates: cap must be >= 0");
+    if (counts_out) {
+        const int64_t rows = art::band_local_rows(p->height, p->band_rows, p->band_count, p->band_index);
+        const int64_t tiles = static_cast<int64_t>((p->width + 7) / 8) * ((rows + 7) / 8);
+        if (cap < tiles) return fail(RT_E_INVALID, "rt_tile_candidates: counts_out holds " + std::to_string(cap) + " entries, the frame has " +
+                                                       std::to_string(tiles) + " tiles");
+    }
+    return guard(RT_E_DEVICE, [&] {
+        return s->device_renderer().tile_candidates(camera_of(cam), render_params(p), counts_out, static_cast<size_t>(counts_out ? cap : 0));
+    });
+}
+
 int rt_camera_rays(const rt_camera* cam, const rt_params* p, uint32_t sample_base, int device, double* rays_out, uint64_t* rng_out) {
     std::string why;
     if (!cam || !rays_out) return fail(RT_E_INVALID, "rt_camera_rays: camera and rays_out must be non-NULL");

@@ -20,6 +20,7 @@ struct DeviceScene {
     bool tex_basic = false;                          // only solid and checker textures
     bool lds_scene = false;                          // view.lds_image holds the layout.h LDS scene image
     bool lds_shade = false;                          // ... including a complete shading table (fused variant)
+    uint32_t tile_reps = 0;                          // > 0: the representative slots behind the image (tile_lists.h TileReps)
     bool codes16 = false;                            // every node's child codes fit BvhNode::pad's 16-bit form
     uint32_t leaf_shift = 0;                         // 1: 16-bit leaf codes count slot pairs (F_LEAF2; leaves on even slots)
     bool tex_bary = false;                           // image textures are barycentric ones on triangles only (TF_BARY)

@@ -8,14 +8,16 @@
 #include <unordered_map>
 
 #include "options.h"
+#include "tile_lists.h"
 
 namespace art {
 
 // Builds the layout.h LDS scene image when the f64 scene qualifies: spheres only, every BVH node and leaf slot within
 // the plane capacities, and image + stack within one CU's LDS.  Returns an empty vector otherwise.
-static std::vector<uint8_t> lds_scene_image(const FlatScene& f, uint32_t& nmov, bool& shade_ok) {
+static std::vector<uint8_t> lds_scene_image(const FlatScene& f, uint32_t& nmov, bool& shade_ok, uint32_t& tile_reps) {
     std::vector<uint8_t> img;
     nmov = 0;
+    tile_reps = 0;
     shade_ok = false;
     if ((f.features & ~kFeatSpheres) != 0 || f.nodes.empty() || f.nodes.size() > kLdsNodeCap || f.primrefs.size() > kLdsSlotCap ||
         f.world.size() > kPathsWorldCap || f.objs.size() > kPathsWorldCap ||
@@ -126,6 +128,32 @@ static std::vector<uint8_t> lds_scene_image(const FlatScene& f, uint32_t& nmov, 
         put(kLdsOffMatIdx + sl * 2, &mi, 2);
     }
     if (nent > kLdsMatCap) shade_ok = false;
+    // Behind the image: one representative slot per sphere (tile_lists.h TileReps; spatial splits put a sphere into
+    // several leaves), the lowest slot whose index field names it.  k_paths' tile lists test representatives only and
+    // shade by them, so every slot of a sphere must hold the representative's bytes in every per-slot plane; the
+    // world holds nothing but BVHs over these slots (checked above).  Otherwise n stays 0: no lists.
+    TileReps reps{};
+    {
+        std::unordered_map<uint32_t, uint32_t> first;  // sphere index -> representative slot
+        bool same = shade_ok;
+        auto eq = [&](uint32_t off, uint32_t stride, uint32_t a, uint32_t b) { return std::memcmp(img.data() + off + a * stride, img.data() + off + b * stride, stride) == 0; };
+        for (uint32_t sl = 0; sl < f.primrefs.size(); ++sl) {
+            const uint32_t idx = primref_index(f.primrefs[sl]);
+            const auto it = first.find(idx);
+            if (it == first.end()) {
+                first.emplace(idx, sl);
+                reps.slot[reps.n++] = static_cast<uint16_t>(sl);
+                continue;
+            }
+            const uint32_t r = it->second;
+            same = same && eq(kLdsOffSph, 16, sl, r) && eq(kLdsOffSph + kLdsSlotCap * 16, 16, sl, r) && eq(kLdsOffMov, 8, sl, r) &&
+                   eq(kLdsOffRef, 4, sl, r) && eq(kLdsOffMatIdx, 2, sl, r) && eq(kLdsOffInvR, 8, sl, r);
+        }
+        if (!same) reps.n = 0;
+    }
+    img.resize(kLdsImageBytes + sizeof(TileReps));
+    std::memcpy(img.data() + kLdsImageBytes, &reps, sizeof reps);
+    tile_reps = reps.n;
     return img;
 }
 
@@ -333,7 +361,9 @@ void build_device_scene(const FlatScene& f0, DeviceScene& ds) {
     {
         uint32_t nmov = 0;
         bool shade_ok = false;
-        const std::vector<uint8_t> img = ds.leaf_shift ? std::vector<uint8_t>() : lds_scene_image(f, nmov, shade_ok);
+        uint32_t tile_reps = 0;
+        const std::vector<uint8_t> img = ds.leaf_shift ? std::vector<uint8_t>() : lds_scene_image(f, nmov, shade_ok, tile_reps);
+        ds.tile_reps = img.empty() ? 0 : tile_reps;
         if (!img.empty()) {
             ds.view.lds_image = ds.upload(img);
             ds.lds_scene = true;

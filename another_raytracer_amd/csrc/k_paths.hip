@@ -3,6 +3,7 @@
 #include "launch.h"
 #include "path_pool.h"
 #include "path_work.h"
+#include "tile_lists.h"
 
 namespace art {
 
@@ -55,8 +56,9 @@ struct PathPool {
     }
     // Claims the next 64 slots and generates their camera rays: true for a lane whose slot is a pixel of the pass
     // (st: the new path, q: its slot); a padding slot of a partial tile or a slot >= P does nothing.
+    // tile: the batch's 8x8 tile in sample-major passes (wave-uniform: its 64 slots are one tile's pixels).
     __device__ __forceinline__ bool batch(const PassGeom& sg, const CameraRec& sc, uint32_t* next_slot, uint32_t lane, PathState& st,
-                                          uint32_t& q) {
+                                          uint32_t& q, uint32_t& tile) {
         if (cur == end) {
             const uint32_t chunk = sg.chunk;
             uint32_t nb = 0;
@@ -73,6 +75,7 @@ struct PathPool {
         int lx, ly;
         uint32_t qi, j;
         slot_split(sg, q, qi, j);
+        tile = __builtin_amdgcn_readfirstlane(qi >> 6);  // the whole wave is here
         if (!(q < sg.P && slot_pixel(sg, qi, lx, ly))) return false;
         cam_ray(sg, sc, j, lx, ly, st.ray, st.rng);
         st.T = mk(1.0, 1.0, 1.0);
@@ -107,6 +110,38 @@ struct PathPool {
         depth = static_cast<int>(e.depth);
     }
 };
+// A batch's trace over its tile's record (tile_lists.h TileRec, as eight wave-uniform dwords: the count, then up to
+// kTileK leaf slots, nearest first) instead of the tree: every active lane tests the record's slots in order on
+// [0.001, closest], the interval and the leaf test of the world walk.  The record holds every sphere a camera ray of
+// the tile can reach, and sphere_root's candidate root (the near root if >= tmin, else the far one) is accepted iff
+// it is <= the current tmax, so the nearest accepted root over this superset is the one the traversal finds, whatever
+// the order; all slots of a sphere hold the same bytes (device_scene.hip), so shading by the representative gives the
+// same bits.  No stack, no node planes.
+typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ bool trace_tile_list(const uint8_t* lds, const Ray& r, u32x8 rec, double& t, HitOut& h) {
+    const double d_a = len2(r.d), d_inv_a = 1.0 / d_a;  // traverse()'s
+    uint64_t q0 = rec[0] | (static_cast<uint64_t>(rec[1]) << 32), q1 = rec[2] | (static_cast<uint64_t>(rec[3]) << 32);
+    uint64_t q2 = rec[4] | (static_cast<uint64_t>(rec[5]) << 32), q3 = rec[6] | (static_cast<uint64_t>(rec[7]) << 32);
+    const uint32_t n = static_cast<uint32_t>(q0) & 0xFFFFu;
+    double closest = __builtin_inf();
+    bool any = false;
+    for (uint32_t k = 0; k < n; ++k) {
+        q0 = (q0 >> 16) | (q1 << 48), q1 = (q1 >> 16) | (q2 << 48), q2 = (q2 >> 16) | (q3 << 48), q3 >>= 16;
+        const uint32_t slot = static_cast<uint32_t>(q0) & 0xFFFFu;
+        double tt;
+        uint32_t prim, mt;
+        if (hit_lds_slot(lds, slot, r, d_a, d_inv_a, 0.001, closest, tt, prim, mt)) {
+            closest = tt;
+            any = true;
+            h.prim = prim;
+            h.obj = slot << 16;
+            h.mt = mt;
+        }
+    }
+    t = closest;
+    return any;
+}
+
 __global__ __launch_bounds__(kBlockL, 1) void k_paths(DevScene S0, PassGeom g, CameraRec cam, Work w, uint32_t* next_slot) {
     constexpr int B = kBlockL;
     // dynamic LDS only (no static __shared__, so the image starts at LDS address 0 and every image offset is an
@@ -153,6 +188,8 @@ __global__ __launch_bounds__(kBlockL, 1) void k_paths(DevScene S0, PassGeom g, C
 #ifdef ART_STATS
     unsigned long long tm_load = 0, tm_trace = 0, tm_shade = 0, tm_app = 0, tm_fb = 0, tm_prev = __builtin_amdgcn_s_memtime();
 #endif
+    const bool lists = w.tiles != nullptr && g.list == nullptr;  // tile-order slots only (pixel lists keep the tree)
+    uint32_t tile = 0;
     PathPool pp;
     pp.init(w.pool, blockIdx.x, gridDim.x, B / 64, threadIdx.x / 64);
     for (;;) {
@@ -170,7 +207,7 @@ __global__ __launch_bounds__(kBlockL, 1) void k_paths(DevScene S0, PassGeom g, C
             if (lane == 0) atomicAdd(&g_art_stats[51], static_cast<unsigned long long>(__popcll(m_busy)));
 #endif
             if (m_busy) pp.push(m_busy, static_cast<uint32_t>(__popcll(m_busy & below)), busy, st, q, depth);
-            act = pp.batch(s_g, s_cam, next_slot, lane, st, q);
+            act = pp.batch(s_g, s_cam, next_slot, lane, st, q, tile);
             depth = 0;
         } else {
             const uint32_t npop = pool_pop_count(pp.count, n_idle);
@@ -193,7 +230,15 @@ __global__ __launch_bounds__(kBlockL, 1) void k_paths(DevScene S0, PassGeom g, C
         bool hitw = false;
         if (act) {
             ++segs;
-            hitw = trace_world<kFeatSpheres, B, true>(S, lds, st.ray, stk, st.rng, t, h);
+            // a batch of a pass with tile lists (whole-image sample-major passes: Work::tiles) reads its tile's record
+            // with one scalar load (constant address space: written by k_tile_lists before the launch); an overflow
+            // tile, and every ordinary round, walks the tree
+            u32x8 rec = {kTileOverflow, 0, 0, 0, 0, 0, 0, 0};
+            if (fb && lists)
+                rec = *(reinterpret_cast<const __attribute__((address_space(4))) u32x8*>(reinterpret_cast<uintptr_t>(w.tiles)) +
+                        __builtin_amdgcn_readfirstlane(tile));
+            if ((rec[0] & 0xFFFFu) != kTileOverflow) hitw = trace_tile_list(lds, st.ray, rec, t, h);
+            else hitw = trace_world<kFeatSpheres, B, true>(S, lds, st.ray, stk, st.rng, t, h);
 #if ART_LDS_LEAF_NOREF
             if (hitw) h.mt = reinterpret_cast<const uint32_t*>(lds + kLdsOffRef)[h.obj >> 16] >> kLdsRefMatShift;
 #endif

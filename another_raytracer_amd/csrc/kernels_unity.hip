@@ -4,5 +4,6 @@
 #include "k_paths.hip"
 #include "k_paths_g_mesh.hip"
 #include "radiance_rays.hip"
+#include "tile_lists.hip"
 #include "device_scene.hip"
 #include "renderer.hip"

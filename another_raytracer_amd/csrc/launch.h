@@ -91,6 +91,9 @@ void launch_camera_rays(hipStream_t st, const PassGeom& g, const CameraRec& cam,
 // k_paths.hip
 void launch_paths(int num_cu, hipStream_t st, const DevScene& S, const PassGeom& g, const CameraRec& cam, const Work& w,
                   uint32_t* next_slot);
+// tile_lists.hip: fills one TileRec (tile_lists.h) per 8x8 tile of g's frame geometry for `cam`; S holds an LDS scene
+// image with representative slots (DeviceScene::tile_reps > 0)
+void launch_tile_lists(hipStream_t st, const DevScene& S, const PassGeom& g, const CameraRec& cam, void* tiles);
 size_t pool_bytes(int variant, int num_cu);  // the path pools of `variant` (k_paths' PathPool, kPoolCap entries per wave; 0 for every other)
 
 }  // namespace art

@@ -32,6 +32,8 @@ enum class Opt : int {
                      // sorting network (0, default: measured faster) or nearest first (1); the same answers either way (A/B)
     ViewsMaxPaths,   // views.max_paths: cap on the paths of one rt_render_views launch, i.e. on the views of a group (0,
                      // default: off; a group is never less than one view; diagnostic: the results do not depend on it)
+    TileLists,       // render.tile_lists: k_paths' batches test a per-tile sphere list instead of walking the tree (tile_lists.h):
+                     // 0 off, 1 (default) when a pass holds enough samples per pixel to pay for the table, 2 always
     // multi-GPU
     MultiTimeoutMs,  // multi.timeout_ms: deadline of RCCL init / gather waits (unset: ART_MULTI_TIMEOUT_MS, else 120000;
                      // inf, or anything beyond ~292 years, means no deadline)

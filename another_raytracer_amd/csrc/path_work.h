@@ -146,6 +146,7 @@ struct Work {
     unsigned long long* segments;
     double* acc;                // local pixels * 3
     void* pool;                 // k_paths path pools: the paths a batch displaces, kPoolCap PoolRays per wave (path_pool.h)
+    const void* tiles;          // k_paths: one TileRec per 8x8 tile of the pass geometry (tile_lists.h), or null: no lists
 };
 __host__ __device__ __forceinline__ uint32_t* counter(const Work& w, int d, int kind, int s) {
     return w.counters + (static_cast<size_t>((d * kQueueKinds + kind) * kShards + s)) * kCounterStride;

@@ -88,6 +88,11 @@ public:
     // pixel are optional; host buffers, or device ones with RT_OUT_DEVICE.
     void render_noise_target(const CameraRec& cam, const RenderParams& p, const NoiseParams& np, uint8_t* out_rgb, double* out_acc,
                              int32_t* out_count, double* out_moments, RenderStats& stats, NoiseResult& result);
+    // rt_tile_candidates: the tile lists render() would build for this camera and these parameters (tile_lists.h), as
+    // one count per 8x8 tile of the local rows in tile order (kTileOverflow for a tile that walks the tree).  Returns
+    // the number of tiles, or 0 when render() would build no lists (the scene, the option, the mode or the sample
+    // count).  counts may be null (the number only); otherwise it holds at least `cap` >= tiles entries.
+    int tile_candidates(const CameraRec& cam, const RenderParams& p, uint16_t* counts, size_t cap);
     int device() const;
     size_t scene_bytes() const;
     const FlatScene& flat() const;

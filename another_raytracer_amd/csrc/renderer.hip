@@ -18,6 +18,7 @@
 #include "launch.h"
 #include "options.h"
 #include "pass_plan.h"
+#include "tile_lists.h"
 #include "view_plan.h"
 #include "workspace.h"
 
@@ -87,6 +88,16 @@ static PassGeom make_pass_geom(const RenderParams& p, int nrows, uint32_t stack)
     g.inv_h1 = 1.0 / static_cast<double>(p.height - 1);
     g.stack = stack;
     return g;
+}
+// Does a whole-image render of k samples per pass build k_paths' tile lists (option render.tile_lists)?  Only the LDS
+// scene's persistent kernel reads them, and only a scene whose image carries representative slots gets them.  Auto:
+// when the table's one launch stays below 1 % of a pass.  Both scale with the tile count, so the rule is a sample count:
+// k_tile_lists takes 168 microseconds per 1920x1080 frame and scene 1 traces 0.26 ms per sample there: 0.9 % at 72
+// (DESIGN 4.1).
+constexpr uint32_t kTileListsAutoSpp = 72;
+static bool tile_lists_wanted(const DeviceScene& ds, int variant, uint32_t k) {
+    const int mode = static_cast<int>(opt(Opt::TileLists));
+    return variant == EXT_MEGA && ds.tile_reps > 0 && (mode == 2 || (mode == 1 && k >= kTileListsAutoSpp));
 }
 // The wavefront variants' queue counters: a line per depth (at least 4: the device-counted adaptive levels take one each)
 static size_t counter_words(int max_depth) { return static_cast<size_t>(std::max(max_depth + 1, 4)) * kQueueKinds * kShards * kCounterStride; }
@@ -412,6 +423,7 @@ void Renderer::render(const CameraRec& cam, const RenderParams& p, uint8_t* out_
 #ifdef ART_TRACE
     trace_setup();
 #endif
+    TileRec* tile_tab = nullptr;
     if (!begin_frame(f, stats, b.spp_t, true, adaptive ? 4 : 1, [&](Carver& c) {
         const bool wf = !f.mega;  // wavefront-only buffers
         f.w.paths = c.take<PathRec>(f.Pmax, wf);
@@ -427,6 +439,7 @@ void Renderer::render(const CameraRec& cam, const RenderParams& p, uint8_t* out_
         double* qsum = c.take<double>(3 * f.local_pix, images);
         b.qsum = images ? qsum : nullptr;
         f.w.pool = c.take<char>(pool_bytes(f.variant, I.num_cu));
+        tile_tab = c.take<TileRec>(f.g.npix_pad / 64u, !adaptive && tile_lists_wanted(f.ds, f.variant, f.k));
         b.ad_work = c.take<int32_t>(3 * f.local_pix, adaptive);
         b.ad_lists = c.take<uint32_t>(f.local_pix + 4 * 64, adaptive);
         b.ad_f0 = c.take<uint8_t>(21 * (f.local_pix / (kBig * kBig)), adaptive);  // 1 + 4 + 16 flags per big square
@@ -436,11 +449,46 @@ void Renderer::render(const CameraRec& cam, const RenderParams& p, uint8_t* out_
     b.sqx = p.width / kBig, b.nsq = static_cast<uint32_t>(b.sqx) * static_cast<uint32_t>(f.nrows / kBig);
     uint32_t ad_counts[4] = {0, 0, 0, 0};  // the device-counted levels' entry counts (read back with the frame)
     uint64_t primary = 0;
+    // the tile lists of this call's camera and geometry (nothing is kept across calls), before the first pass; the
+    // adaptive levels' passes are pixel lists and keep the tree
+    if (!adaptive && p.max_depth > 0 && tile_lists_wanted(f.ds, f.variant, f.k)) {
+        launch_tile_lists(f.stream, f.ds.view, f.g, cam, tile_tab);
+        f.w.tiles = tile_tab;
+    }
     if (!adaptive) primary = render_whole(f, b);
     else if (f.mega && f.k == static_cast<uint32_t>(b.spp_t) && !images && !p.on_pass) adaptive_device_counted(f, b, ad_counts);
     else primary = adaptive_host_counted(f, b);
     end_frame(f, stats, out_rgb, adaptive ? nullptr : out_acc);
     stats.primary = primary + (static_cast<uint64_t>(ad_counts[0]) + ad_counts[1] + ad_counts[2] + ad_counts[3]) * static_cast<uint64_t>(b.spp_t);
+}
+
+int Renderer::tile_candidates(const CameraRec& cam, const RenderParams& p, uint16_t* counts, size_t cap) {
+    upload();
+    Impl& I = *impl_;
+    DeviceScene& ds = I.s64;
+    const int nrows = band_local_rows(p.height, p.band_rows, p.band_count, p.band_index);
+    if (nrows == 0 || p.max_depth <= 0 || (p.flags & RT_ADAPTIVE)) return 0;
+    const PassGeom g = make_pass_geom(p, nrows, stack_rows(ds.max_stack));
+    if (g.npix_pad > kMaxPassSlots) throw std::runtime_error("image too large for one pass (more than 2^31 padded pixels)");
+    const int variant = extend_variant(ds, p.flags);
+    // the samples per pass begin_frame would plan for a persistent kernel
+    size_t free_b = 0, total_b = 0;
+    HIP_OK(hipMemGetInfo(&free_b, &total_b));
+    const int spp_t = (p.flags & RT_PARALLEL_IMAGES) ? 4 * (p.spp / 4) : p.spp;
+    const PassPlan plan = plan_passes((free_b + I.ws.size()) / 2 / sizeof(ResRec), p.samples_per_pass, g.npix_pad, spp_t, true);
+    if (!tile_lists_wanted(ds, variant, plan.k)) return 0;
+    const size_t ntiles = g.npix_pad / 64u;
+    if (!counts) return static_cast<int>(ntiles);
+    if (cap < ntiles) throw std::runtime_error("rt_tile_candidates: counts holds fewer entries than the frame has tiles");
+    Carver c(I.ws.reserve(sizeof(TileRec) * ntiles));
+    TileRec* tab = c.take<TileRec>(ntiles);
+    launch_tile_lists(I.own_stream, ds.view, g, cam, tab);
+    HIP_OK(hipGetLastError());
+    std::vector<TileRec> host(ntiles);
+    HIP_OK(hipMemcpyAsync(host.data(), tab, sizeof(TileRec) * ntiles, hipMemcpyDeviceToHost, I.own_stream));
+    HIP_OK(hipStreamSynchronize(I.own_stream));
+    for (size_t i = 0; i < ntiles; ++i) counts[i] = host[i].n;
+    return static_cast<int>(ntiles);
 }
 
 void Renderer::upload() {

@@ -202,6 +202,24 @@ class engine:
         self.stats = st.as_dict()
         return int(round(st.ms))
 
+    def tile_candidates(self, band_rows=None, band_count=1, band_index=0):
+        """rt_tile_candidates: the per-tile sphere lists run() would build (option render.tile_lists: 0 off, 1 when a
+        pass holds at least 72 samples per pixel, 2 always), as a uint16 array (tile rows, tile columns) of candidate
+        counts, 0xFFFF for a tile with more than 15 spheres, whose batches walk the tree; None when run() builds no
+        lists (the scene, the option, the mode or the sample count)."""
+        if self._scene is None:
+            raise ValueError("no scene set")
+        flags = ((RT_GLOBAL_SCENE if self.global_scene else 0) | (RT_SPLIT_SHADE if self.split_shade else 0)
+                 | (RT_ADAPTIVE if self.m == engine_mode.adaptive else 0)
+                 | (RT_PARALLEL_IMAGES if self.m == engine_mode.parallel_images else 0) | (RT_WAVEFRONT if self.wavefront else 0))
+        p = self.params(band_rows, band_count, band_index, flags)
+        rows = check(lib.rt_local_rows(ctypes.byref(p), None), "rt_local_rows")
+        tx, ty = (self.width + 7) // 8, (rows + 7) // 8
+        counts = np.zeros((ty, tx), np.uint16)
+        n = check(lib.rt_tile_candidates(self._scene, ctypes.byref(self.cam.c), ctypes.byref(p), ctypes.c_void_p(counts.ctypes.data), tx * ty),
+                  "engine.tile_candidates")
+        return counts if n else None
+
     def render_guides(self, guides=None, rays=None, band_rows=None, band_count=1, band_index=0, stream=None):
         """First-hit guide buffers (rt_render_guides): float64 (local_rows, W, 10) = albedo, normal, position, t of the
         pixel-centre ray of every local pixel (a miss: t = position = inf, normal 0, albedo 1).  `guides` / `rays`

@@ -70,7 +70,8 @@ extern "C" {
  * rt_query_params, RT_Q_ANY_HIT, RT_Q_NO_MEDIA, RT_HIT_DOUBLES (ray queries with the hit record, a per-ray t_max, occlusion
  * queries, device buffers and a caller's stream), option query.any_sorted; rt_radiance_rays, rt_radiance_params (path-traced
  * radiance along caller-given rays), rt_camera_rays (the renderer's camera rays and post-camera RNG states as data);
- * rt_render_views (many cameras of one scene in one persistent launch), option views.max_paths. */
+ * rt_render_views (many cameras of one scene in one persistent launch), option views.max_paths; rt_tile_candidates (the
+ * per-tile sphere lists of a render, as counts), option render.tile_lists. */
 #define RT_ABI_VERSION 5
 
 /* return codes */
@@ -179,6 +180,9 @@ int rt_device_count(void);
  *   sorting network; 1 = nearest first; the answers are identical either way, DESIGN.md 4.7 measured both);
  *   views.max_paths (0 = off; N caps the paths of one rt_render_views launch, so the views run in groups of
  *   floor(N / (width * height * spp)) views, at least one; diagnostic: the frames are identical either way);
+ *   render.tile_lists (1; the batches of 64 camera rays of the LDS-scene path kernel test a per-tile list of the spheres
+ *   their 8x8 tile can reach instead of walking the tree: 0 = off, 1 = when a pass holds at least 72 samples per pixel, so
+ *   that the table's one launch per rt_render call is below 1 % of it, 2 = always; the frames are identical either way);
  *   multi.timeout_ms (the RCCL deadline; inf = none), multi.rccl_blocking (0; 1 = blocking communicators, diagnosis:
  *   gives up the deadline and the error-path protection);
  *   test.fault_workspace_bytes (0 = off; N refuses workspace growth beyond N bytes), test.fault_gather_abort (0; 1 = the
@@ -314,6 +318,14 @@ int rt_radiance_rays(rt_scene* scene, const rt_radiance_params* q, const double*
  * buffers on `device`, written on params->stream (the call returns once enqueued; NULL: the default stream, and the call
  * waits).  RT_E_INVALID also when the padded local pixels (8x8 tiles) times k exceed 2^31: fewer samples per call. */
 int rt_camera_rays(const rt_camera* cam, const rt_params* params, uint32_t sample_base, int device, double* rays_out, uint64_t* rng_out);
+/* rt_tile_candidates (additive since ABI 5): the tile lists rt_render(scene, cam, params, ...) would build (option
+ * render.tile_lists), as data: counts_out[i] = the number of spheres the camera rays of 8x8 tile i of the local rows can
+ * reach (tiles in row-major order, (width + 7) / 8 per row), or 0xFFFF for a tile with more than 15, whose batches walk
+ * the tree.  Returns the number of tiles, or 0 when that render builds no lists: the scene is not a spheres-only scene
+ * traced from LDS, the option is 0, the mode is RT_ADAPTIVE, or (option 1) a pass holds fewer than 72 samples per pixel.
+ * counts_out may be NULL (the number only); otherwise it holds `cap` entries, RT_E_INVALID when that is fewer than the
+ * tiles.  Host buffer, blocking.  The diagnostic of a caller whose scene gains nothing: many 0xFFFF tiles or none at all. */
+int rt_tile_candidates(rt_scene* scene, const rt_camera* cam, const rt_params* params, uint16_t* counts_out, int64_t cap);
 /* rt_render_views (additive since ABI 5): nviews whole frames of one scene in one call -- an orbit of a mesh, the six faces of
  * a cube map, a light field -- where a loop of rt_render pays a workspace reset, a launch per pass, the accumulation, a
  * host wait and a copy per frame.  Every view has params->width x height, spp, max_depth and background; view v looks
