@@ -85,6 +85,10 @@ class rt_query_params(ctypes.Structure):  # zero-initialised = closest hit, host
     _fields_ = [("flags", ctypes.c_int32), ("reserved", ctypes.c_int32), ("stream", ctypes.c_void_p)]
 
 
+class rt_update_params(ctypes.Structure):  # zero-initialised = host buffer, the scene's stream
+    _fields_ = [("flags", ctypes.c_int32), ("reserved", ctypes.c_int32), ("stream", ctypes.c_void_p)]
+
+
 class rt_radiance_params(ctypes.Structure):  # zero-initialised + max_depth = host buffers, seed 0, spp 1
     _fields_ = [("flags", ctypes.c_int32), ("spp", ctypes.c_int32), ("max_depth", ctypes.c_int32), ("sample_base", ctypes.c_uint32),
                 ("seed", ctypes.c_uint64), ("id_base", ctypes.c_uint64), ("stream", ctypes.c_void_p), ("background", ctypes.c_double * 3)]
@@ -118,6 +122,9 @@ SIGNATURES = {
     "rt_scene_destroy": (None, [_P]),
     "rt_scene_save": (_I, [_P, ctypes.c_char_p]),
     "rt_scene_load": (_I, [ctypes.c_char_p, _I, ctypes.POINTER(_P)]),
+    "rt_scene_triangles_get": (ctypes.c_int64, [_P, _P, ctypes.c_int64]),
+    "rt_scene_update_triangles": (_I, [_P, ctypes.POINTER(rt_update_params), _P, ctypes.c_int64, ctypes.c_int64, _DP]),
+    "rt_scene_bvh_get": (_I, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     "rt_render": (_I, [_P, ctypes.POINTER(rt_camera), ctypes.POINTER(rt_params), _P, _P, ctypes.POINTER(rt_stats)]),
     "rt_render_progressive": (_I, [_P, ctypes.POINTER(rt_camera), ctypes.POINTER(rt_params), _P, _P, rt_progress_fn, _P,
                                    ctypes.POINTER(rt_stats)]),

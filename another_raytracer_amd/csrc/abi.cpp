@@ -33,6 +33,17 @@ struct rt_scene {
     int device = 0;
     std::unique_ptr<art::Renderer> renderer;  // created on first render (scene build/dump works without a GPU)
     art::Renderer& device_renderer() { return renderer ? *renderer : *(renderer = std::make_unique<art::Renderer>(flat, device)); }
+    // rt_scene_update_triangles leaves `flat` stale: the renderer counts the updates, and whoever reads the vertices or
+    // the boxes of `flat` (rt_scene_triangles_get, rt_scene_save) takes them from the device first
+    uint64_t synced = 0;
+    bool updated() const { return renderer && renderer->generation() > 0; }
+    void sync_flat() {
+        if (!renderer || renderer->generation() == synced) return;
+        const art::FlatScene& now = renderer->current_flat();
+        flat.tris = now.tris;
+        flat.nodes = now.nodes;
+        synced = renderer->generation();
+    }
 };
 struct rt_graph {
     art::SceneGraph g;
@@ -208,6 +219,10 @@ size_t rt_scene_dump(const rt_scene* s, char* buf, size_t cap) {
         fail(RT_E_INVALID, "a scene loaded from a flat-scene file has no object graph to dump");
         return 0;
     }
+    if (s->updated()) {
+        fail(RT_E_SCENE, "the scene's triangles were updated (rt_scene_update_triangles): its object graph no longer describes it");
+        return 0;
+    }
     try {
         std::string d = art::dump_scene(s->graph);
         if (buf && cap) {
@@ -225,8 +240,62 @@ size_t rt_scene_dump(const rt_scene* s, char* buf, size_t cap) {
 int rt_scene_save(const rt_scene* s, const char* path) {
     if (!s || !path) return fail(RT_E_INVALID, "scene and path must be non-NULL");
     return guard(RT_E_INVALID, [&] {
+        const_cast<rt_scene*>(s)->sync_flat();  // an updated scene is saved as the device holds it
         art::save_scene_file(path, s->flat, s->view);
         return RT_OK;
+    });
+}
+
+int64_t rt_scene_triangles_get(rt_scene* s, double* p_out, int64_t cap) {
+    if (!s) return fail(RT_E_INVALID, "rt_scene_triangles_get: scene is NULL");
+    const int64_t count = static_cast<int64_t>(s->flat.tris.size());
+    if (!p_out) return count;
+    if (cap < count) return fail(RT_E_INVALID, "rt_scene_triangles_get: p_out holds " + std::to_string(cap) + " triangles, the scene has " + std::to_string(count));
+    const int rc = guard(RT_E_DEVICE, [&] {
+        s->sync_flat();
+        return RT_OK;
+    });
+    if (rc != RT_OK) return rc;
+    for (int64_t t = 0; t < count; ++t) std::memcpy(p_out + 9 * t, s->flat.tris[static_cast<size_t>(t)].p, 9 * sizeof(double));
+    return count;
+}
+
+int rt_scene_update_triangles(rt_scene* s, const rt_update_params* u, const double* p, int64_t first, int64_t n, double* ms) {
+    if (!s || !u) return fail(RT_E_INVALID, "rt_scene_update_triangles: scene and params must be non-NULL");
+    const int64_t count = static_cast<int64_t>(s->flat.tris.size());
+    if (first < 0 || n < 0 || first > count || n > count - first)
+        return fail(RT_E_INVALID, "rt_scene_update_triangles: [first, first + n) must lie within the scene's " + std::to_string(count) + " triangles");
+    if (u->flags & ~RT_OUT_DEVICE) return fail(RT_E_INVALID, "rt_scene_update_triangles takes RT_OUT_DEVICE only");
+    if (u->stream && !(u->flags & RT_OUT_DEVICE))
+        return fail(RT_E_INVALID, "rt_scene_update_triangles: stream needs RT_OUT_DEVICE (host buffers run on the scene's own stream)");
+    if (n > 0 && !p) return fail(RT_E_INVALID, "rt_scene_update_triangles: p is NULL");
+    const bool device = (u->flags & RT_OUT_DEVICE) != 0;
+    if (!device)
+        for (int64_t i = 0; i < 9 * n; ++i)
+            if (!std::isfinite(p[i]))
+                return fail(RT_E_INVALID, "rt_scene_update_triangles: vertex value " + std::to_string(i % 9) + " of triangle " + std::to_string(first + i / 9) + " is not finite");
+    if (ms) *ms = 0;
+    if (n == 0) return RT_OK;
+    return guard(RT_E_DEVICE, [&] {
+        s->device_renderer().update_triangles(p, static_cast<size_t>(first), static_cast<size_t>(n), device, u->stream, ms);
+        return RT_OK;
+    });
+}
+
+int rt_scene_bvh_get(rt_scene* s, void* nodes_out, int64_t node_cap, uint32_t* primrefs_out, int64_t ref_cap, int64_t* n_nodes, int64_t* n_primrefs) {
+    if (!s) return fail(RT_E_INVALID, "rt_scene_bvh_get: scene is NULL");
+    return guard(RT_E_DEVICE, [&] {
+        size_t nn = 0, nr = 0;
+        art::Renderer& r = s->device_renderer();
+        r.bvh_get(nullptr, nullptr, nn, nr);
+        if (n_nodes) *n_nodes = static_cast<int64_t>(nn);
+        if (n_primrefs) *n_primrefs = static_cast<int64_t>(nr);
+        if (nodes_out && node_cap < static_cast<int64_t>(nn))
+            return fail(RT_E_INVALID, "rt_scene_bvh_get: nodes_out holds " + std::to_string(node_cap) + " nodes, the scene has " + std::to_string(nn));
+        if (primrefs_out && ref_cap < static_cast<int64_t>(nr))
+            return fail(RT_E_INVALID, "rt_scene_bvh_get: primrefs_out holds " + std::to_string(ref_cap) + " references, the scene has " + std::to_string(nr));
+        if (nodes_out || primrefs_out) r.bvh_get(nodes_out, primrefs_out, nn, nr);
+        return static_cast<int>(RT_OK);
     });
 }
 

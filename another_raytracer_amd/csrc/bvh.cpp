@@ -1,6 +1,7 @@
 // bvh.cpp — full-sweep SAH binary tree, collapsed into the 4-wide node array of layout.h (see bvh.h).
 #include "bvh.h"
 #include "options.h"
+#include "refit.h"
 
 #include <algorithm>
 #include <array>
@@ -470,16 +471,7 @@ int32_t collapse(const std::vector<BNode>& tree, int bn, std::vector<BvhNode>& o
 }  // namespace
 
 void conservative_box(const AABBd& b, float lo[3], float hi[3]) {
-    for (int k = 0; k < 3; ++k) {
-        float l = static_cast<float>(b.mn[k]);
-        float h = static_cast<float>(b.mx[k]);
-        if (static_cast<double>(l) > b.mn[k]) l = std::nextafter(l, -std::numeric_limits<float>::infinity());
-        if (static_cast<double>(h) < b.mx[k]) h = std::nextafter(h, std::numeric_limits<float>::infinity());
-        // relative pad: covers f32 rounding of the ray origin/direction and of the slab arithmetic
-        float pad = 1e-6f * std::max(std::max(std::fabs(l), std::fabs(h)), h - l) + 1e-30f;
-        lo[k] = l - pad;
-        hi[k] = h + pad;
-    }
+    conservative_box(b.mn.e, b.mx.e, lo, hi);  // refit.h: the text the device's refit runs too
 }
 
 int32_t build_sah_bvh(const std::vector<AABBd>& boxes, const std::vector<uint32_t>& refs, std::vector<BvhNode>& nodes,

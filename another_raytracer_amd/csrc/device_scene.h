@@ -25,6 +25,12 @@ struct DeviceScene {
     uint32_t leaf_shift = 0;                         // 1: 16-bit leaf codes count slot pairs (F_LEAF2; leaves on even slots)
     bool tex_bary = false;                           // image textures are barycentric ones on triangles only (TF_BARY)
     size_t bytes = 0;
+    // rt_scene_update_triangles: the host copy of view.primrefs (slot_pad[i]: slot i belongs to no leaf), and what the
+    // scene's first update makes: the f64 box of every slot's primitive on the device and the level ranges of the nodes
+    std::vector<uint32_t> slot_refs;
+    std::vector<uint8_t> slot_pad;
+    double* slot_box = nullptr;
+    std::vector<uint32_t> level_begin;
 
     template <class T>
     const T* upload(const std::vector<T>& v) {

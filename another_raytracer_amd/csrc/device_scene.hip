@@ -265,6 +265,8 @@ void build_device_scene(const FlatScene& f0, DeviceScene& ds) {
     ds.view.rects = ds.upload(rect);
     ds.view.boxes = ds.upload(box);
     ds.view.primrefs = ds.upload(f.primrefs);
+    ds.slot_refs = f.primrefs;
+    ds.slot_pad = slot_pad;
     {  // every scene with a BVH: any kernel instantiated with triangles reads it, whatever the scene holds
         std::vector<TriRec> lt(f.primrefs.size());
         for (size_t i = 0; i < lt.size(); ++i)

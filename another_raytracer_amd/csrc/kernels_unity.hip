@@ -5,5 +5,6 @@
 #include "k_paths_g_mesh.hip"
 #include "radiance_rays.hip"
 #include "tile_lists.hip"
+#include "refit.hip"
 #include "device_scene.hip"
 #include "renderer.hip"

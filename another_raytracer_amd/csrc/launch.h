@@ -94,6 +94,26 @@ void launch_paths(int num_cu, hipStream_t st, const DevScene& S, const PassGeom&
 // tile_lists.hip: fills one TileRec (tile_lists.h) per 8x8 tile of g's frame geometry for `cam`; S holds an LDS scene
 // image with representative slots (DeviceScene::tile_reps > 0)
 void launch_tile_lists(hipStream_t st, const DevScene& S, const PassGeom& g, const CameraRec& cam, void* tiles);
+// refit.hip
+// One rt_scene_update_triangles call as k_update_tris sees it: new vertices p (9 doubles each) for triangles
+// [first, first + n), written into every array of the uploaded scene that holds one.
+struct UpdateJob {
+    const double* p;
+    uint32_t first, n;
+    const uint32_t* primrefs;      // the device copy (pair-aligned where the scene runs an F_LEAF2 kernel)
+    const ObjRec* objs;
+    uint32_t n_slots, n_objs;
+    TriRec* tris;
+    TriRec* leaf_tris;
+    TriRec112* leaf_tris112;
+    PrimRec80* leaf_prims;
+    PrimRec80* obj_prims;
+    double* slot_box;              // 6 doubles per slot: the f64 box of its primitive (refit.h)
+};
+void launch_update_tris(hipStream_t st, const UpdateJob& j);
+// k_refit_level over every level [level_begin[l], level_begin[l + 1]) (refit.h refit_levels), the deepest first
+void launch_refit_levels(hipStream_t st, BvhNode* nodes, uint32_t n_nodes, const double* slot_box, uint32_t n_slots,
+                         const std::vector<uint32_t>& level_begin);
 size_t pool_bytes(int variant, int num_cu);  // the path pools of `variant` (k_paths' PathPool, kPoolCap entries per wave; 0 for every other)
 
 }  // namespace art

@@ -1,0 +1,77 @@
+// refit.hip — rt_scene_update_triangles on the device: k_update_tris writes the new vertices into every array that holds
+// a triangle (the records, the three leaf-ordered copies, the prim objects' copies) and the f64 box of every leaf slot
+// it touches; k_refit_level then recomputes the child boxes of one tree level from what lies below it (refit.h).  One
+// launch per level, deepest first, on one stream: stream order is the only dependency between the levels.
+#include "launch.h"
+#include "refit.h"
+
+namespace art {
+
+constexpr int kRefitBlock = 256;
+
+// The nine doubles of a triangle into a record's p[] (TriRec, TriRec112 and a PrimRec80 holding a TriRec start with them)
+__device__ __forceinline__ void put9(double* dst, const double v[9]) {
+    for (int k = 0; k < 9; ++k) dst[k] = v[k];
+}
+
+__global__ void __launch_bounds__(kRefitBlock) k_update_tris(UpdateJob j) {
+    const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (i < j.n_slots) {  // leaf slot i: a pad slot of the pair-aligned copy holds reference 0, a sphere
+        const uint32_t ref = j.primrefs[i];
+        const uint32_t t = primref_index(ref) - j.first;  // (wraps above n for a triangle below `first`)
+        if (primref_type(ref) == PRIM_TRIANGLE && t < j.n) {
+            double v[9];
+            for (int k = 0; k < 9; ++k) v[k] = j.p[9 * static_cast<size_t>(t) + k];
+            put9(j.leaf_tris[i].p, v);
+            // the plane as device_scene.hip makes it: n = cross(pt2 - pt1, pt3 - pt1), dd = -dot(n, pt1)
+            const V3 p1 = ld3(v), nn = cross(ld3(v + 3) - p1, ld3(v + 6) - p1);
+            TriRec112& r = j.leaf_tris112[i];
+            put9(r.p, v);
+            r.n[0] = nn.x, r.n[1] = nn.y, r.n[2] = nn.z;
+            r.dd = -dot(nn, p1);
+            put9(reinterpret_cast<double*>(j.leaf_prims[i].b), v);
+            tri_box(v, j.slot_box + 6 * static_cast<size_t>(i));
+        }
+    }
+    if (i < j.n) {  // triangle first + i: its record (mat stays)
+        double v[9];
+        for (int k = 0; k < 9; ++k) v[k] = j.p[9 * static_cast<size_t>(i) + k];
+        put9(j.tris[j.first + i].p, v);
+    }
+    if (i < j.n_objs && j.objs[i].kind == OBJ_PRIM) {  // a loose triangle of the world: obj_prims[i] is its record
+        const uint32_t ref = static_cast<uint32_t>(j.objs[i].a);
+        const uint32_t t = primref_index(ref) - j.first;
+        if (primref_type(ref) == PRIM_TRIANGLE && t < j.n) {
+            double v[9];
+            for (int k = 0; k < 9; ++k) v[k] = j.p[9 * static_cast<size_t>(t) + k];
+            put9(reinterpret_cast<double*>(j.obj_prims[i].b), v);
+        }
+    }
+}
+
+// Four lanes per node of [begin, end), one per child
+__global__ void __launch_bounds__(kRefitBlock) k_refit_level(BvhNode* nodes, uint32_t n_nodes, const double* slot_box, uint32_t n_slots,
+                                                             uint32_t begin, uint32_t end) {
+    const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+    const uint32_t n = begin + (i >> 2);
+    if (n < end) refit_child(nodes, n_nodes, slot_box, n_slots, n, static_cast<int>(i & 3u));
+}
+
+void launch_update_tris(hipStream_t st, const UpdateJob& j) {
+    const uint32_t threads = std::max(std::max(j.n_slots, j.n), j.n_objs);
+    if (threads == 0) return;
+    hipLaunchKernelGGL(k_update_tris, dim3((threads + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, j);
+}
+
+void launch_refit_levels(hipStream_t st, BvhNode* nodes, uint32_t n_nodes, const double* slot_box, uint32_t n_slots,
+                         const std::vector<uint32_t>& level_begin) {
+    for (size_t l = level_begin.size(); l-- > 1;) {
+        const uint32_t begin = level_begin[l - 1], end = level_begin[l];
+        if (end <= begin) continue;
+        const uint32_t threads = 4u * (end - begin);
+        hipLaunchKernelGGL(k_refit_level, dim3((threads + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, nodes, n_nodes, slot_box,
+                           n_slots, begin, end);
+    }
+}
+
+}  // namespace art

@@ -93,6 +93,21 @@ public:
     // the number of tiles, or 0 when render() would build no lists (the scene, the option, the mode or the sample
     // count).  counts may be null (the number only); otherwise it holds at least `cap` >= tiles entries.
     int tile_candidates(const CameraRec& cam, const RenderParams& p, uint16_t* counts, size_t cap);
+    // rt_scene_update_triangles: new vertices p (9 doubles each) for triangles [first, first + n) of flat().tris, written
+    // into every device array that holds a triangle (k_update_tris), then a refit of every BVH box, one launch per tree
+    // level from the deepest up (k_refit_level; refit.h).  device: p is a device pointer read in place on `stream` (null:
+    // the scene's own, and the call waits); a host p goes through the workspace: a copy, the kernels, a wait, as
+    // query_rays.  ms (may be null: then a device call on the caller's stream returns once enqueued): HIP events around
+    // the kernels.  The scene's first update makes the slot boxes and the level table (blocking).  Leaves the host copy
+    // stale: generation() counts the updates, current_flat() fetches before it answers.
+    void update_triangles(const double* p, size_t first, size_t n, bool device, void* stream, double* ms);
+    uint64_t generation() const;
+    // flat() with the triangle vertices and the 24 box floats of every node as the device holds them now (fetched when an
+    // update happened since the last fetch; waits for the device).  Node order and child codes are the compiled ones.
+    const FlatScene& current_flat();
+    // rt_scene_bvh_get: the device's nodes (n_nodes x 128 bytes, as uploaded) and primitive references; either may be
+    // null (both null: the counts only).  Uploads the scene if no call has yet; blocking.
+    void bvh_get(void* nodes_out, uint32_t* primrefs_out, size_t& n_nodes, size_t& n_primrefs);
     int device() const;
     size_t scene_bytes() const;
     const FlatScene& flat() const;

@@ -18,6 +18,7 @@
 #include "launch.h"
 #include "options.h"
 #include "pass_plan.h"
+#include "refit.h"
 #include "tile_lists.h"
 #include "view_plan.h"
 #include "workspace.h"
@@ -34,6 +35,7 @@ struct Renderer::Impl {
     DeviceBuffer ws{true};  // the workspace, with the test.fault_workspace_bytes fault point
     hipEvent_t ev[2] = {nullptr, nullptr};
     std::vector<ViewRec> view_table;  // rt_render_views: the camera table of the last call, as uploaded
+    uint64_t gen = 0, fetched_gen = 0;  // rt_scene_update_triangles calls so far / the one `flat` was last fetched after
 
     ~Impl() {
         s64.release();
@@ -848,6 +850,105 @@ void Renderer::render_noise_target(const CameraRec& cam, const RenderParams& p, 
     });
     stats.primary = result.samples = samples;
     result.rounds = rounds, result.converged_pixels = nconv;
+}
+
+// ------------------------------------------------------------------------------------------------ rt_scene_update_triangles
+// What a scene's first update makes: the f64 box of every leaf slot's primitive from the host records (refit.h; a
+// pad slot of the pair-aligned copy gets the empty box), uploaded once -- after that only k_update_tris writes it --
+// and the level ranges of the node array.
+static void prepare_refit(const FlatScene& f, DeviceScene& ds) {
+    if (ds.slot_box || ds.slot_refs.empty()) return;
+    ds.level_begin = refit_levels(f.nodes, f.objs);
+    std::vector<double> box(6 * ds.slot_refs.size());
+    for (size_t i = 0; i < ds.slot_refs.size(); ++i) {
+        double* b = box.data() + 6 * i;
+        const uint32_t ref = ds.slot_refs[i], idx = primref_index(ref);
+        if (ds.slot_pad[i]) {
+            empty_box6(b);
+            continue;
+        }
+        switch (primref_type(ref)) {
+            case PRIM_SPHERE: sphere_box(f.spheres.at(idx), b); break;
+            case PRIM_TRIANGLE: tri_box(f.tris.at(idx).p, b); break;
+            case PRIM_RECT: rect_box(f.rects.at(idx), b); break;
+            default: box_box(f.boxes.at(idx), b); break;
+        }
+    }
+    ds.slot_box = const_cast<double*>(ds.upload(box));
+}
+
+void Renderer::update_triangles(const double* p, size_t first, size_t n, bool device, void* stream, double* ms) {
+    upload();
+    Impl& I = *impl_;
+    DeviceScene& ds = I.s64;
+    if (n == 0) return;
+    if (first + n > I.flat.tris.size()) throw std::runtime_error("update_triangles: range beyond the scene's triangles");
+    prepare_refit(I.flat, ds);
+    hipStream_t st = (device && stream) ? static_cast<hipStream_t>(stream) : I.own_stream;
+    UpdateJob job{};
+    job.p = p;
+    if (!device) {  // host vertices: through the workspace
+        const size_t bytes = sizeof(double) * 9 * n;
+        Carver c(I.ws.reserve(bytes), 1);
+        double* d_p = c.take<double>(9 * n);
+        HIP_OK(hipMemcpyAsync(d_p, p, bytes, hipMemcpyHostToDevice, st));
+        job.p = d_p;
+    }
+    job.first = static_cast<uint32_t>(first), job.n = static_cast<uint32_t>(n);
+    job.primrefs = ds.view.primrefs, job.objs = ds.view.objs;
+    job.n_slots = ds.view.n_primrefs, job.n_objs = ds.view.n_objs;
+    // the arrays build_device_scene uploaded: const in the kernels' view only, the DeviceScene owns them
+    job.tris = const_cast<TriRec*>(ds.view.tris);
+    job.leaf_tris = const_cast<TriRec*>(ds.view.leaf_tris);
+    job.leaf_tris112 = const_cast<TriRec112*>(ds.view.leaf_tris112);
+    job.leaf_prims = const_cast<PrimRec80*>(ds.view.leaf_prims);
+    job.obj_prims = const_cast<PrimRec80*>(ds.view.obj_prims);
+    job.slot_box = ds.slot_box;
+    if (ms)
+        for (auto& e : I.ev)
+            if (!e) HIP_OK(hipEventCreate(&e));
+    if (ms) HIP_OK(hipEventRecord(I.ev[0], st));
+    launch_update_tris(st, job);
+    if (ds.slot_box) launch_refit_levels(st, const_cast<BvhNode*>(ds.view.nodes), ds.view.n_nodes, ds.slot_box, ds.view.n_primrefs, ds.level_begin);
+    HIP_OK(hipGetLastError());
+    if (ms) HIP_OK(hipEventRecord(I.ev[1], st));
+    ++I.gen;
+    // a device call on the caller's stream without ms returns here, enqueued; every other waits
+    if (!device || !stream || ms) HIP_OK(hipStreamSynchronize(st));
+    if (ms) {
+        float t = 0;
+        HIP_OK(hipEventElapsedTime(&t, I.ev[0], I.ev[1]));
+        *ms = t;
+    }
+}
+
+uint64_t Renderer::generation() const { return impl_->gen; }
+
+const FlatScene& Renderer::current_flat() {
+    Impl& I = *impl_;
+    if (I.fetched_gen == I.gen) return I.flat;
+    HIP_OK(hipSetDevice(I.device));
+    HIP_OK(hipDeviceSynchronize());  // an update enqueued on a caller's stream included
+    const DeviceScene& ds = I.s64;
+    std::vector<TriRec> tris(I.flat.tris.size());
+    if (!tris.empty()) HIP_OK(hipMemcpy(tris.data(), ds.view.tris, sizeof(TriRec) * tris.size(), hipMemcpyDeviceToHost));
+    for (size_t t = 0; t < tris.size(); ++t) std::memcpy(I.flat.tris[t].p, tris[t].p, sizeof tris[t].p);
+    std::vector<BvhNode> nodes(I.flat.nodes.size());
+    if (!nodes.empty()) HIP_OK(hipMemcpy(nodes.data(), ds.view.nodes, sizeof(BvhNode) * nodes.size(), hipMemcpyDeviceToHost));
+    // the 24 box floats only: the device's leaf codes address the pair-aligned slots, the host's the compiled ones
+    for (size_t k = 0; k < nodes.size(); ++k) std::memcpy(&I.flat.nodes[k], &nodes[k], 24 * sizeof(float));
+    I.fetched_gen = I.gen;
+    return I.flat;
+}
+
+void Renderer::bvh_get(void* nodes_out, uint32_t* primrefs_out, size_t& n_nodes, size_t& n_primrefs) {
+    upload();
+    const DeviceScene& ds = impl_->s64;
+    n_nodes = ds.view.n_nodes, n_primrefs = ds.view.n_primrefs;
+    if (!nodes_out && !primrefs_out) return;
+    HIP_OK(hipDeviceSynchronize());
+    if (nodes_out && n_nodes) HIP_OK(hipMemcpy(nodes_out, ds.view.nodes, sizeof(BvhNode) * n_nodes, hipMemcpyDeviceToHost));
+    if (primrefs_out && n_primrefs) HIP_OK(hipMemcpy(primrefs_out, ds.view.primrefs, sizeof(uint32_t) * n_primrefs, hipMemcpyDeviceToHost));
 }
 
 int device_count() {

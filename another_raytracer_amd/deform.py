@@ -1,0 +1,81 @@
+"""Deforming a compiled scene (rt_scene_update_triangles, include/art.h): new vertices for its triangles and a refit of
+its BVH boxes on the device -- an animated mesh, a morph target, vertices that come out of a torch optimiser -- where a
+new scene would cost a graph, a full SAH build and an upload per frame.
+
+    world = art.scene_manager().build("cow")
+    P = art.scene_triangles(world)                   # (n, 3, 3) float64, the compiled order
+    art.update_triangles(world, P + [0.0, 1.0, 0.0])  # numpy: copies and blocks
+    V = torch.from_numpy(P).cuda()
+    art.update_triangles(world, deform(V))           # a device tensor: in place on torch's current stream, no wait
+    frames = art.render_views(world, cams, W, H, spp, out=frames_gpu)   # same stream: ordered after the update
+
+Every later call on the scene gives the bits a scene compiled fresh from the same vertices gives (closest hits do not
+depend on the tree); topology, materials and texture coordinates stay.
+"""
+import ctypes
+
+import numpy as np
+
+from ._lib import RT_OUT_DEVICE, check, lib, rt_update_params
+from .rays import _f64_buffer, _is_tensor, _native_scene, _stream_handle
+
+# layout.h BvhNode as uploaded: the four child boxes as planes, the 32-bit child codes, the 16-bit codes in pad
+BVH_NODE = np.dtype([("lox", "<f4", 4), ("hix", "<f4", 4), ("loy", "<f4", 4), ("hiy", "<f4", 4), ("loz", "<f4", 4), ("hiz", "<f4", 4),
+                     ("child", "<i4", 4), ("pad", "<i4", 4)])
+assert BVH_NODE.itemsize == 128
+
+
+def scene_triangles(world):
+    """rt_scene_triangles_get: the scene's triangles as it holds them now, (n, 3, 3) float64 -- triangle, vertex (pt1, pt2,
+    pt3), xyz -- in compiled order: the order the triangles are met walking the world list.  Takes a scene_manager scene,
+    its .objects or a compile_world handle.  Needs no device unless the scene has been updated."""
+    handle = _native_scene(world)
+    n = check(lib.rt_scene_triangles_get(handle, None, 0), "scene_triangles")
+    out = np.empty((n, 3, 3), np.float64)
+    if n:
+        check(lib.rt_scene_triangles_get(handle, ctypes.c_void_p(out.ctypes.data), n), "scene_triangles")
+    return out
+
+
+def update_triangles(world, p, first=0, stream=None, timing=False):
+    """rt_scene_update_triangles: p holds new vertices for triangles [first, first + n), shape (n, 3, 3) or (n, 9) float64 in
+    scene_triangles' order; every BVH box is then refitted on the device.
+
+    p: a numpy array (the call copies through the scene's workspace and blocks), or a contiguous float64 torch tensor on the
+    scene's device, read in place on `stream` (a torch stream or a raw hipStream_t; default: torch's current stream) -- the
+    call then returns once the work is enqueued, unless timing is asked for.  The update writes the arrays the render
+    kernels read: order the calls on one scene on one stream, or synchronise between them.  timing=True returns the
+    device time of the update's kernels in milliseconds (HIP events; waits), otherwise None."""
+    handle = _native_scene(world)
+    dev = _is_tensor(p)
+    if not dev and not isinstance(p, np.ndarray):
+        raise TypeError("p must be a numpy array or a torch tensor")
+    shape = tuple(int(x) for x in p.shape)
+    if not (len(shape) == 3 and shape[1:] == (3, 3)) and not (len(shape) == 2 and shape[1] == 9):
+        raise ValueError("p must have shape (n, 3, 3) or (n, 9): three vertices per triangle")
+    ptr = _f64_buffer(p, shape, "p", dev, handle.device)
+    u = rt_update_params()
+    if dev:
+        u.flags = RT_OUT_DEVICE
+        u.stream = _stream_handle(stream, p.device)
+    elif stream is not None:
+        raise ValueError("stream applies to device tensors only: the host path runs on the scene's own stream and blocks")
+    ms = ctypes.c_double()
+    check(lib.rt_scene_update_triangles(handle, ctypes.byref(u), ctypes.c_void_p(ptr), int(first), shape[0], ctypes.byref(ms) if timing else None),
+          "update_triangles")
+    return ms.value if timing else None
+
+
+def scene_bvh(world):
+    """rt_scene_bvh_get (diagnostic): the device's BVH as it is now -- (nodes, primrefs): a structured array of the 128-byte
+    four-child nodes (BVH_NODE: lox, hix, loy, hiy, loz, hiz as float32[4] planes of the child boxes; child: int32[4],
+    >= 0 an inner node, -1 empty, else a leaf ~((count << 24) | first slot); pad: the 16-bit codes) and the uint32 primitive
+    reference of every leaf slot (type << 30 | index; type 1 = triangle).  Uploads the scene if needed; blocks."""
+    handle = _native_scene(world)
+    nn, nr = ctypes.c_int64(), ctypes.c_int64()
+    check(lib.rt_scene_bvh_get(handle, None, 0, None, 0, ctypes.byref(nn), ctypes.byref(nr)), "scene_bvh")
+    nodes = np.zeros((nn.value,), BVH_NODE)
+    refs = np.zeros((nr.value,), np.uint32)
+    check(lib.rt_scene_bvh_get(handle, ctypes.c_void_p(nodes.ctypes.data), nn.value, ctypes.c_void_p(refs.ctypes.data), nr.value, None, None),
+          "scene_bvh")
+    return nodes, refs

@@ -35,6 +35,8 @@
  *     (an orbit, a cube map, a light field)                          stats): every view in one persistent launch, rt_render's bits
  *   (scene construction every run)           scene_manager.cpp,  rt_scene_save / rt_scene_load (flat-scene files)
  *                                            mesh.h, bvh.cpp
+ *   (none: a scene is rebuilt every run)                          rt_scene_update_triangles (new vertices for a compiled
+ *                                                                    scene's triangles, BVH boxes refitted on the device)
  *   (none: engine_mode::adaptive interpolates     engine.h:96-333  rt_render_guides + rt_denoise, or rt_render_denoised
  *    untraced pixels; there is no denoiser)                          (first-hit guides, variance-guided a-trous filter)
  *   (none: tracer_constants::samples_per_pixel is   tracer_constants.h:12  rt_render_noise_target (per-pixel sample counts:
@@ -71,7 +73,8 @@ extern "C" {
  * queries, device buffers and a caller's stream), option query.any_sorted; rt_radiance_rays, rt_radiance_params (path-traced
  * radiance along caller-given rays), rt_camera_rays (the renderer's camera rays and post-camera RNG states as data);
  * rt_render_views (many cameras of one scene in one persistent launch), option views.max_paths; rt_tile_candidates (the
- * per-tile sphere lists of a render, as counts), option render.tile_lists. */
+ * per-tile sphere lists of a render, as counts), option render.tile_lists; rt_scene_update_triangles, rt_update_params,
+ * rt_scene_triangles_get, rt_scene_bvh_get (new vertices for a compiled scene's triangles and a BVH refit on the device). */
 #define RT_ABI_VERSION 5
 
 /* return codes */
@@ -209,6 +212,52 @@ void rt_scene_destroy(rt_scene* scene);
  * fails).  Wrong magic, version, record layout, size or checksum: RT_E_SCENE with the reason. */
 int rt_scene_save(const rt_scene* scene, const char* path);
 int rt_scene_load(const char* path, int device, rt_scene** out);
+
+/* ---- deforming a compiled scene (additive since ABI 5; the reference rebuilds a scene to move a vertex) ----
+ * The scene's triangles as it holds them now: 9 doubles each (pt1, pt2, pt3), in compiled order -- the order the
+ * triangles are met walking the world list, rt_scene_info.triangles of them.  Returns the count; p_out may be NULL (the
+ * count only), else it holds cap >= count triangles (RT_E_INVALID otherwise).  Host buffer.  Needs no device unless the
+ * scene has been updated. */
+int64_t rt_scene_triangles_get(rt_scene* scene, double* p_out, int64_t cap);
+typedef struct rt_update_params {   /* zero-initialised = host buffer, scene's stream */
+    int32_t flags;                  /* RT_OUT_DEVICE: p is a device pointer on the scene's device */
+    int32_t reserved;
+    void* stream;                   /* hipStream_t (RT_OUT_DEVICE only), or NULL for the scene's own stream */
+} rt_update_params;
+/* rt_scene_update_triangles: new vertices for triangles [first, first + n) (9 doubles each, as rt_scene_triangles_get
+ * orders them), then a refit of every BVH box on the device -- a cloth step, a morph target, a mesh whose vertices come
+ * out of an optimiser -- where the only other way to move a vertex is a new graph, a full SAH build and a new upload.
+ * Materials, texture coordinates and topology stay; spheres, rects and boxes cannot be updated; rt_multi is not covered.
+ * Equality with a fresh compile: let scene A be compiled from triangles P0 and updated to P1, and scene B be compiled
+ *   from the same graph with P1.  Every later call on A gives the bits it gives on B: rt_render, rt_render_views,
+ *   rt_query_rays (all 12 doubles, prim included: the compiled triangle order is the same), rt_radiance_rays, and the
+ *   segment counts -- closest hits do not depend on the tree, up to the exact-t ties any two trees can differ in.  A's
+ *   tree keeps its topology, so rt_stats.kernel_* of A does not change; its boxes are the builder's own conservative
+ *   boxes of what lies below them (a spatially split reference gets its triangle's whole box), so a refit tree is as
+ *   tight as its topology allows but not re-optimised: after a large deformation a fresh compile traverses faster.
+ * Streams and waiting: the work (one kernel that writes the vertices, then one small kernel per tree level) runs on
+ *   u->stream, or on the scene's own stream when that is NULL (then the call waits).  On a caller's stream the call
+ *   returns once enqueued when ms is NULL; with ms (HIP events around the kernels, milliseconds) it waits.
+ * Ordering: the update writes the arrays the render kernels read.  Calls on one scene must be ordered by the caller --
+ *   the same stream, or a synchronisation between them -- the rule the scene's workspace already imposes.
+ * Upload: the first call uploads the scene if no render has done so yet (blocking), and makes the refit's own tables.
+ * RT_E_INVALID, before any device work: scene or u NULL; first < 0, n < 0 or first + n above the triangle count; p NULL
+ *   with n > 0; a flag bit other than RT_OUT_DEVICE; a stream without RT_OUT_DEVICE; a non-finite value in a host
+ *   buffer (a device buffer is not inspected).  n = 0 is RT_OK and touches nothing; a scene without triangles accepts
+ *   only n = 0.
+ * Host copies: after an update rt_scene_triangles_get, rt_scene_bvh_get and rt_scene_save fetch what they need from the
+ *   device first (the triangle records and the 24 box floats per node; they wait for the device), so a saved and loaded
+ *   updated scene renders as the updated one.  rt_scene_dump fails (RT_E_SCENE) once a scene has been updated, as for
+ *   a loaded scene: the graph no longer describes it. */
+int rt_scene_update_triangles(rt_scene* scene, const rt_update_params* u, const double* p, int64_t first, int64_t n, double* ms);
+/* Diagnostic, as rt_tile_candidates is: the device's BVH as it is now.  nodes_out: n_nodes x 128 bytes (four-child nodes
+ * as uploaded: six float[4] planes lox, hix, loy, hiy, loz, hiz of the child boxes, int32 child[4] codes -- >= 0 an inner
+ * node, -1 empty, else a leaf ~((count << 24) | first slot) -- and the 16-bit codes in int32 pad[4]); primrefs_out:
+ * n_primrefs x uint32 (type:2 | index:30 per leaf slot; the device copy, pair-aligned where the scene runs an F_LEAF2
+ * kernel).  Either may be NULL; the counts come back through n_nodes / n_primrefs (either may be NULL); a buffer smaller
+ * than its count (node_cap / ref_cap entries) is RT_E_INVALID.  Uploads the scene if needed.  Host buffers, blocking. */
+int rt_scene_bvh_get(rt_scene* scene, void* nodes_out, int64_t node_cap, uint32_t* primrefs_out, int64_t ref_cap, int64_t* n_nodes,
+                     int64_t* n_primrefs);
 
 /* ---- render (engine::run; the engine_mode is in rt_params.flags: RT_ADAPTIVE, RT_PARALLEL_IMAGES, or neither for
  * single and parallel_stripes, which compute the same image) ----

@@ -225,6 +225,29 @@ inline void render_views(const scene& world, const std::vector<camera>& cams, in
           "render_views");
 }
 
+// Deforming a compiled scene (rt_scene_update_triangles).  scene_triangles: the world's triangles as it holds them now, 9
+// doubles each (pt1, pt2, pt3) in compiled order.  update_triangles: new vertices p (9 doubles each, that order) for
+// triangles [first, first + n), then a refit of every BVH box on the device; every later call on the world gives the bits
+// a world compiled fresh from those vertices gives.  flags: RT_OUT_DEVICE with `stream` for a device buffer -- the call
+// then returns once enqueued on a non-null stream unless ms (the device time of the update, milliseconds) is asked for.
+inline std::vector<double> scene_triangles(const scene& world) {
+    const std::int64_t n = rt_scene_triangles_get(world.objects.get(), nullptr, 0);
+    check(n < 0 ? static_cast<int>(n) : RT_OK, "scene_triangles");
+    std::vector<double> p(static_cast<std::size_t>(9 * n));
+    if (n > 0) {
+        const std::int64_t got = rt_scene_triangles_get(world.objects.get(), p.data(), n);
+        check(got < 0 ? static_cast<int>(got) : RT_OK, "scene_triangles");
+    }
+    return p;
+}
+inline void update_triangles(const scene& world, const double* p, std::int64_t first, std::int64_t n, std::int32_t flags = 0, void* stream = nullptr,
+                             double* ms = nullptr) {
+    rt_update_params u{};
+    u.flags = flags;
+    u.stream = stream;
+    check(rt_scene_update_triangles(world.objects.get(), &u, p, first, n, ms), "update_triangles");
+}
+
 // The engine with a runtime image size (the reference fixes W, H, C at compile time: engine<W,H,C> below); samples
 // per pixel and max depth are the reference's tracer_constants (tracer_constants.h:12-13) as arguments with the same
 // defaults.
