@@ -2,7 +2,8 @@
 // queries, radiance along caller-given rays, many views of a scene in one launch, camera rays and guide buffers.  Host
 // code only: every kernel is launched through launch.h / noise_target.h.
 //
-// The workspace is one grow-only DeviceBuffer that every entry point carves (workspace.h).  rt_render and
+// The workspace is one grow-only DeviceBuffer that every entry point carves (workspace.h); a Call is the protocol of one
+// entry point on the caller's buffers: stream, staging, timing and the wait (call_plan.h).  rt_render and
 // rt_render_noise_target share a Frame: begin_frame sets it up (geometry, variant, the samples per pass of pass_plan.h,
 // workspace, events) and opens the timed region, run_pass runs one pass and keeps the pass, launch and RT_PROFILE
 // accounts, end_frame closes the region, copies the frame out and fills the stats.  rt_render's three modes and the
@@ -15,6 +16,7 @@
 #include <cstring>
 #include <vector>
 
+#include "call_plan.h"
 #include "launch.h"
 #include "options.h"
 #include "pass_plan.h"
@@ -60,6 +62,87 @@ Renderer::~Renderer() {
         delete impl_;
     }
 }
+
+// One call's host protocol, in the order every entry point enqueues it: the stream (call_plan.h), the workspace layout
+// with the copies in, [the caller's memsets,] begin(), [the launches,] end() with the copies out, finish() with the wait.
+// `rule` is plan_call or plan_frame_call; own / ev are the renderer's stream and Impl::ev (rt_camera_rays, which has no
+// renderer: the null stream and no events).
+struct Call {
+    bool device = false, timed = false, wait = true, sizing = false;
+    hipStream_t st = nullptr;
+    hipEvent_t* ev = nullptr;
+    struct Copy { void* dst; const void* src; size_t bytes; } outs[3];
+    int nouts = 0;
+
+    Call() = default;
+    Call(hipStream_t own, hipEvent_t* ev, bool device, void* stream, bool timed, CallPlan (*rule)(bool, bool, bool) = plan_call)
+        : device(device), timed(timed), ev(ev) {
+        const CallPlan plan = rule(device, stream != nullptr, timed);
+        st = plan.callers_stream ? static_cast<hipStream_t>(stream) : own;
+        wait = plan.wait;
+    }
+    // Lays `buf` out: layout(Carver&) runs twice, over a null base for the size and over the allocation for the pointers.
+    template <class Layout>
+    void carve(DeviceBuffer& buf, Layout&& layout, size_t align = 256) {
+        Carver size(nullptr, align);
+        sizing = true, layout(size);
+        Carver parts(buf.reserve(size.total()), align);
+        sizing = false, nouts = 0, layout(parts);
+    }
+    // Within a layout, the device pointer of a caller's input / of a result: the caller's as it is (null stays null), or a
+    // part of the workspace -- an input is copied there now, a result is copied out by end().
+    template <class T>
+    const T* in(Carver& c, const T* src, size_t count) {
+        T* staged = c.take<T>(count, !device && src);
+        if (device || !src) return src;
+        if (!sizing) HIP_OK(hipMemcpyAsync(staged, src, sizeof(T) * count, hipMemcpyHostToDevice, st));
+        return staged;
+    }
+    template <class T>
+    T* out(Carver& c, T* dst, size_t count) {
+        T* staged = c.take<T>(count, !device && dst);
+        if (device || !dst) return dst;
+        outs[nouts++] = Copy{dst, staged, sizeof(T) * count};
+        return staged;
+    }
+    // A result that always leaves the workspace: to the caller's device or host buffer (null: not asked for).
+    void copy_out(void* dst, const void* src, size_t bytes) {
+        if (dst) HIP_OK(hipMemcpyAsync(dst, src, bytes, device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    }
+    // The timed region (Impl::ev, created on the first timed call).
+    void begin() {
+        for (int i = 0; timed && i < 2; ++i)
+            if (!ev[i]) HIP_OK(hipEventCreate(&ev[i]));
+        if (timed) HIP_OK(hipEventRecord(ev[0], st));
+    }
+    void end() {
+        HIP_OK(hipGetLastError());
+        if (timed) HIP_OK(hipEventRecord(ev[1], st));
+        for (int i = 0; i < nouts; ++i) HIP_OK(hipMemcpyAsync(outs[i].dst, outs[i].src, outs[i].bytes, hipMemcpyDeviceToHost, st));
+    }
+    // The wait rule; a timed call (which always waits) gets the elapsed time and the segment count at d_segments.
+    struct Done {
+        float ms = 0;
+        unsigned long long segments = 0;
+        void fill(RenderStats* s, uint64_t primary, int passes, int samples_per_pass) const {
+            if (s) *s = RenderStats{}, s->segments = segments, s->primary = primary, s->ms = ms, s->passes = passes, s->samples_per_pass = samples_per_pass;
+        }
+    };
+    Done finish(const unsigned long long* d_segments = nullptr) {
+        Done d;
+        if (timed && d_segments) HIP_OK(hipMemcpyAsync(&d.segments, d_segments, sizeof d.segments, hipMemcpyDeviceToHost, st));
+        if (wait) HIP_OK(hipStreamSynchronize(st));
+        if (timed) HIP_OK(hipEventElapsedTime(&d.ms, ev[0], ev[1]));
+        return d;
+    }
+};
+// What half of the free HBM holds in slots of slot_bytes (call_plan.h's slot_target).
+static uint64_t slot_target(const Renderer::Impl& I, size_t slot_bytes) {
+    size_t free_b = 0, total_b = 0;
+    HIP_OK(hipMemGetInfo(&free_b, &total_b));
+    return slot_target(free_b, I.ws.size(), slot_bytes);
+}
+
 size_t Renderer::scene_bytes() const { return impl_->s64.bytes; }
 int Renderer::device() const { return impl_->device; }
 const FlatScene& Renderer::flat() const { return impl_->flat; }
@@ -138,6 +221,7 @@ struct Frame {
     DeviceScene& ds;
     const CameraRec& cam;
     const RenderParams& p;
+    Call call;                 // timed, on `stream`
     hipStream_t stream = nullptr;
     int variant = 0, nrows = 0;
     bool mega = false;         // a persistent-path kernel: one launch per pass, a slot is its radiance record only
@@ -206,7 +290,8 @@ template <class Carve>
 static bool begin_frame(Frame& f, RenderStats& stats, int spp, bool spread, int profile_levels, Carve&& carve) {
     Renderer::Impl& I = f.I;
     const RenderParams& p = f.p;
-    f.stream = p.stream ? static_cast<hipStream_t>(p.stream) : I.own_stream;
+    f.call = Call(I.own_stream, I.ev, (p.flags & RT_OUT_DEVICE) != 0, p.stream, true, plan_frame_call);
+    f.stream = f.call.st;
     for (int a = 0; a < 3; ++a) f.ds.view.bg[a] = p.background[a];  // engine::set_scene's background
     f.nrows = band_local_rows(p.height, p.band_rows, p.band_count, p.band_index);
     stats.local_rows = f.nrows;
@@ -215,10 +300,7 @@ static bool begin_frame(Frame& f, RenderStats& stats, int spp, bool spread, int 
     f.variant = extend_variant(f.ds, p.flags);
     f.mega = f.variant == EXT_MEGA || f.variant == EXT_MEGA_G;
     const size_t slot_bytes = f.mega ? sizeof(ResRec) : sizeof(PathRec) + sizeof(HitRecD) + sizeof(ResRec) + 4u * (2u + kNumMatTypes) + 8u;
-    // the slot target: what half of the free HBM holds (plus the workspace this renderer already owns: a fixed point, no regrowth)
-    size_t free_b = 0, total_b = 0;
-    HIP_OK(hipMemGetInfo(&free_b, &total_b));
-    const uint64_t target = (free_b + I.ws.size()) / 2 / slot_bytes;
+    const uint64_t target = slot_target(I, slot_bytes);
     if (f.g.npix_pad > kMaxPassSlots) throw std::runtime_error("image too large for one pass (more than 2^31 padded pixels)");
     const PassPlan plan = plan_passes(target, p.samples_per_pass, f.g.npix_pad, spp, spread);
     f.k = plan.k, f.npasses = plan.npasses;
@@ -226,17 +308,12 @@ static bool begin_frame(Frame& f, RenderStats& stats, int spp, bool spread, int 
     f.g.cap = shard_cap(f.Pmax);
     f.local_pix = static_cast<size_t>(f.nrows) * p.width;
     f.counter_bytes = f.mega ? 4u * kCounterStride : 4ull * counter_words(p.max_depth);
-    Carver size(nullptr);
-    carve(size);
-    Carver parts(I.ws.reserve(size.total()));
-    carve(parts);
-    for (auto& e : I.ev)
-        if (!e) HIP_OK(hipEventCreate(&e));
+    f.call.carve(I.ws, carve);
     if (p.flags & RT_PROFILE) {  // (a pixel-list level never needs more passes than k gives)
         f.marks.reserve(static_cast<size_t>(profile_levels) * f.npasses * (f.mega ? 2 : 3 * p.max_depth));
         f.mark = [&f]() { f.marks.mark(f.stream); };
     }
-    HIP_OK(hipEventRecord(I.ev[0], f.stream));
+    f.call.begin();
     HIP_OK(hipMemsetAsync(f.w.segments, 0, sizeof(unsigned long long), f.stream));
     if (p.max_depth == 0) HIP_OK(hipMemsetAsync(f.w.res, 0, sizeof(ResRec) * f.Pmax, f.stream));  // engine.h:451-452
     return true;
@@ -280,21 +357,16 @@ static PassGeom list_geom(PassGeom g, const uint32_t* list, uint32_t nlist, uint
 // the sums, the caller's further copies, the segment count; after the stream has drained, every field of the stats but
 // `primary`, which is the caller's.
 static void end_frame(Frame& f, RenderStats& stats, uint8_t* out_rgb, double* out_acc, const std::function<void()>& more_copies = {}) {
-    HIP_OK(hipGetLastError());
 #ifdef ART_STATS
+    HIP_OK(hipGetLastError());
     dump_art_stats(f.stream);
 #endif
-    HIP_OK(hipEventRecord(f.I.ev[1], f.stream));
-    const hipMemcpyKind kind = (f.p.flags & RT_OUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (out_rgb) HIP_OK(hipMemcpyAsync(out_rgb, f.drgb, 3 * f.local_pix, kind, f.stream));
-    if (out_acc) HIP_OK(hipMemcpyAsync(out_acc, f.w.acc, sizeof(double) * 3 * f.local_pix, kind, f.stream));
+    f.call.end();
+    f.call.copy_out(out_rgb, f.drgb, 3 * f.local_pix);
+    f.call.copy_out(out_acc, f.w.acc, sizeof(double) * 3 * f.local_pix);
     if (more_copies) more_copies();
-    unsigned long long segs = 0;
-    HIP_OK(hipMemcpyAsync(&segs, f.w.segments, sizeof segs, hipMemcpyDeviceToHost, f.stream));
-    HIP_OK(hipStreamSynchronize(f.stream));
-    float ms = 0;
-    HIP_OK(hipEventElapsedTime(&ms, f.I.ev[0], f.I.ev[1]));
-    stats.ms = ms, stats.segments = segs, stats.passes = f.passes, stats.samples_per_pass = static_cast<int>(f.k);
+    const Call::Done done = f.call.finish(f.w.segments);
+    stats.ms = done.ms, stats.segments = done.segments, stats.passes = f.passes, stats.samples_per_pass = static_cast<int>(f.k);
     stats.extend_variant = f.variant, stats.kernel_features = f.kid.f, stats.kernel_textures = f.kid.tf, stats.kernel_lds_mode = f.kid.lm;
     if (f.p.flags & RT_PROFILE) {
         f.marks.sum(f.mega ? 2 : 3, stats.extend_ms, stats.shade_ms);
@@ -343,9 +415,8 @@ static int trace_samples(Frame& f, const RenderBufs& b, const uint32_t* list, ui
         // progressive snapshot: write_color of the sums so far, with the samples so far
         if (!list && p.on_pass) {
             launch_finalize(f.stream, f.w.acc, f.drgb, npix, done);
-            const hipMemcpyKind kind = (p.flags & RT_OUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-            if (b.out_rgb) HIP_OK(hipMemcpyAsync(b.out_rgb, f.drgb, 3ull * npix, kind, f.stream));
-            if (b.out_acc) HIP_OK(hipMemcpyAsync(b.out_acc, f.w.acc, sizeof(double) * 3 * npix, kind, f.stream));
+            f.call.copy_out(b.out_rgb, f.drgb, 3ull * npix);
+            f.call.copy_out(b.out_acc, f.w.acc, sizeof(double) * 3 * npix);
             HIP_OK(hipStreamSynchronize(f.stream));
             if (!p.on_pass(done)) break;
         }
@@ -474,10 +545,8 @@ int Renderer::tile_candidates(const CameraRec& cam, const RenderParams& p, uint1
     if (g.npix_pad > kMaxPassSlots) throw std::runtime_error("image too large for one pass (more than 2^31 padded pixels)");
     const int variant = extend_variant(ds, p.flags);
     // the samples per pass begin_frame would plan for a persistent kernel
-    size_t free_b = 0, total_b = 0;
-    HIP_OK(hipMemGetInfo(&free_b, &total_b));
     const int spp_t = (p.flags & RT_PARALLEL_IMAGES) ? 4 * (p.spp / 4) : p.spp;
-    const PassPlan plan = plan_passes((free_b + I.ws.size()) / 2 / sizeof(ResRec), p.samples_per_pass, g.npix_pad, spp_t, true);
+    const PassPlan plan = plan_passes(slot_target(I, sizeof(ResRec)), p.samples_per_pass, g.npix_pad, spp_t, true);
     if (!tile_lists_wanted(ds, variant, plan.k)) return 0;
     const size_t ntiles = g.npix_pad / 64u;
     if (!counts) return static_cast<int>(ntiles);
@@ -506,16 +575,13 @@ void Renderer::trace_rays(const double* rays, size_t n, bool global_scene, doubl
     const DeviceScene& ds = impl_->s64;
     if (n == 0) return;
     if (n > (1u << 30)) throw std::runtime_error("too many rays");
-    hipStream_t st = impl_->own_stream;
-    const size_t in_b = sizeof(double) * 7 * n, t_b = sizeof(double) * n, n_b = sizeof(double) * 3 * n;
-    Carver c(impl_->ws.reserve(in_b + t_b + n_b), 1);  // packed
-    double *d_rays = c.take<double>(7 * n), *d_t = c.take<double>(n), *d_n = c.take<double>(3 * n);
-    HIP_OK(hipMemcpyAsync(d_rays, rays, in_b, hipMemcpyHostToDevice, st));
-    launch_trace_rays(ds, global_scene, st, d_rays, static_cast<uint32_t>(n), d_t, d_n);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(t_out, d_t, t_b, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(n_out, d_n, n_b, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
+    Call call(impl_->own_stream, impl_->ev, false, nullptr, false);
+    const double* d_rays = nullptr;
+    double *d_t = nullptr, *d_n = nullptr;
+    call.carve(impl_->ws, [&](Carver& c) { d_rays = call.in(c, rays, 7 * n), d_t = call.out(c, t_out, n), d_n = call.out(c, n_out, 3 * n); }, 1);  // packed
+    launch_trace_rays(ds, global_scene, call.st, d_rays, static_cast<uint32_t>(n), d_t, d_n);
+    call.end();
+    call.finish();
 }
 
 void Renderer::query_rays(const double* rays, const double* t_max, size_t n, bool device, bool global_scene, bool any_hit, bool no_media,
@@ -525,54 +591,39 @@ void Renderer::query_rays(const double* rays, const double* t_max, size_t n, boo
     const DeviceScene& ds = I.s64;
     if (n == 0) return;
     if (n > (1u << 30)) throw std::runtime_error("too many rays");
-    hipStream_t st = (device && stream) ? static_cast<hipStream_t>(stream) : I.own_stream;
-    const uint32_t nn = static_cast<uint32_t>(n);
-    if (device) {  // the caller's buffers as they are: no workspace, no copy
-        if (any_hit) launch_occlude_rays(ds, global_scene, st, rays, t_max, nn, occluded);
-        else launch_query_rays(ds, global_scene, st, rays, t_max, nn, no_media, hits);
-        HIP_OK(hipGetLastError());
-        if (!stream) HIP_OK(hipStreamSynchronize(st));  // the scene's own stream: nobody else can wait on it
-        return;
-    }
-    // host buffers: [rays][t_max][hits or occluded] packed in the workspace (each part 8-byte aligned)
-    const size_t in_b = sizeof(double) * 7 * n, tm_b = t_max ? sizeof(double) * n : 0;
-    const size_t out_b = any_hit ? n : sizeof(double) * RT_HIT_DOUBLES * n;
-    Carver c(I.ws.reserve(in_b + tm_b + out_b), 1);
-    double *d_rays = c.take<double>(7 * n), *d_tm = t_max ? c.take<double>(n) : nullptr;
-    char* d_out = c.take<char>(out_b);
-    HIP_OK(hipMemcpyAsync(d_rays, rays, in_b, hipMemcpyHostToDevice, st));
-    if (t_max) HIP_OK(hipMemcpyAsync(d_tm, t_max, tm_b, hipMemcpyHostToDevice, st));
-    if (any_hit) launch_occlude_rays(ds, global_scene, st, d_rays, d_tm, nn, reinterpret_cast<uint8_t*>(d_out));
-    else launch_query_rays(ds, global_scene, st, d_rays, d_tm, nn, no_media, reinterpret_cast<double*>(d_out));
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(any_hit ? static_cast<void*>(occluded) : static_cast<void*>(hits), d_out, out_b, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
+    // never timed: a device call waits exactly on the scene's own stream (the null handle), on which nobody else can
+    Call call(I.own_stream, I.ev, device, stream, false);
+    // device buffers: the caller's as they are, no workspace, no copy; host buffers: [rays][t_max][hits or occluded]
+    // packed in the workspace (each part 8-byte aligned)
+    const double *d_rays = nullptr, *d_tm = nullptr;
+    double* d_hits = nullptr;
+    uint8_t* d_occ = nullptr;
+    call.carve(I.ws, [&](Carver& c) {
+        d_rays = call.in(c, rays, 7 * n), d_tm = call.in(c, t_max, n);
+        if (any_hit) d_occ = call.out(c, occluded, n);
+        else d_hits = call.out(c, hits, RT_HIT_DOUBLES * n);
+    }, 1);
+    if (any_hit) launch_occlude_rays(ds, global_scene, call.st, d_rays, d_tm, static_cast<uint32_t>(n), d_occ);
+    else launch_query_rays(ds, global_scene, call.st, d_rays, d_tm, static_cast<uint32_t>(n), no_media, d_hits);
+    call.end();
+    call.finish();
 }
 
 void Renderer::render_guides(const CameraRec& cam, const RenderParams& p, double* guides, double* rays_out) {
     upload();
     Impl& I = *impl_;
     const DeviceScene& ds = I.s64;
-    hipStream_t st = p.stream ? static_cast<hipStream_t>(p.stream) : I.own_stream;
     GuideGeom g{p.width, p.height, band_local_rows(p.height, p.band_rows, p.band_count, p.band_index), p.band_rows, p.band_count, p.band_index};
     if (g.rows == 0) return;
     const size_t npix = static_cast<size_t>(g.rows) * p.width;
-    const size_t g_b = sizeof(double) * 10 * npix, r_b = sizeof(double) * 7 * npix;
-    const bool dev_out = (p.flags & RT_OUT_DEVICE) != 0;
-    double* d_g = guides;
-    double* d_r = rays_out;
-    if (!dev_out) {  // host buffers: the kernel writes the (packed) workspace, copied out below
-        Carver c(I.ws.reserve(g_b + (rays_out ? r_b : 0)), 1);
-        d_g = c.take<double>(10 * npix);
-        d_r = rays_out ? c.take<double>(7 * npix) : nullptr;
-    }
-    launch_guides(ds, p.flags, st, g, cam, d_g, d_r);
-    HIP_OK(hipGetLastError());
-    if (!dev_out) {
-        HIP_OK(hipMemcpyAsync(guides, d_g, g_b, hipMemcpyDeviceToHost, st));
-        if (rays_out) HIP_OK(hipMemcpyAsync(rays_out, d_r, r_b, hipMemcpyDeviceToHost, st));
-    }
-    HIP_OK(hipStreamSynchronize(st));
+    const bool device = (p.flags & RT_OUT_DEVICE) != 0;
+    Call call(I.own_stream, I.ev, device, p.stream, false, plan_frame_call);
+    // host buffers: the kernel writes the (packed) workspace, copied out by end()
+    double *d_g = nullptr, *d_r = nullptr;
+    call.carve(I.ws, [&](Carver& c) { d_g = call.out(c, guides, 10 * npix), d_r = call.out(c, rays_out, 7 * npix); }, 1);
+    launch_guides(ds, p.flags, call.st, g, cam, d_g, d_r);
+    call.end();
+    call.finish();
 }
 
 void Renderer::radiance_rays(const RadianceParams& p, const double* rays, const uint64_t* rng, size_t n, double* radiance, RenderStats* stats) {
@@ -583,59 +634,32 @@ void Renderer::radiance_rays(const RadianceParams& p, const double* rays, const 
     const uint32_t spp = static_cast<uint32_t>(std::max(1, p.spp));
     const uint64_t P = static_cast<uint64_t>(n) * spp;
     if (n > (1u << 30) || P > kMaxPassSlots) throw std::runtime_error("too many rays or paths");
-    hipStream_t st = (p.device && p.stream) ? static_cast<hipStream_t>(p.stream) : I.own_stream;
+    Call call(I.own_stream, I.ev, p.device, p.stream, stats != nullptr);
+    hipStream_t st = call.st;
     // workspace: the claim counter's line, the segment count, the per-path records (spp > 1) and, for host buffers,
     // the device copies of the caller's
     RadianceJob job{};
-    double *d_rays = nullptr, *d_rad = nullptr;
-    uint64_t* d_rng = nullptr;
-    auto carve = [&](Carver& c) {
+    call.carve(I.ws, [&](Carver& c) {
         job.next = c.take<uint32_t>(kCounterStride);
         job.segments = c.take<unsigned long long>(1);
         job.res = c.take<ResRec>(P, spp > 1);
-        d_rays = c.take<double>(7 * n, !p.device);
-        d_rng = c.take<uint64_t>(P, !p.device && rng);
-        d_rad = c.take<double>(3 * n, !p.device);
-    };
-    Carver size(nullptr);
-    carve(size);
-    Carver parts(I.ws.reserve(size.total()));
-    carve(parts);
+        job.rays = call.in(c, rays, 7 * n);
+        job.rng = call.in(c, rng, P);
+        job.radiance = call.out(c, radiance, 3 * n);
+    });
     if (spp == 1) job.res = nullptr;
-    job.rays = p.device ? rays : d_rays;
-    job.rng = !rng ? nullptr : (p.device ? rng : d_rng);
-    job.radiance = p.device ? radiance : d_rad;
     job.P = static_cast<uint32_t>(P), job.spp = spp, job.chunk = path_chunk(job.P, I.num_cu);
     job.sample_base = p.sample_base, job.id_base = static_cast<uint32_t>(p.id_base);
     job.stack = stack_rows(ds.max_stack);
     job.max_depth = p.max_depth;
     job.seed_mix = splitmix64(p.seed);
     job.fd_spp = FastDiv::make(spp);
-    if (stats)
-        for (auto& e : I.ev)
-            if (!e) HIP_OK(hipEventCreate(&e));
-    if (!p.device) {
-        HIP_OK(hipMemcpyAsync(d_rays, rays, sizeof(double) * 7 * n, hipMemcpyHostToDevice, st));
-        if (rng) HIP_OK(hipMemcpyAsync(d_rng, rng, sizeof(uint64_t) * P, hipMemcpyHostToDevice, st));
-    }
     HIP_OK(hipMemsetAsync(job.next, 0, sizeof(uint32_t), st));
     HIP_OK(hipMemsetAsync(job.segments, 0, sizeof(unsigned long long), st));
-    if (stats) HIP_OK(hipEventRecord(I.ev[0], st));
+    call.begin();
     launch_radiance_rays(ds, p.global_scene ? RT_GLOBAL_SCENE : 0, I.num_cu, st, job, static_cast<uint32_t>(n), p.background);
-    HIP_OK(hipGetLastError());
-    if (stats) HIP_OK(hipEventRecord(I.ev[1], st));
-    if (!p.device) HIP_OK(hipMemcpyAsync(radiance, d_rad, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, st));
-    unsigned long long segs = 0;
-    if (stats) HIP_OK(hipMemcpyAsync(&segs, job.segments, sizeof segs, hipMemcpyDeviceToHost, st));
-    // a device call on the caller's stream without stats returns here, enqueued; every other waits
-    if (!p.device || !p.stream || stats) HIP_OK(hipStreamSynchronize(st));
-    if (stats) {
-        float ms = 0;
-        HIP_OK(hipEventElapsedTime(&ms, I.ev[0], I.ev[1]));
-        *stats = RenderStats{};
-        stats->segments = segs, stats->primary = P, stats->ms = ms;
-        stats->passes = 1, stats->samples_per_pass = static_cast<int>(spp);
-    }
+    call.end();
+    call.finish(job.segments).fill(stats, P, 1, static_cast<int>(spp));  // (a device call on the caller's stream without stats returns enqueued)
 }
 
 void Renderer::render_views(const CameraRec* cams, const uint64_t* seeds, size_t nviews, const RenderParams& p, uint8_t* out_rgb, double* out_acc,
@@ -645,16 +669,15 @@ void Renderer::render_views(const CameraRec* cams, const uint64_t* seeds, size_t
     const DeviceScene& ds = I.s64;
     if (nviews == 0) return;
     const bool device = (p.flags & RT_OUT_DEVICE) != 0;
-    hipStream_t st = (device && p.stream) ? static_cast<hipStream_t>(p.stream) : I.own_stream;
+    Call call(I.own_stream, I.ev, device, p.stream, stats != nullptr);
+    hipStream_t st = call.st;
     const uint32_t spp = static_cast<uint32_t>(p.spp);
     const uint64_t npix = static_cast<uint64_t>(p.width) * static_cast<uint64_t>(p.height);
     const uint64_t view_paths = npix * spp;
-    // the groups (view_plan.h): a launch's records within half of the free HBM (plus the workspace this renderer already
-    // owns: a fixed point, as begin_frame's slot target), within kMaxPassSlots and within views.max_paths
-    size_t free_b = 0, total_b = 0;
-    HIP_OK(hipMemGetInfo(&free_b, &total_b));
+    // the groups (view_plan.h): a launch's records within begin_frame's slot target, within kMaxPassSlots and within
+    // views.max_paths
     ViewPlan plan{};
-    if (!plan_views(nviews, view_paths, (free_b + I.ws.size()) / 2 / sizeof(ResRec), static_cast<uint64_t>(opt(Opt::ViewsMaxPaths)), plan))
+    if (!plan_views(nviews, view_paths, slot_target(I, sizeof(ResRec)), static_cast<uint64_t>(opt(Opt::ViewsMaxPaths)), plan))
         throw std::runtime_error("a view has more paths than one launch holds (kMaxPassSlots)");
     const uint64_t group_paths = static_cast<uint64_t>(plan.per_group) * view_paths;
     const size_t pixels = static_cast<size_t>(nviews) * static_cast<size_t>(npix);
@@ -664,33 +687,24 @@ void Renderer::render_views(const CameraRec* cams, const uint64_t* seeds, size_t
     unsigned long long* segments = nullptr;
     ViewRec* table = nullptr;
     ResRec* res = nullptr;
-    double* d_acc = nullptr;
-    uint8_t* d_rgb = nullptr;
-    auto carve = [&](Carver& c) {
+    double* acc = nullptr;
+    uint8_t* rgb = nullptr;
+    call.carve(I.ws, [&](Carver& c) {
         next = c.take<uint32_t>(static_cast<size_t>(plan.ngroups) * kCounterStride);
         segments = c.take<unsigned long long>(1);
         table = c.take<ViewRec>(nviews);
         res = c.take<ResRec>(group_paths, spp > 1);
-        d_acc = c.take<double>(3 * pixels, !(device && out_acc));
-        d_rgb = c.take<uint8_t>(3 * pixels, !device);
-    };
-    Carver size(nullptr);
-    carve(size);
-    Carver parts(I.ws.reserve(size.total()));
-    carve(parts);
-    double* acc = (device && out_acc) ? out_acc : d_acc;
-    uint8_t* rgb = device ? out_rgb : d_rgb;
+        rgb = call.out(c, out_rgb, 3 * pixels);
+        acc = out_acc ? call.out(c, out_acc, 3 * pixels) : c.take<double>(3 * pixels);  // the sums are traced even when nobody asks for them
+    });
     // the table's host copy lives in the renderer until the next call: the upload may still read it when a call on the
     // caller's stream returns
     I.view_table.resize(nviews);
     for (size_t v = 0; v < nviews; ++v) I.view_table[v] = ViewRec{cams[v], splitmix64(seeds ? seeds[v] : p.seed)};
-    if (stats)
-        for (auto& e : I.ev)
-            if (!e) HIP_OK(hipEventCreate(&e));
     HIP_OK(hipMemcpyAsync(table, I.view_table.data(), sizeof(ViewRec) * nviews, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemsetAsync(next, 0, sizeof(uint32_t) * plan.ngroups * kCounterStride, st));
     HIP_OK(hipMemsetAsync(segments, 0, sizeof(unsigned long long), st));
-    if (stats) HIP_OK(hipEventRecord(I.ev[0], st));
+    call.begin();
     ViewsJob job{};
     job.segments = segments;
     job.spp = spp, job.npix = static_cast<uint32_t>(npix);
@@ -710,23 +724,9 @@ void Renderer::render_views(const CameraRec* cams, const uint64_t* seeds, size_t
         launch_radiance_views(ds, p.flags, I.num_cu, st, job, gpix, p.background);
         launch_finalize(st, job.radiance, rgb + 3 * v0 * npix, gpix, p.spp);
     }
-    HIP_OK(hipGetLastError());
-    if (stats) HIP_OK(hipEventRecord(I.ev[1], st));
-    if (!device) {
-        HIP_OK(hipMemcpyAsync(out_rgb, d_rgb, 3 * pixels, hipMemcpyDeviceToHost, st));
-        if (out_acc) HIP_OK(hipMemcpyAsync(out_acc, d_acc, sizeof(double) * 3 * pixels, hipMemcpyDeviceToHost, st));
-    }
-    unsigned long long segs = 0;
-    if (stats) HIP_OK(hipMemcpyAsync(&segs, segments, sizeof segs, hipMemcpyDeviceToHost, st));
-    // a device call on the caller's stream without stats returns here, enqueued; every other waits
-    if (!device || !p.stream || stats) HIP_OK(hipStreamSynchronize(st));
-    if (stats) {
-        float ms = 0;
-        HIP_OK(hipEventElapsedTime(&ms, I.ev[0], I.ev[1]));
-        *stats = RenderStats{};
-        stats->segments = segs, stats->primary = static_cast<uint64_t>(nviews) * view_paths, stats->ms = ms;
-        stats->passes = static_cast<int>(plan.ngroups), stats->samples_per_pass = p.spp;
-    }
+    call.end();
+    // (a device call on the caller's stream without stats returns enqueued)
+    call.finish(segments).fill(stats, static_cast<uint64_t>(nviews) * view_paths, static_cast<int>(plan.ngroups), p.spp);
 }
 
 void Renderer::camera_rays(int device, const CameraRec& cam, const RenderParams& p, uint32_t sample_base, double* rays_out, uint64_t* rng_out) {
@@ -739,21 +739,16 @@ void Renderer::camera_rays(int device, const CameraRec& cam, const RenderParams&
     g.k = k, g.sample_base = sample_base, g.P = k * g.npix_pad;
     const size_t ne = static_cast<size_t>(nrows) * static_cast<size_t>(p.width) * k;
     g.live = static_cast<uint32_t>(ne);
-    if (p.flags & RT_OUT_DEVICE) {
-        hipStream_t st = static_cast<hipStream_t>(p.stream);
-        launch_camera_rays(st, g, cam, rays_out, rng_out);
-        HIP_OK(hipGetLastError());
-        if (!st) HIP_OK(hipStreamSynchronize(st));
-        return;
-    }
-    DeviceBuffer tmp;  // no scene, so no renderer workspace: freed on return
-    Carver c(tmp.reserve(sizeof(double) * 7 * ne + (rng_out ? sizeof(uint64_t) * ne : 0)), 1);
-    double* d_rays = c.take<double>(7 * ne);
-    uint64_t* d_rng = rng_out ? c.take<uint64_t>(ne) : nullptr;
-    launch_camera_rays(nullptr, g, cam, d_rays, d_rng);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpy(rays_out, d_rays, sizeof(double) * 7 * ne, hipMemcpyDeviceToHost));
-    if (rng_out) HIP_OK(hipMemcpy(rng_out, d_rng, sizeof(uint64_t) * ne, hipMemcpyDeviceToHost));
+    // no scene, so no renderer: the null stream stands in for its own (a call there waits), and host buffers are staged
+    // in a buffer of the call's, freed on return
+    Call call(nullptr, nullptr, (p.flags & RT_OUT_DEVICE) != 0, p.stream, false);
+    DeviceBuffer tmp;
+    double* d_rays = nullptr;
+    uint64_t* d_rng = nullptr;
+    call.carve(tmp, [&](Carver& c) { d_rays = call.out(c, rays_out, 7 * ne), d_rng = call.out(c, rng_out, ne); }, 1);
+    launch_camera_rays(call.st, g, cam, d_rays, d_rng);
+    call.end();
+    call.finish();
 }
 
 // Noise-target rendering (rt_render_noise_target; the kernels in noise_target.hip).  The base pass traces samples
@@ -843,9 +838,8 @@ void Renderer::render_noise_target(const CameraRec& cam, const RenderParams& p, 
     nt_finalize(stream, w.acc, count, f.drgb, npix);
     uint32_t nconv = 0;
     end_frame(f, stats, out_rgb, out_acc, [&]() {
-        const hipMemcpyKind kind = (p.flags & RT_OUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        if (out_count) HIP_OK(hipMemcpyAsync(out_count, count, sizeof(int32_t) * local_pix, kind, stream));
-        if (out_moments) HIP_OK(hipMemcpyAsync(out_moments, mom, sizeof(double) * 2 * local_pix, kind, stream));
+        f.call.copy_out(out_count, count, sizeof(int32_t) * local_pix);
+        f.call.copy_out(out_moments, mom, sizeof(double) * 2 * local_pix);
         HIP_OK(hipMemcpyAsync(&nconv, conv, 4, hipMemcpyDeviceToHost, stream));
     });
     stats.primary = result.samples = samples;
@@ -884,16 +878,10 @@ void Renderer::update_triangles(const double* p, size_t first, size_t n, bool de
     if (n == 0) return;
     if (first + n > I.flat.tris.size()) throw std::runtime_error("update_triangles: range beyond the scene's triangles");
     prepare_refit(I.flat, ds);
-    hipStream_t st = (device && stream) ? static_cast<hipStream_t>(stream) : I.own_stream;
+    Call call(I.own_stream, I.ev, device, stream, ms != nullptr);
+    hipStream_t st = call.st;
     UpdateJob job{};
-    job.p = p;
-    if (!device) {  // host vertices: through the workspace
-        const size_t bytes = sizeof(double) * 9 * n;
-        Carver c(I.ws.reserve(bytes), 1);
-        double* d_p = c.take<double>(9 * n);
-        HIP_OK(hipMemcpyAsync(d_p, p, bytes, hipMemcpyHostToDevice, st));
-        job.p = d_p;
-    }
+    call.carve(I.ws, [&](Carver& c) { job.p = call.in(c, p, 9 * n); }, 1);  // host vertices: through the workspace
     job.first = static_cast<uint32_t>(first), job.n = static_cast<uint32_t>(n);
     job.primrefs = ds.view.primrefs, job.objs = ds.view.objs;
     job.n_slots = ds.view.n_primrefs, job.n_objs = ds.view.n_objs;
@@ -904,22 +892,13 @@ void Renderer::update_triangles(const double* p, size_t first, size_t n, bool de
     job.leaf_prims = const_cast<PrimRec80*>(ds.view.leaf_prims);
     job.obj_prims = const_cast<PrimRec80*>(ds.view.obj_prims);
     job.slot_box = ds.slot_box;
-    if (ms)
-        for (auto& e : I.ev)
-            if (!e) HIP_OK(hipEventCreate(&e));
-    if (ms) HIP_OK(hipEventRecord(I.ev[0], st));
+    call.begin();
     launch_update_tris(st, job);
     if (ds.slot_box) launch_refit_levels(st, const_cast<BvhNode*>(ds.view.nodes), ds.view.n_nodes, ds.slot_box, ds.view.n_primrefs, ds.level_begin);
-    HIP_OK(hipGetLastError());
-    if (ms) HIP_OK(hipEventRecord(I.ev[1], st));
+    call.end();
     ++I.gen;
-    // a device call on the caller's stream without ms returns here, enqueued; every other waits
-    if (!device || !stream || ms) HIP_OK(hipStreamSynchronize(st));
-    if (ms) {
-        float t = 0;
-        HIP_OK(hipEventElapsedTime(&t, I.ev[0], I.ev[1]));
-        *ms = t;
-    }
+    const Call::Done done = call.finish();  // (a device call on the caller's stream without ms returns enqueued)
+    if (ms) *ms = done.ms;
 }
 
 uint64_t Renderer::generation() const { return impl_->gen; }

@@ -17,7 +17,8 @@ import ctypes
 import numpy as np
 
 from ._lib import RT_OUT_DEVICE, check, lib, rt_update_params
-from .rays import _f64_buffer, _is_tensor, _native_scene, _stream_handle
+from ._buffers import address, stream_handle
+from .rays import _native_scene
 
 # layout.h BvhNode as uploaded: the four child boxes as planes, the 32-bit child codes, the 16-bit codes in pad
 BVH_NODE = np.dtype([("lox", "<f4", 4), ("hix", "<f4", 4), ("loy", "<f4", 4), ("hiy", "<f4", 4), ("loz", "<f4", 4), ("hiz", "<f4", 4),
@@ -47,19 +48,15 @@ def update_triangles(world, p, first=0, stream=None, timing=False):
     kernels read: order the calls on one scene on one stream, or synchronise between them.  timing=True returns the
     device time of the update's kernels in milliseconds (HIP events; waits), otherwise None."""
     handle = _native_scene(world)
-    dev = _is_tensor(p)
-    if not dev and not isinstance(p, np.ndarray):
+    if not hasattr(p, "shape"):
         raise TypeError("p must be a numpy array or a torch tensor")
     shape = tuple(int(x) for x in p.shape)
     if not (len(shape) == 3 and shape[1:] == (3, 3)) and not (len(shape) == 2 and shape[1] == 9):
         raise ValueError("p must have shape (n, 3, 3) or (n, 9): three vertices per triangle")
-    ptr = _f64_buffer(p, shape, "p", dev, handle.device)
+    ptr, dev = address(p, "p", ("float64",), shape=shape, device_index=handle.device)
     u = rt_update_params()
-    if dev:
-        u.flags = RT_OUT_DEVICE
-        u.stream = _stream_handle(stream, p.device)
-    elif stream is not None:
-        raise ValueError("stream applies to device tensors only: the host path runs on the scene's own stream and blocks")
+    u.flags = RT_OUT_DEVICE if dev else 0
+    u.stream = stream_handle(stream, p.device if dev else None)
     ms = ctypes.c_double()
     check(lib.rt_scene_update_triangles(handle, ctypes.byref(u), ctypes.c_void_p(ptr), int(first), shape[0], ctypes.byref(ms) if timing else None),
           "update_triangles")

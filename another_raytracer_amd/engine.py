@@ -11,6 +11,7 @@ import enum
 import numpy as np
 
 from ._lib import RT_ADAPTIVE, RT_DN_NO_DEMODULATE, RT_FP64, RT_GUIDE_DOUBLES, rt_denoise_params, RT_PARALLEL_IMAGES, rt_progress_fn, RT_GLOBAL_SCENE, RT_OUT_DEVICE, RT_PROFILE, RT_SPLIT_SHADE, RT_WAVEFRONT, check, dvec, lib, rt_camera, rt_params, rt_stats
+from ._buffers import ANY, address, same_place
 from .scene import compile_world
 
 
@@ -36,30 +37,14 @@ class camera:  # camera.h:8-36
                            float(focus_dist), float(time0), float(time1))
 
 
-def _pointer(out, nbytes):
-    """(address, is_device) of a writable uint8 buffer: numpy array or torch tensor (CPU or CUDA/HIP)."""
-    if isinstance(out, np.ndarray):
-        if not out.flags.c_contiguous or out.dtype != np.uint8 or out.nbytes < nbytes:
-            raise ValueError(f"output must be a C-contiguous uint8 array of >= {nbytes} bytes")
-        return out.ctypes.data, False
-    if hasattr(out, "data_ptr"):
-        if not out.is_contiguous() or out.element_size() * out.numel() < nbytes:
-            raise ValueError(f"output tensor must be contiguous with >= {nbytes} bytes")
-        return out.data_ptr(), out.device.type != "cpu"
-    raise TypeError("output must be a numpy array or a torch tensor")
+def _pointer(out, nbytes, what="output"):
+    """(address, is_device) of a frame of RGB8 bytes: a uint8 numpy array, or a tensor (CPU or device) of >= nbytes bytes."""
+    return address(out, what, ("uint8",), min_bytes=nbytes, tensor_dtypes=ANY)
 
 
-def _f64_pointer(buf, count, what):
-    """(address, is_device) of a float64 buffer of >= count elements: numpy array or torch tensor."""
-    if isinstance(buf, np.ndarray):
-        if not buf.flags.c_contiguous or buf.dtype != np.float64 or buf.size < count:
-            raise ValueError(f"{what} must be a C-contiguous float64 array of >= {count} elements")
-        return buf.ctypes.data, False
-    if hasattr(buf, "data_ptr"):
-        if not buf.is_contiguous() or buf.element_size() != 8 or buf.numel() < count:
-            raise ValueError(f"{what} must be a contiguous float64 tensor of >= {count} elements")
-        return buf.data_ptr(), buf.device.type != "cpu"
-    raise TypeError(f"{what} must be a numpy array or a torch tensor")
+def _f64(buf, what, count):
+    """(address, is_device) of >= count float64 elements: a numpy array, or a tensor (CPU or device) of 8-byte elements."""
+    return address(buf, what, ("float64",), at_least=count, tensor_dtypes=8)
 
 
 def _denoise_params(width, height, iterations=0, normal_squarings=0, sigma_color=0.0, sigma_plane=0.0, albedo_floor=0.0,
@@ -92,18 +77,10 @@ def denoise(accum_a, accum_b, spp_each, guides, out_color=None, out_rgb8=None, d
         else:
             import torch
             out_color = torch.empty((h, w, 3), dtype=torch.float64, device=accum_a.device)
-    pa, dev = _f64_pointer(accum_a, 3 * n, "accum_a")
-    ptrs = [pa]
-    for buf, count, what in ((accum_b, 3 * n, "accum_b"), (guides, RT_GUIDE_DOUBLES * n, "guides"), (out_color, 3 * n, "out_color")):
-        ptr, d = _f64_pointer(buf, count, what)
-        if d != dev:
-            raise ValueError("accum_a, accum_b, guides and out_color must all live on the host or all on the device")
-        ptrs.append(ptr)
-    rgb_ptr = None
-    if out_rgb8 is not None:
-        rgb_ptr, d = _pointer(out_rgb8, 3 * n)
-        if d != dev:
-            raise ValueError("out_rgb8 must live where the other buffers do")
+    bufs = {"accum_a": (accum_a, 3 * n), "accum_b": (accum_b, 3 * n), "guides": (guides, RT_GUIDE_DOUBLES * n), "out_color": (out_color, 3 * n)}
+    ptrs, where = zip(*(_f64(buf, what, count) for what, (buf, count) in bufs.items()))
+    rgb_ptr, rgb_dev = (None, None) if out_rgb8 is None else _pointer(out_rgb8, 3 * n, "out_rgb8")
+    dev = same_place(**dict(zip(bufs, where)), out_rgb8=rgb_dev)
     p = _denoise_params(w, h, **denoise_options)
     if dev:
         p.flags |= RT_OUT_DEVICE
@@ -188,13 +165,9 @@ class engine:
         p = self.params(band_rows, band_count, band_index, flags, stream)
         rows = check(lib.rt_local_rows(ctypes.byref(p), None), "rt_local_rows")
         nbytes = rows * self.width * 3
-        ptr, dev = _pointer(output_image, nbytes)
-        acc_ptr = None
-        if accum is not None:
-            acc_ptr, acc_dev = _pointer(accum.view(np.uint8) if isinstance(accum, np.ndarray) else accum, nbytes * 8)
-            if acc_dev != dev:
-                raise ValueError("output_image and accum must both live on the host or both on the device")
-        if dev:
+        ptr, dev = _pointer(output_image, nbytes, "output_image")
+        acc_ptr, acc_dev = (None, None) if accum is None else address(accum, "accum", ANY, min_bytes=nbytes * 8)
+        if same_place(output_image=dev, accum=acc_dev):
             p.flags |= RT_OUT_DEVICE
         st = rt_stats()
         check(lib.rt_render(self._scene, ctypes.byref(self.cam.c), ctypes.byref(p), ctypes.c_void_p(ptr),
@@ -232,13 +205,9 @@ class engine:
         n = rows * self.width
         if guides is None:
             guides = np.empty((rows, self.width, RT_GUIDE_DOUBLES), np.float64)
-        ptr, dev = _f64_pointer(guides, RT_GUIDE_DOUBLES * n, "guides")
-        rays_ptr = None
-        if rays is not None:
-            rays_ptr, rays_dev = _f64_pointer(rays, 7 * n, "rays")
-            if rays_dev != dev:
-                raise ValueError("guides and rays must both live on the host or both on the device")
-        if dev:
+        ptr, dev = _f64(guides, "guides", RT_GUIDE_DOUBLES * n)
+        rays_ptr, rays_dev = (None, None) if rays is None else _f64(rays, "rays", 7 * n)
+        if same_place(guides=dev, rays=rays_dev):
             p.flags |= RT_OUT_DEVICE
         check(lib.rt_render_guides(self._scene, ctypes.byref(self.cam.c), ctypes.byref(p), ctypes.c_void_p(ptr),
                                    ctypes.c_void_p(rays_ptr) if rays_ptr else None), "engine.render_guides")
@@ -259,13 +228,9 @@ class engine:
                  | (RT_WAVEFRONT if self.wavefront else 0))
         p = self.params(None, 1, 0, flags, denoise_options.pop("stream", None))
         n = self.height * self.width
-        ptr, dev = _pointer(output_image, 3 * n)
-        color_ptr = None
-        if color is not None:
-            color_ptr, color_dev = _f64_pointer(color, 3 * n, "color")
-            if color_dev != dev:
-                raise ValueError("output_image and color must both live on the host or both on the device")
-        if dev:
+        ptr, dev = _pointer(output_image, 3 * n, "output_image")
+        color_ptr, color_dev = (None, None) if color is None else _f64(color, "color", 3 * n)
+        if same_place(output_image=dev, color=color_dev):
             p.flags |= RT_OUT_DEVICE
         d = _denoise_params(self.width, self.height, **denoise_options)
         st = rt_stats()
@@ -301,33 +266,14 @@ class engine:
             raise TypeError(f"run_noise_target: unknown options {sorted(opts)}")
         rows = check(lib.rt_local_rows(ctypes.byref(p), None), "rt_local_rows")
         npix = rows * self.width
-        ptr, dev = _pointer(output_image, 3 * npix)
-        ptrs = []
-        for buf, per, what in ((accum, 3, "accum"), (moments, 2, "moments")):
-            if buf is None:
-                ptrs.append(None)
-                continue
-            a, d = _f64_pointer(buf, per * npix, what)
-            if d != dev:
-                raise ValueError(f"output_image and {what} must both live on the host or both on the device")
-            ptrs.append(ctypes.c_void_p(a))
-        cnt_ptr = None
-        if counts is not None:
-            if isinstance(counts, np.ndarray):
-                ok = counts.flags.c_contiguous and counts.dtype == np.int32 and counts.size >= npix
-                a, d = (counts.ctypes.data if ok else None), False
-            elif hasattr(counts, "data_ptr"):
-                ok = counts.is_contiguous() and str(counts.dtype) == "torch.int32" and counts.numel() >= npix
-                a, d = (counts.data_ptr() if ok else None), counts.device.type != "cpu"
-            else:
-                raise TypeError("counts must be a numpy array or a torch tensor")
-            if not ok:
-                raise ValueError(f"counts must be a contiguous int32 buffer of >= {npix} elements")
-            if d != dev:
-                raise ValueError("output_image and counts must both live on the host or both on the device")
-            cnt_ptr = ctypes.c_void_p(a)
-        if dev:
+        ptr, dev = _pointer(output_image, 3 * npix, "output_image")
+        acc_ptr, acc_dev = (None, None) if accum is None else _f64(accum, "accum", 3 * npix)
+        mom_ptr, mom_dev = (None, None) if moments is None else _f64(moments, "moments", 2 * npix)
+        cnt_ptr, cnt_dev = (None, None) if counts is None else address(counts, "counts", ("int32",), at_least=npix)
+        if same_place(output_image=dev, accum=acc_dev, counts=cnt_dev, moments=mom_dev):
             p.flags |= RT_OUT_DEVICE
+        ptrs = [None if a is None else ctypes.c_void_p(a) for a in (acc_ptr, mom_ptr)]
+        cnt_ptr = None if cnt_ptr is None else ctypes.c_void_p(cnt_ptr)
         st, res = rt_stats(), rt_noise_result()
         check(lib.rt_render_noise_target(self._scene, ctypes.byref(self.cam.c), ctypes.byref(p), ctypes.byref(n), ctypes.c_void_p(ptr), ptrs[0],
                                          cnt_ptr, ptrs[1], ctypes.byref(st), ctypes.byref(res)), "engine.run_noise_target")
@@ -347,13 +293,9 @@ class engine:
         p = self.params(None, 1, 0, 0, None)
         p.samples_per_pass = int(samples_per_pass)
         nbytes = self.height * self.width * 3
-        ptr, dev = _pointer(output_image, nbytes)
-        acc_ptr = None
-        if accum is not None:
-            acc_ptr, acc_dev = _pointer(accum.view(np.uint8) if isinstance(accum, np.ndarray) else accum, nbytes * 8)
-            if acc_dev != dev:
-                raise ValueError("output_image and accum must both live on the host or both on the device")
-        if dev:
+        ptr, dev = _pointer(output_image, nbytes, "output_image")
+        acc_ptr, acc_dev = (None, None) if accum is None else address(accum, "accum", ANY, min_bytes=nbytes * 8)
+        if same_place(output_image=dev, accum=acc_dev):
             p.flags |= RT_OUT_DEVICE
         errors = []
 

@@ -16,8 +16,9 @@ import ctypes
 
 import numpy as np
 
+from ._buffers import address, same_place, scene_background, stream_handle
 from ._lib import (RT_FP64, RT_GLOBAL_SCENE, RT_HIT_DOUBLES, RT_OUT_DEVICE, RT_Q_ANY_HIT, RT_Q_NO_MEDIA, check, lib, rt_params, rt_query_params,
-                   rt_radiance_params, rt_scene_info, rt_stats)
+                   rt_radiance_params, rt_stats)
 from .scene import _SceneHandle, hittable_list, scene
 
 # columns of a hit record (RT_HIT_DOUBLES = 12)
@@ -58,28 +59,14 @@ def _native_scene(objects):
     return objects
 
 
-def _is_tensor(x):
-    return hasattr(x, "data_ptr")
-
-
-def _f64_buffer(buf, shape, what, dev, device_index):
-    """Address of a float64 buffer of exactly `shape`, checked as engine._f64_pointer checks (dtype, contiguity, size) and
-    for living where the rays do."""
-    if isinstance(buf, np.ndarray):
-        if dev:
-            raise ValueError(f"{what} must be a torch tensor on the scene's device, as rays is")
-        if buf.dtype != np.float64 or not buf.flags.c_contiguous or tuple(buf.shape) != shape:
-            raise ValueError(f"{what} must be a C-contiguous float64 array of shape {shape}")
-        return buf.ctypes.data
-    if _is_tensor(buf):
-        if not dev:
-            raise ValueError(f"{what} must be a numpy array, as rays is")
-        if str(buf.dtype) != "torch.float64" or not buf.is_contiguous() or tuple(buf.shape) != shape:
-            raise ValueError(f"{what} must be a contiguous float64 tensor of shape {shape}")
-        if buf.device.type == "cpu" or (buf.device.index or 0) != device_index:
-            raise ValueError(f"{what} must live on the scene's device (cuda:{device_index})")
-        return buf.data_ptr()
-    raise TypeError(f"{what} must be a numpy array or a torch tensor")
+def _rays(rays, device_index):
+    """(n, address, is_device) of an (n, 7) float64 ray buffer: a numpy array, or a tensor on the scene's device."""
+    if not hasattr(rays, "shape"):
+        raise TypeError("rays must be a numpy array or a torch tensor")
+    if len(rays.shape) != 2 or int(rays.shape[1]) != 7:
+        raise ValueError("rays must have shape (n, 7): origin, direction, time")
+    n = int(rays.shape[0])
+    return (n,) + address(rays, "rays", ("float64",), shape=(n, 7), device_index=device_index)
 
 
 def query_rays(objects, rays, t_max=None, any_hit=False, no_media=False, global_scene=False, out=None, stream=None):
@@ -95,84 +82,29 @@ def query_rays(objects, rays, t_max=None, any_hit=False, no_media=False, global_
     array / tensor: 1 where some non-medium primitive lies in the interval.  global_scene forces the HBM traversal on a
     scene that has an LDS image (A/B, tests)."""
     handle = _native_scene(objects)
-    dev = _is_tensor(rays)
-    if not dev and not isinstance(rays, np.ndarray):
-        raise TypeError("rays must be a numpy array or a torch tensor")
-    if len(rays.shape) != 2 or int(rays.shape[1]) != 7:
-        raise ValueError("rays must have shape (n, 7): origin, direction, time")
-    n = int(rays.shape[0])
-    rays_ptr = _f64_buffer(rays, (n, 7), "rays", dev, handle.device)
-    tmax_ptr = None if t_max is None else _f64_buffer(t_max, (n,), "t_max", dev, handle.device)
+    n, rays_ptr, dev = _rays(rays, handle.device)
+    tmax_ptr, tmax_dev = (None, None) if t_max is None else address(t_max, "t_max", ("float64",), shape=(n,), device_index=handle.device)
     if dev:
         import torch
     if any_hit:
         if out is None:
             out = torch.empty((n,), dtype=torch.uint8, device=rays.device) if dev else np.empty((n,), np.uint8)
-        elif isinstance(out, np.ndarray):
-            if dev or out.dtype not in (np.uint8, np.bool_) or not out.flags.c_contiguous or out.shape != (n,):
-                raise ValueError(f"out must be a C-contiguous uint8 or bool array of shape ({n},) living where rays does")
-        elif _is_tensor(out):
-            if (not dev or str(out.dtype) not in ("torch.uint8", "torch.bool") or not out.is_contiguous() or tuple(out.shape) != (n,)
-                    or out.device != rays.device):
-                raise ValueError(f"out must be a contiguous uint8 or bool tensor of shape ({n},) on the rays' device")
-        else:
-            raise TypeError("out must be a numpy array or a torch tensor")
-        out_ptr = out.data_ptr() if dev else out.ctypes.data
+        out_ptr, out_dev = address(out, "out", ("uint8", "bool"), shape=(n,), device_index=handle.device)
     else:
         if out is None:
             out = (torch.empty((n, RT_HIT_DOUBLES), dtype=torch.float64, device=rays.device) if dev
                    else np.empty((n, RT_HIT_DOUBLES), np.float64))
-        out_ptr = _f64_buffer(out, (n, RT_HIT_DOUBLES), "out", dev, handle.device)
+        out_ptr, out_dev = address(out, "out", ("float64",), shape=(n, RT_HIT_DOUBLES), device_index=handle.device)
+    same_place(rays=dev, t_max=tmax_dev, out=out_dev)
     q = rt_query_params()
     q.flags = ((RT_OUT_DEVICE if dev else 0) | (RT_GLOBAL_SCENE if global_scene else 0) | (RT_Q_ANY_HIT if any_hit else 0)
                | (RT_Q_NO_MEDIA if no_media else 0))
-    if dev:
-        if stream is None:
-            stream = torch.cuda.current_stream(rays.device)
-        q.stream = getattr(stream, "cuda_stream", stream)
-        if not q.stream:
-            # torch's default stream has the null handle, which rt_query_rays reads as "the scene's own stream" (and then
-            # waits for the query): that stream is not ordered after the default one, so the inputs are finished first
-            torch.cuda.default_stream(rays.device).synchronize()
-    elif stream is not None:
-        raise ValueError("stream applies to device tensors only: the host path runs on the scene's own stream and blocks")
+    q.stream = stream_handle(stream, rays.device if dev else None)
     hits_arg = None if any_hit else ctypes.c_void_p(out_ptr)
     occ_arg = ctypes.c_void_p(out_ptr) if any_hit else None
     check(lib.rt_query_rays(handle, ctypes.byref(q), ctypes.c_void_p(rays_ptr), None if tmax_ptr is None else ctypes.c_void_p(tmax_ptr),
                             n, hits_arg, occ_arg), "query_rays")
     return out if any_hit else HitRecords(out)
-
-
-def _u64_buffer(buf, count, what, dev, device_index):
-    """Address of `count` 64-bit PCG states: a uint64 numpy array, or a torch.int64 / torch.uint64 tensor on the device."""
-    if isinstance(buf, np.ndarray):
-        if dev:
-            raise ValueError(f"{what} must be a torch tensor on the scene's device, as rays is")
-        if buf.dtype != np.uint64 or not buf.flags.c_contiguous or tuple(buf.shape) != (count,):
-            raise ValueError(f"{what} must be a C-contiguous uint64 array of shape ({count},)")
-        return buf.ctypes.data
-    if _is_tensor(buf):
-        if not dev:
-            raise ValueError(f"{what} must be a numpy array, as rays is")
-        if str(buf.dtype) not in ("torch.int64", "torch.uint64") or not buf.is_contiguous() or tuple(buf.shape) != (count,):
-            raise ValueError(f"{what} must be a contiguous int64 or uint64 tensor of shape ({count},)")
-        if buf.device.type == "cpu" or (buf.device.index or 0) != device_index:
-            raise ValueError(f"{what} must live on the scene's device (cuda:{device_index})")
-        return buf.data_ptr()
-    raise TypeError(f"{what} must be a numpy array or a torch tensor")
-
-
-def _stream_handle(stream, device):
-    """The raw hipStream_t of `stream` (a torch stream or a handle; None: torch's current stream on `device`).  The null
-    handle means "the library's own stream, and wait": torch's default stream is then drained first, so the inputs are
-    complete when the call is made."""
-    import torch
-    if stream is None:
-        stream = torch.cuda.current_stream(device)
-    handle = getattr(stream, "cuda_stream", stream)
-    if not handle:
-        torch.cuda.default_stream(device).synchronize()
-    return handle
 
 
 def radiance_rays(objects, rays, spp=1, max_depth=50, seed=0, sample_base=0, id_base=0, rng=None, background=None, global_scene=False,
@@ -191,40 +123,28 @@ def radiance_rays(objects, rays, spp=1, max_depth=50, seed=0, sample_base=0, id_
     hipStream_t; default: torch's current stream) -- the call then returns without waiting unless stats is asked for.
     Calls on one scene share its workspace: order them on one stream, or synchronise between them.  With camera_rays'
     rays and states, the in-order sum over a pixel's samples equals engine.run's accum bit for bit."""
-    if background is None and isinstance(objects, scene):
-        background = objects.background
     handle = _native_scene(objects)
-    dev = _is_tensor(rays)
-    if not dev and not isinstance(rays, np.ndarray):
-        raise TypeError("rays must be a numpy array or a torch tensor")
-    if len(rays.shape) != 2 or int(rays.shape[1]) != 7:
-        raise ValueError("rays must have shape (n, 7): origin, direction, time")
-    n = int(rays.shape[0])
+    n, rays_ptr, dev = _rays(rays, handle.device)
     spp = int(spp)
     if spp < 1:
         raise ValueError("spp must be >= 1")
-    rays_ptr = _f64_buffer(rays, (n, 7), "rays", dev, handle.device)
-    rng_ptr = None if rng is None else _u64_buffer(rng, n * spp, "rng", dev, handle.device)
+    rng_ptr, rng_dev = (None, None) if rng is None else address(rng, "rng", ("uint64",), shape=(n * spp,), device_index=handle.device,
+                                                                tensor_dtypes=("int64", "uint64"))
     if out is None:
         if dev:
             import torch
             out = torch.empty((n, 3), dtype=torch.float64, device=rays.device)
         else:
             out = np.empty((n, 3), np.float64)
-    out_ptr = _f64_buffer(out, (n, 3), "out", dev, handle.device)
-    if background is None:
-        info = rt_scene_info()
-        check(lib.rt_scene_info_get(handle, ctypes.byref(info)), "rt_scene_info_get")
-        background = tuple(info.background)
+    out_ptr, out_dev = address(out, "out", ("float64",), shape=(n, 3), device_index=handle.device)
+    same_place(rays=dev, rng=rng_dev, out=out_dev)
+    background = scene_background(objects, handle, background)
     q = rt_radiance_params()
     q.flags = (RT_OUT_DEVICE if dev else 0) | (RT_GLOBAL_SCENE if global_scene else 0)
     q.spp, q.max_depth, q.sample_base, q.seed, q.id_base = spp, int(max_depth), int(sample_base), int(seed), int(id_base)
     for c in range(3):
         q.background[c] = float(background[c])
-    if dev:
-        q.stream = _stream_handle(stream, rays.device)
-    elif stream is not None:
-        raise ValueError("stream applies to device tensors only: the host path runs on the scene's own stream and blocks")
+    q.stream = stream_handle(stream, rays.device if dev else None)
     st = rt_stats()
     check(lib.rt_radiance_rays(handle, ctypes.byref(q), ctypes.c_void_p(rays_ptr), None if rng_ptr is None else ctypes.c_void_p(rng_ptr), n,
                                ctypes.c_void_p(out_ptr), ctypes.byref(st) if stats else None), "radiance_rays")
@@ -248,8 +168,7 @@ def camera_rays(cam, width, height, spp, seed=0, sample_base=0, bands=None, devi
         raise ValueError("spp must be >= 1")
     ne = rows * p.width * p.spp
     if device is None:
-        if stream is not None:
-            raise ValueError("stream applies to device tensors only")
+        stream_handle(stream, None)
         rays, rng = np.empty((ne, 7), np.float64), np.empty((ne,), np.uint64)
         rays_ptr, rng_ptr, index = rays.ctypes.data, rng.ctypes.data, 0
     else:
@@ -262,7 +181,7 @@ def camera_rays(cam, width, height, spp, seed=0, sample_base=0, bands=None, devi
         rng = torch.empty((ne,), dtype=torch.int64, device=tdev)
         rays_ptr, rng_ptr = rays.data_ptr(), rng.data_ptr()
         p.flags = RT_OUT_DEVICE
-        p.stream = _stream_handle(stream, tdev)
+        p.stream = stream_handle(stream, tdev)
     check(lib.rt_camera_rays(ctypes.byref(cam.c), ctypes.byref(p), int(sample_base), index, ctypes.c_void_p(rays_ptr), ctypes.c_void_p(rng_ptr)),
           "camera_rays")
     return rays, rng

@@ -13,25 +13,9 @@ import ctypes
 
 import numpy as np
 
-from ._lib import RT_FP64, RT_GLOBAL_SCENE, RT_OUT_DEVICE, check, lib, rt_camera, rt_params, rt_scene_info, rt_stats
-from .rays import _is_tensor, _native_scene, _stream_handle
-from .scene import scene
-
-
-def _out_buffer(buf, shape, np_dtype, torch_dtype, what, device_index):
-    """(address, is_device) of an output buffer of exactly `shape`: a C-contiguous numpy array, or a contiguous tensor on
-    the scene's device."""
-    if isinstance(buf, np.ndarray):
-        if buf.dtype != np_dtype or not buf.flags.c_contiguous or tuple(buf.shape) != shape:
-            raise ValueError(f"{what} must be a C-contiguous {np.dtype(np_dtype).name} array of shape {shape}")
-        return buf.ctypes.data, False
-    if _is_tensor(buf):
-        if str(buf.dtype) != torch_dtype or not buf.is_contiguous() or tuple(buf.shape) != shape:
-            raise ValueError(f"{what} must be a contiguous {torch_dtype} tensor of shape {shape}")
-        if buf.device.type == "cpu" or (buf.device.index or 0) != device_index:
-            raise ValueError(f"{what} must live on the scene's device (cuda:{device_index})")
-        return buf.data_ptr(), True
-    raise TypeError(f"{what} must be a numpy array or a torch tensor")
+from ._buffers import address, is_tensor, same_place, scene_background, stream_handle
+from ._lib import RT_FP64, RT_GLOBAL_SCENE, RT_OUT_DEVICE, check, lib, rt_camera, rt_params, rt_stats
+from .rays import _native_scene
 
 
 def render_views(world_or_objects, cams, width, height, spp, max_depth=50, seed=0, seeds=None, background=None, global_scene=False,
@@ -50,8 +34,6 @@ def render_views(world_or_objects, cams, width, height, spp, max_depth=50, seed=
     asked for.  Calls on one scene share its workspace: order them on one stream, or synchronise between them.
     Every view has the same size, samples and depth; a frame of more than 2^31 paths takes engine.run, which splits it
     into passes."""
-    if background is None and isinstance(world_or_objects, scene):
-        background = world_or_objects.background
     handle = _native_scene(world_or_objects)
     cams = list(cams)
     for c in cams:
@@ -68,13 +50,10 @@ def render_views(world_or_objects, cams, width, height, spp, max_depth=50, seed=
     shape = (nviews, height, width, 3)
     want_accum = accum is not False and accum is not None
     acc = None if not want_accum or accum is True else accum
-    given = [b for b in (out, acc) if b is not None]
-    dev = any(_is_tensor(b) for b in given)
-    if dev:
+    # buffers that are not given are allocated where the given ones live
+    if any(is_tensor(b) for b in (out, acc)):
         import torch
-        if not all(_is_tensor(b) for b in given):
-            raise ValueError("out and accum must both be numpy arrays or both be tensors on the scene's device")
-        tdev = next(b.device for b in given)
+        tdev = next(b.device for b in (out, acc) if is_tensor(b))
         if out is None:
             out = torch.empty(shape, dtype=torch.uint8, device=tdev)
         if want_accum and acc is None:
@@ -84,26 +63,17 @@ def render_views(world_or_objects, cams, width, height, spp, max_depth=50, seed=
             out = np.empty(shape, np.uint8)
         if want_accum and acc is None:
             acc = np.empty(shape, np.float64)
-    out_ptr, out_dev = _out_buffer(out, shape, np.uint8, "torch.uint8", "out", handle.device)
-    acc_ptr = None
-    if want_accum:
-        acc_ptr, acc_dev = _out_buffer(acc, shape, np.float64, "torch.float64", "accum", handle.device)
-        if acc_dev != out_dev:
-            raise ValueError("out and accum must both be numpy arrays or both be tensors on the scene's device")
-    if background is None:
-        info = rt_scene_info()
-        check(lib.rt_scene_info_get(handle, ctypes.byref(info)), "rt_scene_info_get")
-        background = tuple(info.background)
+    out_ptr, out_dev = address(out, "out", ("uint8",), shape=shape, device_index=handle.device)
+    acc_ptr, acc_dev = address(acc, "accum", ("float64",), shape=shape, device_index=handle.device) if want_accum else (None, None)
+    same_place(out=out_dev, accum=acc_dev)
+    background = scene_background(world_or_objects, handle, background)
     p = rt_params()
     p.width, p.height, p.spp, p.max_depth, p.seed, p.fp_mode = width, height, spp, int(max_depth), int(seed), RT_FP64
     p.band_rows, p.band_count, p.band_index = height, 1, 0
     p.flags = (RT_OUT_DEVICE if out_dev else 0) | (RT_GLOBAL_SCENE if global_scene else 0)
     for c in range(3):
         p.background[c] = float(background[c])
-    if out_dev:
-        p.stream = _stream_handle(stream, out.device)
-    elif stream is not None:
-        raise ValueError("stream applies to device tensors only: the host path runs on the scene's own stream and blocks")
+    p.stream = stream_handle(stream, out.device if out_dev else None)
     table = (rt_camera * max(nviews, 1))(*[c.c for c in cams])
     seed_arr = None if seeds is None else (ctypes.c_uint64 * max(nviews, 1))(*seeds)
     st = rt_stats()

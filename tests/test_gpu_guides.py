@@ -118,6 +118,22 @@ def test_device_buffers_receive_the_same_records(gpu):
     assert same_bits(r.cpu().numpy(), np.ascontiguousarray(rays)).all()
 
 
+@pytest.mark.parametrize("scene", ["1", "cow"])
+def test_device_buffers_on_a_side_stream_receive_the_same_records(gpu, scene):
+    # device buffers written in place on the caller's stream (the call waits all the same); the host frame is the reference
+    import torch
+    W, H = 37, 23
+    _, eng, guides, rays = frame(scene, W, H)
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        g = torch.zeros((H, W, 10), dtype=torch.float64, device="cuda")
+        r = torch.zeros((H, W, 7), dtype=torch.float64, device="cuda")
+        eng.render_guides(guides=g, rays=r, stream=side.cuda_stream)
+        got_g, got_r = g.cpu().numpy(), r.cpu().numpy()
+    assert same_bits(got_g, np.ascontiguousarray(guides)).all()
+    assert same_bits(got_r, np.ascontiguousarray(rays)).all()
+
+
 def test_albedo_is_the_first_hits_material_colour(gpu):
     art.reset_scene_rng()
     red, green, blue, steel = (0.8, 0.1, 0.15), (0.2, 0.7, 0.25), (0.1, 0.3, 0.9), (0.6, 0.55, 0.4)

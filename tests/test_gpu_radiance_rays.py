@@ -161,6 +161,29 @@ def test_host_and_device_buffers_agree(gpu, scene):
     assert dst["segments"] == st["segments"] and dst["primary"] == 5 * len(rays) and st["ms"] > 0
 
 
+@pytest.mark.parametrize("scene", ["1", "cow"])
+def test_device_buffers_on_the_null_stream_agree_with_host_buffers(gpu, scene):
+    # torch's default stream has the null handle: the call runs on the scene's own stream and waits.  65 rays: a wave and one
+    import torch
+    world, rays = world_of(scene), np.array(probe_rays(scene)[:65])  # a writable copy
+    host = art.radiance_rays(world, rays, spp=2, seed=3)
+    assert torch.cuda.current_stream().cuda_stream == 0
+    out = torch.full((65, 3), 7.0, dtype=torch.float64, device="cuda")
+    got = art.radiance_rays(world, torch.from_numpy(rays).to("cuda"), spp=2, seed=3, out=out)
+    assert got is out and (bits(out.cpu().numpy()) == bits(host)).all()
+    assert host.max() > 0.0
+
+
+def test_camera_rays_on_the_null_stream_agree_with_host_buffers(gpu):
+    import torch
+    cam = camera_of(world_of("1"), 13, 5)
+    rays, rng = art.camera_rays(cam, 13, 5, 1, seed=7)  # 65 rays
+    assert torch.cuda.current_stream().cuda_stream == 0
+    d_rays, d_rng = art.camera_rays(cam, 13, 5, 1, seed=7, device=0)
+    assert d_rays.is_cuda and tuple(d_rays.shape) == (65, 7)
+    assert (bits(d_rays.cpu().numpy()) == bits(rays)).all() and (d_rng.cpu().numpy().view(np.uint64) == rng).all()
+
+
 # ------------------------------------------------------------------------------------------------ 7. the workspace fault point
 def test_a_refused_workspace_fails_the_call_and_the_next_one_works(gpu, options):
     # an injected allocation refusal on the host (test.fault_workspace_bytes), on a scene of its own: its workspace is empty

@@ -183,3 +183,18 @@ def test_host_and_device_buffers_agree(gpu, scene):
     assert (out.cpu().numpy() == rgb).all() and (bits(sums.cpu().numpy()) == bits(acc)).all()
     host = np.zeros((5, H, W, 3), np.uint8)
     assert art.render_views(world, cams, W, H, SPP, seeds=seeds, out=host) is host and (host == rgb).all()
+
+
+@pytest.mark.parametrize("scene", ["1", "cow"])
+def test_device_buffers_on_the_null_stream_agree_with_host_buffers(gpu, scene):
+    # torch's default stream has the null handle: the call runs on the scene's own stream and waits.  2 views of 16 x 16 x 2
+    import torch
+    world = world_of(scene)
+    cams = cameras(world, 16, 16)[:2]
+    host, host_sums = art.render_views(world, cams, 16, 16, 2, seeds=[5, 6], accum=True)
+    assert torch.cuda.current_stream().cuda_stream == 0
+    out = torch.full((2, 16, 16, 3), 7, dtype=torch.uint8, device="cuda")
+    sums = torch.full((2, 16, 16, 3), 7.0, dtype=torch.float64, device="cuda")
+    assert art.render_views(world, cams, 16, 16, 2, seeds=[5, 6], out=out, accum=sums)[0] is out
+    assert (out.cpu().numpy() == host).all() and (bits(sums.cpu().numpy()) == bits(host_sums)).all()
+    assert host.max() > 0

@@ -266,6 +266,25 @@ def test_a_partial_update_of_the_middle_third(gpu):
     same_queries(a, b, random_rays(p1))
 
 
+@pytest.mark.parametrize("name", ["grid", "cow"])
+def test_a_timed_update_on_a_side_stream_equals_the_host_update(gpu, name):
+    # timing on a caller's stream: the call runs there and waits.  Three triangles from the middle of the mesh
+    import torch
+    p0 = mesh(name)
+    p1 = twist(p0)
+    first = len(p0) // 2
+    part = np.ascontiguousarray(p1[first:first + 3])
+    a, b, cam = build(p0, p1), build(p0, p1), frame_camera(p1)
+    art.update_triangles(b, part, first=first)  # host buffers
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        ms = art.update_triangles(a, torch.from_numpy(part).to("cuda"), first=first, timing=True)
+    assert ms > 0
+    assert (bits(art.scene_triangles(a)) == bits(art.scene_triangles(b))).all()
+    assert (bits(art.scene_triangles(a)[first:first + 3]) == bits(part)).all()
+    assert same_render(render(a, cam), render(b, cam))
+
+
 # ------------------------------------------------------------------------------------------------ 5. loose primitives
 def test_loose_triangles_of_an_unmerged_world_are_updated(gpu, options):
     options("compile.world_merge", 0)  # the world stays a list: the floor's two triangles are prim objects (obj_prims)
