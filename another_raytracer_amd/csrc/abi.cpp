@@ -33,13 +33,15 @@ struct rt_scene {
     int device = 0;
     std::unique_ptr<art::Renderer> renderer;  // created on first render (scene build/dump works without a GPU)
     art::Renderer& device_renderer() { return renderer ? *renderer : *(renderer = std::make_unique<art::Renderer>(flat, device)); }
-    // rt_scene_update_triangles leaves `flat` stale: the renderer counts the updates, and whoever reads the vertices or
-    // the boxes of `flat` (rt_scene_triangles_get, rt_scene_save) takes them from the device first
+    // rt_scene_update_triangles and rt_scene_update_spheres leave `flat` stale: the renderer counts the updates, and whoever
+    // reads the vertices, the spheres or the boxes of `flat` (rt_scene_triangles_get, rt_scene_spheres_get, rt_scene_save)
+    // takes them from the device first
     uint64_t synced = 0;
     bool updated() const { return renderer && renderer->generation() > 0; }
     void sync_flat() {
         if (!renderer || renderer->generation() == synced) return;
         const art::FlatScene& now = renderer->current_flat();
+        flat.spheres = now.spheres;
         flat.tris = now.tris;
         flat.nodes = now.nodes;
         synced = renderer->generation();
@@ -220,7 +222,7 @@ size_t rt_scene_dump(const rt_scene* s, char* buf, size_t cap) {
         return 0;
     }
     if (s->updated()) {
-        fail(RT_E_SCENE, "the scene's triangles were updated (rt_scene_update_triangles): its object graph no longer describes it");
+        fail(RT_E_SCENE, "the scene's triangles or spheres were updated (rt_scene_update_triangles, rt_scene_update_spheres): its object graph no longer describes it");
         return 0;
     }
     try {
@@ -280,6 +282,63 @@ int rt_scene_update_triangles(rt_scene* s, const rt_update_params* u, const doub
         s->device_renderer().update_triangles(p, static_cast<size_t>(first), static_cast<size_t>(n), device, u->stream, ms);
         return RT_OK;
     });
+}
+
+int64_t rt_scene_spheres_get(rt_scene* s, double* s_out, int64_t cap) {
+    if (!s) return fail(RT_E_INVALID, "rt_scene_spheres_get: scene is NULL");
+    const int64_t count = static_cast<int64_t>(s->flat.spheres.size());
+    if (!s_out) return count;
+    if (cap < count) return fail(RT_E_INVALID, "rt_scene_spheres_get: s_out holds " + std::to_string(cap) + " spheres, the scene has " + std::to_string(count));
+    const int rc = guard(RT_E_DEVICE, [&] {
+        s->sync_flat();
+        return RT_OK;
+    });
+    if (rc != RT_OK) return rc;
+    for (int64_t k = 0; k < count; ++k) {
+        const art::SphereRec& sp = s->flat.spheres[static_cast<size_t>(k)];
+        s_out[4 * k] = sp.c[0], s_out[4 * k + 1] = sp.c[1], s_out[4 * k + 2] = sp.c[2], s_out[4 * k + 3] = sp.r;
+    }
+    return count;
+}
+
+int rt_scene_update_spheres(rt_scene* s, const rt_update_params* u, const double* v, int64_t first, int64_t n, double* ms) {
+    if (!s || !u) return fail(RT_E_INVALID, "rt_scene_update_spheres: scene and params must be non-NULL");
+    const int64_t count = static_cast<int64_t>(s->flat.spheres.size());
+    if (first < 0 || n < 0 || first > count || n > count - first)
+        return fail(RT_E_INVALID, "rt_scene_update_spheres: [first, first + n) must lie within the scene's " + std::to_string(count) + " spheres");
+    if (u->flags & ~RT_OUT_DEVICE) return fail(RT_E_INVALID, "rt_scene_update_spheres takes RT_OUT_DEVICE only");
+    if (u->stream && !(u->flags & RT_OUT_DEVICE))
+        return fail(RT_E_INVALID, "rt_scene_update_spheres: stream needs RT_OUT_DEVICE (host buffers run on the scene's own stream)");
+    if (n > 0 && !v) return fail(RT_E_INVALID, "rt_scene_update_spheres: s is NULL");
+    const bool device = (u->flags & RT_OUT_DEVICE) != 0;
+    if (!device)
+        for (int64_t i = 0; i < 4 * n; ++i) {
+            if (!std::isfinite(v[i]))
+                return fail(RT_E_INVALID, "rt_scene_update_spheres: value " + std::to_string(i % 4) + " of sphere " + std::to_string(first + i / 4) + " is not finite");
+            if (i % 4 == 3 && !(v[i] > 0.0))
+                return fail(RT_E_INVALID, "rt_scene_update_spheres: the radius of sphere " + std::to_string(first + i / 4) + " is not positive");
+        }
+    if (ms) *ms = 0;
+    if (n == 0) return RT_OK;
+    return guard(RT_E_DEVICE, [&] {
+        s->device_renderer().update_spheres(v, static_cast<size_t>(first), static_cast<size_t>(n), device, u->stream, ms);
+        return RT_OK;
+    });
+}
+
+int64_t rt_scene_lds_image_get(rt_scene* s, int32_t rebuilt, uint8_t* out, int64_t cap) {
+    if (!s) return fail(RT_E_INVALID, "rt_scene_lds_image_get: scene is NULL");
+    if (rebuilt != 0 && rebuilt != 1) return fail(RT_E_INVALID, "rt_scene_lds_image_get: rebuilt must be 0 or 1");
+    int64_t bytes = 0;
+    const int rc = guard(RT_E_DEVICE, [&] {
+        art::Renderer& r = s->device_renderer();
+        bytes = static_cast<int64_t>(r.lds_image_get(rebuilt != 0, nullptr));
+        if (out && bytes > 0 && cap < bytes)
+            return fail(RT_E_INVALID, "rt_scene_lds_image_get: out holds " + std::to_string(cap) + " bytes, the image has " + std::to_string(bytes));
+        if (out && bytes > 0) r.lds_image_get(rebuilt != 0, out);
+        return static_cast<int>(RT_OK);
+    });
+    return rc != RT_OK ? rc : bytes;
 }
 
 int rt_scene_bvh_get(rt_scene* s, void* nodes_out, int64_t node_cap, uint32_t* primrefs_out, int64_t ref_cap, int64_t* n_nodes, int64_t* n_primrefs) {

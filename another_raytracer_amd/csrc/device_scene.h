@@ -30,6 +30,7 @@ struct DeviceScene {
     std::vector<uint32_t> slot_refs;
     std::vector<uint8_t> slot_pad;
     double* slot_box = nullptr;
+    const uint8_t* slot_pad_dev = nullptr;  // slot_pad on the device (k_update_spheres skips pad slots)
     std::vector<uint32_t> level_begin;
 
     template <class T>
@@ -55,5 +56,9 @@ inline uint32_t stack_rows(int max_stack) { return static_cast<uint32_t>(std::ma
 inline size_t extend_lds_bytes(bool L, uint32_t stack) { return extend_pre_offset(L, stack) + 4 * (kShards + 1); }
 
 void build_device_scene(const FlatScene& f0, DeviceScene& ds);  // device_scene.hip
+// The layout.h LDS scene image of f with its TileReps behind it (kLdsImageBytes + sizeof(TileReps) bytes), or an empty
+// vector when f does not qualify; nmov: its moving spheres, shade_ok: the shading table is complete, tile_reps: the
+// representative slots (0: no tile lists).  build_device_scene uploads it; rt_scene_lds_image_get rebuilds it.
+std::vector<uint8_t> build_lds_image(const FlatScene& f, uint32_t& nmov, bool& shade_ok, uint32_t& tile_reps);
 
 }  // namespace art

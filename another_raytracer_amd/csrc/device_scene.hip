@@ -7,14 +7,16 @@
 #include <limits>
 #include <unordered_map>
 
+#include "lds_image.h"
 #include "options.h"
 #include "tile_lists.h"
 
 namespace art {
 
 // Builds the layout.h LDS scene image when the f64 scene qualifies: spheres only, every BVH node and leaf slot within
-// the plane capacities, and image + stack within one CU's LDS.  Returns an empty vector otherwise.
-static std::vector<uint8_t> lds_scene_image(const FlatScene& f, uint32_t& nmov, bool& shade_ok, uint32_t& tile_reps) {
+// the plane capacities, and image + stack within one CU's LDS.  Returns an empty vector otherwise.  What follows a
+// sphere's centre and radius or a node's boxes is lds_image.h's text, which rt_scene_update_spheres' kernels run too.
+std::vector<uint8_t> build_lds_image(const FlatScene& f, uint32_t& nmov, bool& shade_ok, uint32_t& tile_reps) {
     std::vector<uint8_t> img;
     nmov = 0;
     tile_reps = 0;
@@ -46,21 +48,16 @@ static std::vector<uint8_t> lds_scene_image(const FlatScene& f, uint32_t& nmov, 
     auto put = [&](uint32_t off, const void* v, size_t n) { std::memcpy(img.data() + off, v, n); };
     for (size_t n = 0; n < f.nodes.size(); ++n) {
         const BvhNode& b = f.nodes[n];
-        float planes[6][4];
-        const float* src[6] = {b.lox, b.hix, b.loy, b.hiy, b.loz, b.hiz};
         int32_t child[4];
         for (int c = 0; c < 4; ++c) {
-            // an empty slot becomes an empty leaf behind a point box at (3e38, 3e38, 3e38): no slab test of it needs
-            // a child check, and the astronomically rare ray whose three slab times coincide there finds no primitives
+            // an empty slot becomes an empty leaf behind image_put_node_boxes' point box
             const bool empty = b.child[c] == kNodeEmpty;
-            for (int j = 0; j < 6; ++j) planes[j][c] = empty ? kLdsEmptyBox : src[j][c];
             // inner nodes by their byte offset in a plane (index * 16: device.h traverse), leaves as lds_leaf codes
             child[c] = empty ? kLdsEmptyChild : b.child[c] >= 0 ? b.child[c] * 16 : lds_leaf(leaf_first(b.child[c]), leaf_count(b.child[c]));
         }
-        // per axis: lo, hi, lo (layout.h kLdsNodePlanes), then the child codes as int16
-        const int order[9] = {0, 1, 0, 2, 3, 2, 4, 5, 4};
+        // the nine box planes, then the child codes as int16
         const uint32_t nn = static_cast<uint32_t>(n);
-        for (uint32_t j = 0; j < 9; ++j) put(kLdsOffNodes + (j * kLdsNodeCap + nn) * 16, planes[order[j]], 16);
+        image_put_node_boxes(img.data(), nn, b);
         const int16_t c16[8] = {static_cast<int16_t>(child[0]), static_cast<int16_t>(child[1]), static_cast<int16_t>(child[2]),
                                 static_cast<int16_t>(child[3]), 0, 0, 0, 0};
         put(kLdsOffNodes + (kLdsNodePlaneChild * kLdsNodeCap + nn) * 16, c16, 16);
@@ -80,15 +77,9 @@ static std::vector<uint8_t> lds_scene_image(const FlatScene& f, uint32_t& nmov, 
     for (size_t slot = 0; slot < f.primrefs.size(); ++slot) {
         const uint32_t idx = primref_index(f.primrefs[slot]);
         const auto& sp = f.spheres[idx];
-        // a moving sphere's x and z at time tm are c + tm * (+-0) (moving_sphere.h:72-74) == c + d: the image stores
-        // that value (it differs from c only for c = -0 and d = +0), and the device adds tm * dy to y alone
         const bool moving = (sp.flags & SPH_MOVING) != 0;
-        const double cx = moving ? sp.c[0] + sp.d[0] : sp.c[0], cz = moving ? sp.c[2] + sp.d[2] : sp.c[2];
-        const double p0[2] = {cx, sp.c[1]}, p1[2] = {cz, sp.r * sp.r}, inv_r = 1.0 / sp.r;
         const uint32_t sl = static_cast<uint32_t>(slot);
-        put(kLdsOffSph + sl * 16, p0, 16);
-        put(kLdsOffSph + (kLdsSlotCap + sl) * 16, p1, 16);
-        put(kLdsOffInvR + sl * 8, &inv_r, 8);
+        image_put_sphere(img.data(), sl, sp);
         uint32_t code = idx | (f.mats[sp.mat].type << kLdsRefMatShift);
         const double dy = moving ? sp.d[1] : -0.0;
         put(kLdsOffMov + sl * 8, &dy, 8);
@@ -364,7 +355,7 @@ void build_device_scene(const FlatScene& f0, DeviceScene& ds) {
         uint32_t nmov = 0;
         bool shade_ok = false;
         uint32_t tile_reps = 0;
-        const std::vector<uint8_t> img = ds.leaf_shift ? std::vector<uint8_t>() : lds_scene_image(f, nmov, shade_ok, tile_reps);
+        const std::vector<uint8_t> img = ds.leaf_shift ? std::vector<uint8_t>() : build_lds_image(f, nmov, shade_ok, tile_reps);
         ds.tile_reps = img.empty() ? 0 : tile_reps;
         if (!img.empty()) {
             ds.view.lds_image = ds.upload(img);

@@ -111,6 +111,24 @@ struct UpdateJob {
     double* slot_box;              // 6 doubles per slot: the f64 box of its primitive (refit.h)
 };
 void launch_update_tris(hipStream_t st, const UpdateJob& j);
+// One rt_scene_update_spheres call as k_update_spheres sees it: new (cx, cy, cz, r) s for spheres [first, first + n),
+// written into every array of the uploaded scene that holds one, the LDS scene image (null: none) included.
+struct SphereJob {
+    const double* s;
+    uint32_t first, n;
+    const uint32_t* primrefs;
+    const uint8_t* slot_pad;       // 1: slot i belongs to no leaf (DeviceScene::slot_pad)
+    const ObjRec* objs;
+    uint32_t n_slots, n_objs;
+    SphereRec* spheres;
+    PrimRec80* leaf_prims;
+    PrimRec80* obj_prims;
+    double* slot_box;
+    uint8_t* image;
+};
+void launch_update_spheres(hipStream_t st, const SphereJob& j);
+// k_image_nodes: the nine box planes of every node of the LDS scene image from the (refitted) nodes
+void launch_image_nodes(hipStream_t st, uint8_t* image, const BvhNode* nodes, uint32_t n_nodes);
 // k_refit_level over every level [level_begin[l], level_begin[l + 1]) (refit.h refit_levels), the deepest first
 void launch_refit_levels(hipStream_t st, BvhNode* nodes, uint32_t n_nodes, const double* slot_box, uint32_t n_slots,
                          const std::vector<uint32_t>& level_begin);

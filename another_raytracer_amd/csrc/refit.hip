@@ -2,7 +2,11 @@
 // a triangle (the records, the three leaf-ordered copies, the prim objects' copies) and the f64 box of every leaf slot
 // it touches; k_refit_level then recomputes the child boxes of one tree level from what lies below it (refit.h).  One
 // launch per level, deepest first, on one stream: stream order is the only dependency between the levels.
+// rt_scene_update_spheres: k_update_spheres does the same for centres and radii (the records, the leaf-ordered copy,
+// the prim objects' copies, the slot boxes and the sphere planes of the LDS scene image, lds_image.h), and after the
+// levels k_image_nodes rewrites the image's box planes from the refitted nodes.
 #include "launch.h"
+#include "lds_image.h"
 #include "refit.h"
 
 namespace art {
@@ -49,6 +53,42 @@ __global__ void __launch_bounds__(kRefitBlock) k_update_tris(UpdateJob j) {
     }
 }
 
+// (cx, cy, cz, r) into a sphere record; mat, flags and a moving sphere's d, t0, dt stay: it translates with its motion
+__device__ __forceinline__ void put_sphere(SphereRec& r, const double* v) {
+    r.c[0] = v[0], r.c[1] = v[1], r.c[2] = v[2];
+    r.r = v[3];
+}
+
+__global__ void __launch_bounds__(kRefitBlock) k_update_spheres(SphereJob j) {
+    const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+    // leaf slot i.  A pad slot of the pair-aligned copy holds reference 0, which reads as sphere 0: it belongs to no leaf,
+    // its records stay zero and its box stays empty.  Every slot of a sphere that spatial splits put into several leaves
+    // gets the same bytes (tile_lists.h TileReps).
+    if (i < j.n_slots && !j.slot_pad[i]) {
+        const uint32_t ref = j.primrefs[i];
+        const uint32_t t = primref_index(ref) - j.first;  // (wraps above n for a sphere below `first`)
+        if (primref_type(ref) == PRIM_SPHERE && t < j.n) {
+            SphereRec& r = *reinterpret_cast<SphereRec*>(j.leaf_prims[i].b);
+            put_sphere(r, j.s + 4 * static_cast<size_t>(t));
+            const SphereRec now = r;
+            sphere_box(now, j.slot_box + 6 * static_cast<size_t>(i));
+            if (j.image) image_put_sphere(j.image, i, now);  // (an image scene has no pad slots: its slots are these)
+        }
+    }
+    if (i < j.n) put_sphere(j.spheres[j.first + i], j.s + 4 * static_cast<size_t>(i));  // sphere first + i: its record
+    if (i < j.n_objs && j.objs[i].kind == OBJ_PRIM) {  // a loose sphere of the world, or a constant_medium's boundary
+        const uint32_t ref = static_cast<uint32_t>(j.objs[i].a);
+        const uint32_t t = primref_index(ref) - j.first;
+        if (primref_type(ref) == PRIM_SPHERE && t < j.n) put_sphere(*reinterpret_cast<SphereRec*>(j.obj_prims[i].b), j.s + 4 * static_cast<size_t>(t));
+    }
+}
+
+// One thread per node: the image's box planes from the refitted node (the child-code plane stays: topology does)
+__global__ void __launch_bounds__(kRefitBlock) k_image_nodes(uint8_t* image, const BvhNode* nodes, uint32_t n_nodes) {
+    const uint32_t n = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (n < n_nodes) image_put_node_boxes(image, n, nodes[n]);
+}
+
 // Four lanes per node of [begin, end), one per child
 __global__ void __launch_bounds__(kRefitBlock) k_refit_level(BvhNode* nodes, uint32_t n_nodes, const double* slot_box, uint32_t n_slots,
                                                              uint32_t begin, uint32_t end) {
@@ -61,6 +101,17 @@ void launch_update_tris(hipStream_t st, const UpdateJob& j) {
     const uint32_t threads = std::max(std::max(j.n_slots, j.n), j.n_objs);
     if (threads == 0) return;
     hipLaunchKernelGGL(k_update_tris, dim3((threads + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, j);
+}
+
+void launch_update_spheres(hipStream_t st, const SphereJob& j) {
+    const uint32_t threads = std::max(std::max(j.n_slots, j.n), j.n_objs);
+    if (threads == 0) return;
+    hipLaunchKernelGGL(k_update_spheres, dim3((threads + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, j);
+}
+
+void launch_image_nodes(hipStream_t st, uint8_t* image, const BvhNode* nodes, uint32_t n_nodes) {
+    if (!image || n_nodes == 0) return;
+    hipLaunchKernelGGL(k_image_nodes, dim3((n_nodes + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, image, nodes, n_nodes);
 }
 
 void launch_refit_levels(hipStream_t st, BvhNode* nodes, uint32_t n_nodes, const double* slot_box, uint32_t n_slots,

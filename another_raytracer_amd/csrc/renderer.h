@@ -101,8 +101,16 @@ public:
     // the kernels.  The scene's first update makes the slot boxes and the level table (blocking).  Leaves the host copy
     // stale: generation() counts the updates, current_flat() fetches before it answers.
     void update_triangles(const double* p, size_t first, size_t n, bool device, void* stream, double* ms);
+    // rt_scene_update_spheres: new (cx, cy, cz, r) s (4 doubles each) for spheres [first, first + n) of flat().spheres,
+    // written into every device array that holds a sphere, the LDS scene image's sphere planes included
+    // (k_update_spheres), then the same refit, then the image's box planes from the refitted nodes (k_image_nodes).
+    // mat, flags and a moving sphere's d, t0, dt stay.  Buffers, streams, ms and the host copy as update_triangles.
+    void update_spheres(const double* s, size_t first, size_t n, bool device, void* stream, double* ms);
+    // rt_scene_lds_image_get: kLdsImageBytes + sizeof(TileReps), or 0 when the scene has no LDS image; out (may be null:
+    // the size only) receives the device's bytes, or with `rebuilt` what build_lds_image makes of current_flat().
+    size_t lds_image_get(bool rebuilt, uint8_t* out);
     uint64_t generation() const;
-    // flat() with the triangle vertices and the 24 box floats of every node as the device holds them now (fetched when an
+    // flat() with the sphere centres and radii, the triangle vertices and the 24 box floats of every node as the device holds them now (fetched when an
     // update happened since the last fetch; waits for the device).  Node order and child codes are the compiled ones.
     const FlatScene& current_flat();
     // rt_scene_bvh_get: the device's nodes (n_nodes x 128 bytes, as uploaded) and primitive references; either may be

@@ -869,6 +869,7 @@ static void prepare_refit(const FlatScene& f, DeviceScene& ds) {
         }
     }
     ds.slot_box = const_cast<double*>(ds.upload(box));
+    ds.slot_pad_dev = ds.upload(ds.slot_pad);
 }
 
 void Renderer::update_triangles(const double* p, size_t first, size_t n, bool device, void* stream, double* ms) {
@@ -901,6 +902,57 @@ void Renderer::update_triangles(const double* p, size_t first, size_t n, bool de
     if (ms) *ms = done.ms;
 }
 
+void Renderer::update_spheres(const double* s, size_t first, size_t n, bool device, void* stream, double* ms) {
+    upload();
+    Impl& I = *impl_;
+    DeviceScene& ds = I.s64;
+    if (n == 0) return;
+    if (first + n > I.flat.spheres.size()) throw std::runtime_error("update_spheres: range beyond the scene's spheres");
+    prepare_refit(I.flat, ds);
+    Call call(I.own_stream, I.ev, device, stream, ms != nullptr);
+    hipStream_t st = call.st;
+    SphereJob job{};
+    call.carve(I.ws, [&](Carver& c) { job.s = call.in(c, s, 4 * n); }, 1);  // host values: through the workspace
+    job.first = static_cast<uint32_t>(first), job.n = static_cast<uint32_t>(n);
+    job.primrefs = ds.view.primrefs, job.slot_pad = ds.slot_pad_dev, job.objs = ds.view.objs;
+    job.n_slots = ds.slot_box ? ds.view.n_primrefs : 0u, job.n_objs = ds.view.n_objs;
+    // the arrays build_device_scene uploaded: const in the kernels' view only, the DeviceScene owns them
+    job.spheres = const_cast<SphereRec*>(ds.view.spheres);
+    job.leaf_prims = const_cast<PrimRec80*>(ds.view.leaf_prims);
+    job.obj_prims = const_cast<PrimRec80*>(ds.view.obj_prims);
+    job.slot_box = ds.slot_box;
+    job.image = ds.lds_scene ? const_cast<uint8_t*>(ds.view.lds_image) : nullptr;
+    call.begin();
+    launch_update_spheres(st, job);
+    if (ds.slot_box) launch_refit_levels(st, const_cast<BvhNode*>(ds.view.nodes), ds.view.n_nodes, ds.slot_box, ds.view.n_primrefs, ds.level_begin);
+    launch_image_nodes(st, job.image, ds.view.nodes, ds.view.n_nodes);
+    call.end();
+    ++I.gen;
+    const Call::Done done = call.finish();  // (a device call on the caller's stream without ms returns enqueued)
+    if (ms) *ms = done.ms;
+}
+
+size_t Renderer::lds_image_get(bool rebuilt, uint8_t* out) {
+    upload();
+    Impl& I = *impl_;
+    const DeviceScene& ds = I.s64;
+    if (!ds.lds_scene) return 0;
+    const size_t bytes = kLdsImageBytes + sizeof(TileReps);
+    if (!out) return bytes;
+    if (rebuilt) {
+        uint32_t nmov = 0, tile_reps = 0;
+        bool shade_ok = false;
+        const std::vector<uint8_t> img = build_lds_image(current_flat(), nmov, shade_ok, tile_reps);
+        if (img.size() != bytes) throw std::runtime_error("lds_image_get: the scene as the device holds it no longer qualifies for an image");
+        std::memcpy(out, img.data(), bytes);
+        return bytes;
+    }
+    HIP_OK(hipSetDevice(I.device));
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(out, ds.view.lds_image, bytes, hipMemcpyDeviceToHost));
+    return bytes;
+}
+
 uint64_t Renderer::generation() const { return impl_->gen; }
 
 const FlatScene& Renderer::current_flat() {
@@ -912,6 +964,12 @@ const FlatScene& Renderer::current_flat() {
     std::vector<TriRec> tris(I.flat.tris.size());
     if (!tris.empty()) HIP_OK(hipMemcpy(tris.data(), ds.view.tris, sizeof(TriRec) * tris.size(), hipMemcpyDeviceToHost));
     for (size_t t = 0; t < tris.size(); ++t) std::memcpy(I.flat.tris[t].p, tris[t].p, sizeof tris[t].p);
+    std::vector<SphereRec> spheres(I.flat.spheres.size());
+    if (!spheres.empty()) HIP_OK(hipMemcpy(spheres.data(), ds.view.spheres, sizeof(SphereRec) * spheres.size(), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < spheres.size(); ++k) {
+        std::memcpy(I.flat.spheres[k].c, spheres[k].c, sizeof spheres[k].c);
+        I.flat.spheres[k].r = spheres[k].r;
+    }
     std::vector<BvhNode> nodes(I.flat.nodes.size());
     if (!nodes.empty()) HIP_OK(hipMemcpy(nodes.data(), ds.view.nodes, sizeof(BvhNode) * nodes.size(), hipMemcpyDeviceToHost));
     // the 24 box floats only: the device's leaf codes address the pair-aligned slots, the host's the compiled ones

@@ -63,6 +63,59 @@ def update_triangles(world, p, first=0, stream=None, timing=False):
     return ms.value if timing else None
 
 
+def scene_spheres(world):
+    """rt_scene_spheres_get: the scene's spheres as it holds them now, (n, 4) float64 -- cx, cy, cz, r; center0 for a
+    moving_sphere -- in compiled order: the order the spheres are met walking the world list.  Needs no device unless the
+    scene has been updated."""
+    handle = _native_scene(world)
+    n = check(lib.rt_scene_spheres_get(handle, None, 0), "scene_spheres")
+    out = np.empty((n, 4), np.float64)
+    if n:
+        check(lib.rt_scene_spheres_get(handle, ctypes.c_void_p(out.ctypes.data), n), "scene_spheres")
+    return out
+
+
+def update_spheres(world, s, first=0, stream=None, timing=False):
+    """rt_scene_update_spheres: s holds new (cx, cy, cz, r) for spheres [first, first + n), shape (n, 4) float64 in
+    scene_spheres' order; every BVH box, and the LDS scene image of a scene that runs out of one, is then refitted on the
+    device.  Materials stay, and so does a moving sphere's motion: it translates with it.
+
+        S = art.scene_spheres(world)
+        S[1:, 1] += 0.1 * np.sin(t + S[1:, 0])            # bounce
+        art.update_spheres(world, S)
+
+    s, stream and timing are update_triangles': a numpy array copies and blocks (a non-finite value or a radius <= 0 is
+    refused), a contiguous float64 torch tensor on the scene's device is read in place on `stream` and is not inspected."""
+    handle = _native_scene(world)
+    if not hasattr(s, "shape"):
+        raise TypeError("s must be a numpy array or a torch tensor")
+    shape = tuple(int(x) for x in s.shape)
+    if not (len(shape) == 2 and shape[1] == 4):
+        raise ValueError("s must have shape (n, 4): cx, cy, cz, r per sphere")
+    ptr, dev = address(s, "s", ("float64",), shape=shape, device_index=handle.device)
+    u = rt_update_params()
+    u.flags = RT_OUT_DEVICE if dev else 0
+    u.stream = stream_handle(stream, s.device if dev else None)
+    ms = ctypes.c_double()
+    check(lib.rt_scene_update_spheres(handle, ctypes.byref(u), ctypes.c_void_p(ptr), int(first), shape[0], ctypes.byref(ms) if timing else None),
+          "update_spheres")
+    return ms.value if timing else None
+
+
+def scene_lds_image(world, rebuilt=False):
+    """rt_scene_lds_image_get (diagnostic): the scene's LDS scene image (csrc/layout.h) followed by its tile representatives
+    as uint8, or None when the scene has no image.  rebuilt=False: the device's bytes as they are now; rebuilt=True: what
+    the host builder makes now of the scene as the device holds it -- the same bytes after any update.  Uploads the scene
+    if needed; blocks."""
+    handle = _native_scene(world)
+    n = check(lib.rt_scene_lds_image_get(handle, int(bool(rebuilt)), None, 0), "scene_lds_image")
+    if n == 0:
+        return None
+    out = np.zeros((n,), np.uint8)
+    check(lib.rt_scene_lds_image_get(handle, int(bool(rebuilt)), ctypes.c_void_p(out.ctypes.data), n), "scene_lds_image")
+    return out
+
+
 def scene_bvh(world):
     """rt_scene_bvh_get (diagnostic): the device's BVH as it is now -- (nodes, primrefs): a structured array of the 128-byte
     four-child nodes (BVH_NODE: lox, hix, loy, hiy, loz, hiz as float32[4] planes of the child boxes; child: int32[4],

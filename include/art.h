@@ -37,6 +37,8 @@
  *                                            mesh.h, bvh.cpp
  *   (none: a scene is rebuilt every run)                          rt_scene_update_triangles (new vertices for a compiled
  *                                                                    scene's triangles, BVH boxes refitted on the device)
+ *                                                                  rt_scene_update_spheres (new centres and radii; the BVH
+ *                                                                    boxes and the LDS scene image refitted on the device)
  *   (none: engine_mode::adaptive interpolates     engine.h:96-333  rt_render_guides + rt_denoise, or rt_render_denoised
  *    untraced pixels; there is no denoiser)                          (first-hit guides, variance-guided a-trous filter)
  *   (none: tracer_constants::samples_per_pixel is   tracer_constants.h:12  rt_render_noise_target (per-pixel sample counts:
@@ -74,7 +76,8 @@ extern "C" {
  * radiance along caller-given rays), rt_camera_rays (the renderer's camera rays and post-camera RNG states as data);
  * rt_render_views (many cameras of one scene in one persistent launch), option views.max_paths; rt_tile_candidates (the
  * per-tile sphere lists of a render, as counts), option render.tile_lists; rt_scene_update_triangles, rt_update_params,
- * rt_scene_triangles_get, rt_scene_bvh_get (new vertices for a compiled scene's triangles and a BVH refit on the device). */
+ * rt_scene_triangles_get, rt_scene_bvh_get (new vertices for a compiled scene's triangles and a BVH refit on the device);
+ * rt_scene_update_spheres, rt_scene_spheres_get, rt_scene_lds_image_get (new centres and radii for its spheres). */
 #define RT_ABI_VERSION 5
 
 /* return codes */
@@ -227,7 +230,8 @@ typedef struct rt_update_params {   /* zero-initialised = host buffer, scene's s
 /* rt_scene_update_triangles: new vertices for triangles [first, first + n) (9 doubles each, as rt_scene_triangles_get
  * orders them), then a refit of every BVH box on the device -- a cloth step, a morph target, a mesh whose vertices come
  * out of an optimiser -- where the only other way to move a vertex is a new graph, a full SAH build and a new upload.
- * Materials, texture coordinates and topology stay; spheres, rects and boxes cannot be updated; rt_multi is not covered.
+ * Materials, texture coordinates and topology stay; spheres move by rt_scene_update_spheres (below), rects and boxes
+ * cannot be updated; rt_multi is not covered.
  * Equality with a fresh compile: let scene A be compiled from triangles P0 and updated to P1, and scene B be compiled
  *   from the same graph with P1.  Every later call on A gives the bits it gives on B: rt_render, rt_render_views,
  *   rt_query_rays (all 12 doubles, prim included: the compiled triangle order is the same), rt_radiance_rays, and the
@@ -258,6 +262,35 @@ int rt_scene_update_triangles(rt_scene* scene, const rt_update_params* u, const 
  * than its count (node_cap / ref_cap entries) is RT_E_INVALID.  Uploads the scene if needed.  Host buffers, blocking. */
 int rt_scene_bvh_get(rt_scene* scene, void* nodes_out, int64_t node_cap, uint32_t* primrefs_out, int64_t ref_cap, int64_t* n_nodes,
                      int64_t* n_primrefs);
+/* The scene's spheres as it holds them now: 4 doubles each (cx, cy, cz, r; for a moving_sphere c is center0), in
+ * compiled order -- the order the spheres are met walking the world list, rt_scene_info.spheres of them.  Returns the
+ * count; s_out may be NULL (the count only), else it holds cap >= count spheres (RT_E_INVALID otherwise).  Host buffer.
+ * Needs no device unless the scene has been updated. */
+int64_t rt_scene_spheres_get(rt_scene* scene, double* s_out, int64_t cap);
+/* rt_scene_update_spheres: new centres and radii for spheres [first, first + n) (4 doubles each, as
+ * rt_scene_spheres_get orders them), then the refit of every BVH box and, for a scene that runs out of the LDS scene
+ * image (the spheres-only scenes: the benchmark scene among them), of the image -- bouncing spheres, a particle or
+ * physics step, a light or probe sphere an optimiser moves -- without a new graph, SAH build and upload.
+ * What stays: materials and flags, and a moving sphere's motion (center1 - center0, time0, time1): it translates with
+ *   its motion, which is also what keeps an image scene on its kernel.  Topology stays; rects and boxes cannot be
+ *   updated; rt_multi is not covered.
+ * Everything else is rt_scene_update_triangles' contract with "sphere" for "triangle": scene A compiled with spheres S0
+ *   and updated to S1 gives, in every later call, the bits scene B compiled from the same graph with S1 gives --
+ *   rt_render in every variant, rt_render_views, rt_query_rays (all 12 doubles), rt_radiance_rays, rt_render_guides,
+ *   rt_render_noise_target, rt_tile_candidates and the segment counts, up to exact-t ties; A's rt_stats.kernel_* and
+ *   extend_variant do not change, whatever B would hoist or run.  rt_update_params, streams and waiting, ordering, the
+ *   upload at the first call, ms, and the host copies (rt_scene_spheres_get, rt_scene_bvh_get and rt_scene_save fetch
+ *   from the device first; rt_scene_dump refuses an updated scene) are as there.
+ * RT_E_INVALID, before any device work: the rows of rt_scene_update_triangles, and in a host buffer a non-finite value
+ *   or a radius <= 0.  A device buffer is not inspected: a radius <= 0 there gives the boxes sphere_box makes of it, as
+ *   at compile.  n = 0 is RT_OK and touches nothing; a scene without spheres accepts only n = 0. */
+int rt_scene_update_spheres(rt_scene* scene, const rt_update_params* u, const double* s, int64_t first, int64_t n, double* ms);
+/* Diagnostic, as rt_scene_bvh_get is: the scene's LDS scene image (csrc/layout.h) with the tile representatives behind
+ * it.  Returns its size in bytes, or 0 when the scene has none; out may be NULL (the size only), else it holds cap >=
+ * size bytes (RT_E_INVALID otherwise).  rebuilt = 0: the device's bytes as they are now; rebuilt = 1: what the host
+ * builder makes now from the scene as the device holds it (the fetched sphere records and node boxes) -- equal byte for
+ * byte after any update.  Uploads the scene if needed.  Host buffer, blocking. */
+int64_t rt_scene_lds_image_get(rt_scene* scene, int32_t rebuilt, uint8_t* out, int64_t cap);
 
 /* ---- render (engine::run; the engine_mode is in rt_params.flags: RT_ADAPTIVE, RT_PARALLEL_IMAGES, or neither for
  * single and parallel_stripes, which compute the same image) ----

@@ -247,6 +247,25 @@ inline void update_triangles(const scene& world, const double* p, std::int64_t f
     u.stream = stream;
     check(rt_scene_update_triangles(world.objects.get(), &u, p, first, n, ms), "update_triangles");
 }
+// The same for spheres (rt_scene_update_spheres): 4 doubles each (cx, cy, cz, r; center0 of a moving_sphere, whose motion
+// stays) in compiled order; the BVH boxes and, where the world runs out of it, the LDS scene image are refitted.
+inline std::vector<double> scene_spheres(const scene& world) {
+    const std::int64_t n = rt_scene_spheres_get(world.objects.get(), nullptr, 0);
+    check(n < 0 ? static_cast<int>(n) : RT_OK, "scene_spheres");
+    std::vector<double> s(static_cast<std::size_t>(4 * n));
+    if (n > 0) {
+        const std::int64_t got = rt_scene_spheres_get(world.objects.get(), s.data(), n);
+        check(got < 0 ? static_cast<int>(got) : RT_OK, "scene_spheres");
+    }
+    return s;
+}
+inline void update_spheres(const scene& world, const double* s, std::int64_t first, std::int64_t n, std::int32_t flags = 0, void* stream = nullptr,
+                           double* ms = nullptr) {
+    rt_update_params u{};
+    u.flags = flags;
+    u.stream = stream;
+    check(rt_scene_update_spheres(world.objects.get(), &u, s, first, n, ms), "update_spheres");
+}
 
 // The engine with a runtime image size (the reference fixes W, H, C at compile time: engine<W,H,C> below); samples
 // per pixel and max depth are the reference's tracer_constants (tracer_constants.h:12-13) as arguments with the same
