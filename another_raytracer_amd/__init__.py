@@ -21,7 +21,8 @@ caller-given rays (other camera models, probes, lightmaps): radiance_rays(world,
 camera rays as data: camera_rays(cam, W, H, spp) -- see rays.py.  Many cameras of one scene in one persistent launch, every
 frame equal to engine.run's: render_views(world, cams, W, H, spp) -- see views.py.  New vertices for a compiled scene's
 triangles with a BVH refit on the device (animated or optimised meshes): update_triangles(world, p); new centres and radii
-for its spheres: update_spheres(world, s) -- see deform.py.
+for its spheres: update_spheres(world, s) -- see deform.py.  New values for its materials and textures (colours, fuzz,
+ir, noise scale): update_materials(world, m), update_textures(world, t) -- see appearance.py.
 All compute runs in libart.so (HIP, gfx950) behind include/art.h.
 """
 from ._lib import RTError, get_option, lib, set_option  # noqa: F401  (fails loudly when libart.so is missing)
@@ -34,11 +35,12 @@ from .scene import (  # noqa: F401
 from .rays import HitRecords, camera_rays, query_rays, radiance_rays  # noqa: F401
 from .views import render_views  # noqa: F401
 from .deform import scene_bvh, scene_lds_image, scene_spheres, scene_triangles, update_spheres, update_triangles  # noqa: F401
+from .appearance import scene_materials, scene_textures, update_materials, update_textures  # noqa: F401
 from . import imageio  # noqa: F401
 
 __all__ = [
     "RTError", "set_option", "get_option", "camera", "denoise", "engine", "engine_mode", "tracer_constants", "scene", "scene_alias", "scene_manager",
-    "query_rays", "radiance_rays", "camera_rays", "render_views", "scene_triangles", "update_triangles", "scene_bvh", "scene_spheres", "update_spheres", "scene_lds_image", "HitRecords", "compile_world", "hittable_list", "bvh_node", "sphere", "moving_sphere", "triangle", "xy_rect", "xz_rect", "yz_rect", "box",
+    "query_rays", "radiance_rays", "camera_rays", "render_views", "scene_triangles", "update_triangles", "scene_bvh", "scene_spheres", "update_spheres", "scene_lds_image", "scene_materials", "scene_textures", "update_materials", "update_textures", "HitRecords", "compile_world", "hittable_list", "bvh_node", "sphere", "moving_sphere", "triangle", "xy_rect", "xz_rect", "yz_rect", "box",
     "translate", "rotate_y", "constant_medium", "lambertian", "metal", "dielectric", "diffuse_light", "solid_color",
     "checker_texture", "noise_texture", "image_texture", "barycentric_image_texture", "mesh", "random_double", "reset_scene_rng", "imageio", "save_scene",
 ]

@@ -128,6 +128,10 @@ SIGNATURES = {
     "rt_scene_spheres_get": (ctypes.c_int64, [_P, _P, ctypes.c_int64]),
     "rt_scene_update_spheres": (_I, [_P, ctypes.POINTER(rt_update_params), _P, ctypes.c_int64, ctypes.c_int64, _DP]),
     "rt_scene_lds_image_get": (ctypes.c_int64, [_P, ctypes.c_int32, _P, ctypes.c_int64]),
+    "rt_scene_materials_get": (ctypes.c_int64, [_P, _P, _P, ctypes.c_int64]),
+    "rt_scene_textures_get": (ctypes.c_int64, [_P, _P, _P, ctypes.c_int64]),
+    "rt_scene_update_materials": (_I, [_P, ctypes.POINTER(rt_update_params), _P, ctypes.c_int64, ctypes.c_int64, _DP]),
+    "rt_scene_update_textures": (_I, [_P, ctypes.POINTER(rt_update_params), _P, ctypes.c_int64, ctypes.c_int64, _DP]),
     "rt_render": (_I, [_P, ctypes.POINTER(rt_camera), ctypes.POINTER(rt_params), _P, _P, ctypes.POINTER(rt_stats)]),
     "rt_render_progressive": (_I, [_P, ctypes.POINTER(rt_camera), ctypes.POINTER(rt_params), _P, _P, rt_progress_fn, _P,
                                    ctypes.POINTER(rt_stats)]),

@@ -33,9 +33,10 @@ struct rt_scene {
     int device = 0;
     std::unique_ptr<art::Renderer> renderer;  // created on first render (scene build/dump works without a GPU)
     art::Renderer& device_renderer() { return renderer ? *renderer : *(renderer = std::make_unique<art::Renderer>(flat, device)); }
-    // rt_scene_update_triangles and rt_scene_update_spheres leave `flat` stale: the renderer counts the updates, and whoever
-    // reads the vertices, the spheres or the boxes of `flat` (rt_scene_triangles_get, rt_scene_spheres_get, rt_scene_save)
-    // takes them from the device first
+    // rt_scene_update_triangles, _spheres, _materials and _textures leave `flat` stale: the renderer counts the updates,
+    // and whoever reads the vertices, the spheres, the boxes, the materials or the textures of `flat`
+    // (rt_scene_triangles_get, rt_scene_spheres_get, rt_scene_materials_get, rt_scene_textures_get, rt_scene_save) takes
+    // them from the device first
     uint64_t synced = 0;
     bool updated() const { return renderer && renderer->generation() > 0; }
     void sync_flat() {
@@ -44,6 +45,8 @@ struct rt_scene {
         flat.spheres = now.spheres;
         flat.tris = now.tris;
         flat.nodes = now.nodes;
+        flat.mats = now.mats;
+        flat.texs = now.texs;
         synced = renderer->generation();
     }
 };
@@ -222,7 +225,7 @@ size_t rt_scene_dump(const rt_scene* s, char* buf, size_t cap) {
         return 0;
     }
     if (s->updated()) {
-        fail(RT_E_SCENE, "the scene's triangles or spheres were updated (rt_scene_update_triangles, rt_scene_update_spheres): its object graph no longer describes it");
+        fail(RT_E_SCENE, "the scene's triangles, spheres, materials or textures were updated (rt_scene_update_triangles, _spheres, _materials, _textures): its object graph no longer describes it");
         return 0;
     }
     try {
@@ -339,6 +342,102 @@ int64_t rt_scene_lds_image_get(rt_scene* s, int32_t rebuilt, uint8_t* out, int64
         return static_cast<int>(RT_OK);
     });
     return rc != RT_OK ? rc : bytes;
+}
+
+static_assert(RT_MAT_LAMBERTIAN == art::MAT_LAMBERTIAN && RT_MAT_METAL == art::MAT_METAL && RT_MAT_DIELECTRIC == art::MAT_DIELECTRIC &&
+                  RT_MAT_DIFFUSE_LIGHT == art::MAT_LIGHT && RT_MAT_ISOTROPIC == art::MAT_ISOTROPIC,
+              "art.h's RT_MAT_* are layout.h's MatType");
+static_assert(RT_TEX_SOLID == art::TEX_SOLID && RT_TEX_CHECKER == art::TEX_CHECKER && RT_TEX_NOISE == art::TEX_NOISE && RT_TEX_IMAGE == art::TEX_IMAGE &&
+                  RT_TEX_BARY_IMAGE == art::TEX_BARY_IMAGE,
+              "art.h's RT_TEX_* are layout.h's TexType");
+
+// The getters' common part: the count without out pointers, the capacity check, then the host copy as the device holds it
+static int64_t appearance_get(rt_scene* s, const char* fn, const char* what, int64_t count, bool any_out, int64_t cap) {
+    if (!any_out) return count;
+    if (cap < count)
+        return fail(RT_E_INVALID, std::string(fn) + ": the out buffers hold " + std::to_string(cap) + " " + what + ", the scene has " + std::to_string(count));
+    const int rc = guard(RT_E_DEVICE, [&] {
+        s->sync_flat();
+        return RT_OK;
+    });
+    return rc != RT_OK ? rc : count;
+}
+
+int64_t rt_scene_materials_get(rt_scene* s, double* params_out, int32_t* desc_out, int64_t cap) {
+    if (!s) return fail(RT_E_INVALID, "rt_scene_materials_get: scene is NULL");
+    const int64_t count = static_cast<int64_t>(s->flat.mats.size());
+    const int64_t rc = appearance_get(s, "rt_scene_materials_get", "materials", count, params_out || desc_out, cap);
+    if (rc < 0 || (!params_out && !desc_out)) return rc;
+    for (int64_t k = 0; k < count; ++k) {
+        const art::MatRec& m = s->flat.mats[static_cast<size_t>(k)];
+        if (params_out) {
+            double* p = params_out + RT_MATERIAL_DOUBLES * k;
+            p[0] = m.albedo[0], p[1] = m.albedo[1], p[2] = m.albedo[2], p[3] = m.fuzz, p[4] = m.ir;
+        }
+        if (desc_out) {
+            const bool textured = m.type == art::MAT_LAMBERTIAN || m.type == art::MAT_LIGHT || m.type == art::MAT_ISOTROPIC;
+            desc_out[2 * k] = static_cast<int32_t>(m.type), desc_out[2 * k + 1] = textured ? m.tex : -1;
+        }
+    }
+    return count;
+}
+
+int64_t rt_scene_textures_get(rt_scene* s, double* params_out, int32_t* desc_out, int64_t cap) {
+    if (!s) return fail(RT_E_INVALID, "rt_scene_textures_get: scene is NULL");
+    const int64_t count = static_cast<int64_t>(s->flat.texs.size());
+    const int64_t rc = appearance_get(s, "rt_scene_textures_get", "textures", count, params_out || desc_out, cap);
+    if (rc < 0 || (!params_out && !desc_out)) return rc;
+    for (int64_t k = 0; k < count; ++k) {
+        const art::TexRec& t = s->flat.texs[static_cast<size_t>(k)];
+        if (params_out) {
+            double* p = params_out + RT_TEXTURE_DOUBLES * k;
+            p[0] = t.c[0], p[1] = t.c[1], p[2] = t.c[2], p[3] = t.scale;
+        }
+        if (desc_out) {
+            const bool checker = t.type == art::TEX_CHECKER;
+            desc_out[3 * k] = static_cast<int32_t>(t.type), desc_out[3 * k + 1] = checker ? t.even : -1, desc_out[3 * k + 2] = checker ? t.odd : -1;
+        }
+    }
+    return count;
+}
+
+// The refusals rt_scene_update_materials and rt_scene_update_textures share (all before any device work); RT_OK: go on
+static int appearance_update_check(const char* fn, const char* what, rt_scene* s, const rt_update_params* u, const double* v, int width, int64_t count,
+                                   int64_t first, int64_t n) {
+    const std::string f(fn);
+    if (!s || !u) return fail(RT_E_INVALID, f + ": scene and params must be non-NULL");
+    if (first < 0 || n < 0 || first > count || n > count - first)
+        return fail(RT_E_INVALID, f + ": [first, first + n) must lie within the scene's " + std::to_string(count) + " " + what + "s");
+    if (u->flags & ~RT_OUT_DEVICE) return fail(RT_E_INVALID, f + " takes RT_OUT_DEVICE only");
+    if (u->stream && !(u->flags & RT_OUT_DEVICE)) return fail(RT_E_INVALID, f + ": stream needs RT_OUT_DEVICE (host buffers run on the scene's own stream)");
+    if (n > 0 && !v) return fail(RT_E_INVALID, f + ": the value buffer is NULL");
+    if (!(u->flags & RT_OUT_DEVICE))
+        for (int64_t i = 0; i < width * n; ++i)
+            if (!std::isfinite(v[i]))
+                return fail(RT_E_INVALID, f + ": value " + std::to_string(i % width) + " of " + what + " " + std::to_string(first + i / width) + " is not finite");
+    return RT_OK;
+}
+
+int rt_scene_update_materials(rt_scene* s, const rt_update_params* u, const double* m, int64_t first, int64_t n, double* ms) {
+    const int rc = appearance_update_check("rt_scene_update_materials", "material", s, u, m, RT_MATERIAL_DOUBLES, s ? static_cast<int64_t>(s->flat.mats.size()) : 0, first, n);
+    if (rc != RT_OK) return rc;
+    if (ms) *ms = 0;
+    if (n == 0) return RT_OK;
+    return guard(RT_E_DEVICE, [&] {
+        s->device_renderer().update_materials(m, static_cast<size_t>(first), static_cast<size_t>(n), (u->flags & RT_OUT_DEVICE) != 0, u->stream, ms);
+        return RT_OK;
+    });
+}
+
+int rt_scene_update_textures(rt_scene* s, const rt_update_params* u, const double* t, int64_t first, int64_t n, double* ms) {
+    const int rc = appearance_update_check("rt_scene_update_textures", "texture", s, u, t, RT_TEXTURE_DOUBLES, s ? static_cast<int64_t>(s->flat.texs.size()) : 0, first, n);
+    if (rc != RT_OK) return rc;
+    if (ms) *ms = 0;
+    if (n == 0) return RT_OK;
+    return guard(RT_E_DEVICE, [&] {
+        s->device_renderer().update_textures(t, static_cast<size_t>(first), static_cast<size_t>(n), (u->flags & RT_OUT_DEVICE) != 0, u->stream, ms);
+        return RT_OK;
+    });
 }
 
 int rt_scene_bvh_get(rt_scene* s, void* nodes_out, int64_t node_cap, uint32_t* primrefs_out, int64_t ref_cap, int64_t* n_nodes, int64_t* n_primrefs) {

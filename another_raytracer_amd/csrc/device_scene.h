@@ -32,6 +32,9 @@ struct DeviceScene {
     double* slot_box = nullptr;
     const uint8_t* slot_pad_dev = nullptr;  // slot_pad on the device (k_update_spheres skips pad slots)
     std::vector<uint32_t> level_begin;
+    // rt_scene_update_materials / _textures: what the first of them makes of a scene with an image -- each material's
+    // shading-table entry code (lds_image.h image_material_entries) on the device
+    const int32_t* mat_entry_dev = nullptr;
 
     template <class T>
     const T* upload(const std::vector<T>& v) {

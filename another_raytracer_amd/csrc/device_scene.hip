@@ -63,16 +63,12 @@ std::vector<uint8_t> build_lds_image(const FlatScene& f, uint32_t& nmov, bool& s
         put(kLdsOffNodes + (kLdsNodePlaneChild * kLdsNodeCap + nn) * 16, c16, 16);
     }
     // shading table: one entry per material (two for a checker of solid colours); anything else keeps the scene off
-    // the fused variant (shade_ok = false), which shades from the global scene records instead
+    // the fused variant (shade_ok = false), which shades from the global scene records instead.  Which entry a material
+    // gets and what the entry holds are lds_image.h's text, which rt_scene_update_materials / _textures run too.
     std::vector<int32_t> entry(f.mats.size(), -1);
-    uint32_t nent = 0;
-    shade_ok = true;
-    auto put_entry = [&](const double c[3], double param) {
-        const double v[4] = {c[0], c[1], c[2], param};
-        if (nent < kLdsMatCap) put(kLdsOffMat + nent * 32, v, 32);
-        return nent++;
-    };
-    auto solid = [&](int32_t t) { return t >= 0 && static_cast<size_t>(t) < f.texs.size() && f.texs[t].type == TEX_SOLID; };
+    image_material_entries(f.primrefs.data(), f.primrefs.size(), f.spheres.data(), f.mats.data(), f.mats.size(), f.texs.data(), f.texs.size(),
+                           entry.data(), shade_ok);
+    for (size_t k = 0; k < f.mats.size(); ++k) image_put_material(img.data(), entry[k], f.mats[k], f.texs.data());
     uint32_t m = 0;
     for (size_t slot = 0; slot < f.primrefs.size(); ++slot) {
         const uint32_t idx = primref_index(f.primrefs[slot]);
@@ -88,37 +84,9 @@ std::vector<uint8_t> build_lds_image(const FlatScene& f, uint32_t& nmov, bool& s
             ++m;
         }
         put(kLdsOffRef + sl * 4, &code, 4);
-        const auto& mat = f.mats[sp.mat];
-        if (entry[sp.mat] < 0) {
-            if (mat.type == MAT_LAMBERTIAN || mat.type == MAT_LIGHT) {
-                const auto& t = f.texs[mat.tex];
-                if (t.type == TEX_SOLID) {
-                    entry[sp.mat] = static_cast<int32_t>(put_entry(t.c, 0.0));
-                } else if (t.type == TEX_CHECKER && solid(t.even) && solid(t.odd)) {
-                    entry[sp.mat] = static_cast<int32_t>(put_entry(f.texs[t.even].c, 0.0)) | static_cast<int32_t>(kLdsMatChecker);
-                    put_entry(f.texs[t.odd].c, 0.0);
-                } else {
-                    shade_ok = false;
-                }
-            } else if (mat.type == MAT_METAL) {
-                entry[sp.mat] = static_cast<int32_t>(put_entry(mat.albedo, mat.fuzz));
-            } else if (mat.type == MAT_DIELECTRIC) {
-                // dielectric (material.h:63-99): 1 / ir, and reflectance()'s r0 = ((1 - ratio) / (1 + ratio))^2 for
-                // both faces, in the device's IEEE double arithmetic (-ffp-contract=off), then ir
-                const double inv = 1.0 / mat.ir;
-                double r0f = (1.0 - inv) / (1.0 + inv), r0b = (1.0 - mat.ir) / (1.0 + mat.ir);
-                r0f = r0f * r0f;
-                r0b = r0b * r0b;
-                const double d3[3] = {inv, r0f, r0b};
-                entry[sp.mat] = static_cast<int32_t>(put_entry(d3, mat.ir));
-            } else {
-                shade_ok = false;
-            }
-        }
         const uint16_t mi = static_cast<uint16_t>(entry[sp.mat] < 0 ? 0 : entry[sp.mat]);
         put(kLdsOffMatIdx + sl * 2, &mi, 2);
     }
-    if (nent > kLdsMatCap) shade_ok = false;
     // Behind the image: one representative slot per sphere (tile_lists.h TileReps; spatial splits put a sphere into
     // several leaves), the lowest slot whose index field names it.  k_paths' tile lists test representatives only and
     // shade by them, so every slot of a sphere must hold the representative's bytes in every per-slot plane; the

@@ -129,6 +129,22 @@ struct SphereJob {
 void launch_update_spheres(hipStream_t st, const SphereJob& j);
 // k_image_nodes: the nine box planes of every node of the LDS scene image from the (refitted) nodes
 void launch_image_nodes(hipStream_t st, uint8_t* image, const BvhNode* nodes, uint32_t n_nodes);
+// One rt_scene_update_materials / rt_scene_update_textures call as its kernels see it.  k_update_materials (m: 5 doubles
+// per material -- albedo, fuzz, ir) and k_update_textures (t: 4 per texture -- colour, scale) write the fields a record's
+// type takes into records [first, first + n); k_derive_materials then runs over all n_mats materials: a MATF_SOLID
+// record's albedo from its texture, and with an image the shading-table entries of every material that has one
+// (entry: lds_image.h image_material_entries' codes on the device, null without an image).
+struct AppearanceJob {
+    const double* v;
+    uint32_t first, n;
+    MatRec* mats;
+    TexRec* texs;
+    uint32_t n_mats;
+    const int32_t* entry;
+    uint8_t* image;
+};
+void launch_update_materials(hipStream_t st, const AppearanceJob& j);
+void launch_update_textures(hipStream_t st, const AppearanceJob& j);
 // k_refit_level over every level [level_begin[l], level_begin[l + 1]) (refit.h refit_levels), the deepest first
 void launch_refit_levels(hipStream_t st, BvhNode* nodes, uint32_t n_nodes, const double* slot_box, uint32_t n_slots,
                          const std::vector<uint32_t>& level_begin);

@@ -5,6 +5,9 @@
 // rt_scene_update_spheres: k_update_spheres does the same for centres and radii (the records, the leaf-ordered copy,
 // the prim objects' copies, the slot boxes and the sphere planes of the LDS scene image, lds_image.h), and after the
 // levels k_image_nodes rewrites the image's box planes from the refitted nodes.
+// rt_scene_update_materials / rt_scene_update_textures: k_update_materials / k_update_textures write the fields a record's
+// type takes, then k_derive_materials refreshes, for every material of the scene, the two copies made of them at upload:
+// the solid colour inlined into a MATF_SOLID record and the image's shading-table entries (lds_image.h).
 #include "launch.h"
 #include "lds_image.h"
 #include "refit.h"
@@ -89,6 +92,46 @@ __global__ void __launch_bounds__(kRefitBlock) k_image_nodes(uint8_t* image, con
     if (n < n_nodes) image_put_node_boxes(image, n, nodes[n]);
 }
 
+// One thread per record of [first, first + n).  A metal takes albedo and fuzz (clamped as SceneGraph::metal clamps it,
+// material.h:47), a dielectric ir; a lambertian's, a light's and an isotropic's colour is their texture's.
+__global__ void __launch_bounds__(kRefitBlock) k_update_materials(AppearanceJob j) {
+    const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (i >= j.n) return;
+    const double* v = j.v + 5 * static_cast<size_t>(i);
+    MatRec& m = j.mats[j.first + i];
+    if (m.type == MAT_METAL) {
+        m.albedo[0] = v[0], m.albedo[1] = v[1], m.albedo[2] = v[2];
+        m.fuzz = v[3] < 1.0 ? v[3] : 1.0;
+    } else if (m.type == MAT_DIELECTRIC) {
+        m.ir = v[4];
+    }
+}
+
+// A solid texture takes the colour, a noise texture the scale (its perlin table stays); the others nothing
+__global__ void __launch_bounds__(kRefitBlock) k_update_textures(AppearanceJob j) {
+    const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (i >= j.n) return;
+    const double* v = j.v + 4 * static_cast<size_t>(i);
+    TexRec& t = j.texs[j.first + i];
+    if (t.type == TEX_SOLID) {
+        t.c[0] = v[0], t.c[1] = v[1], t.c[2] = v[2];
+    } else if (t.type == TEX_NOISE) {
+        t.scale = v[3];
+    }
+}
+
+// One thread per material of the scene, whatever range was updated: a texture may be shared by materials outside it
+__global__ void __launch_bounds__(kRefitBlock) k_derive_materials(AppearanceJob j) {
+    const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (i >= j.n_mats) return;
+    MatRec& m = j.mats[i];
+    if (m.flags & MATF_SOLID) {  // (set at upload for a valid solid texture only)
+        const TexRec& t = j.texs[m.tex];
+        m.albedo[0] = t.c[0], m.albedo[1] = t.c[1], m.albedo[2] = t.c[2];
+    }
+    if (j.image) image_put_material(j.image, j.entry[i], m, j.texs);
+}
+
 // Four lanes per node of [begin, end), one per child
 __global__ void __launch_bounds__(kRefitBlock) k_refit_level(BvhNode* nodes, uint32_t n_nodes, const double* slot_box, uint32_t n_slots,
                                                              uint32_t begin, uint32_t end) {
@@ -112,6 +155,23 @@ void launch_update_spheres(hipStream_t st, const SphereJob& j) {
 void launch_image_nodes(hipStream_t st, uint8_t* image, const BvhNode* nodes, uint32_t n_nodes) {
     if (!image || n_nodes == 0) return;
     hipLaunchKernelGGL(k_image_nodes, dim3((n_nodes + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, image, nodes, n_nodes);
+}
+
+static void launch_derive_materials(hipStream_t st, const AppearanceJob& j) {
+    if (j.n_mats == 0) return;
+    hipLaunchKernelGGL(k_derive_materials, dim3((j.n_mats + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, j);
+}
+
+void launch_update_materials(hipStream_t st, const AppearanceJob& j) {
+    if (j.n == 0) return;
+    hipLaunchKernelGGL(k_update_materials, dim3((j.n + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, j);
+    launch_derive_materials(st, j);
+}
+
+void launch_update_textures(hipStream_t st, const AppearanceJob& j) {
+    if (j.n == 0) return;
+    hipLaunchKernelGGL(k_update_textures, dim3((j.n + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, j);
+    launch_derive_materials(st, j);
 }
 
 void launch_refit_levels(hipStream_t st, BvhNode* nodes, uint32_t n_nodes, const double* slot_box, uint32_t n_slots,

@@ -106,12 +106,21 @@ public:
     // (k_update_spheres), then the same refit, then the image's box planes from the refitted nodes (k_image_nodes).
     // mat, flags and a moving sphere's d, t0, dt stay.  Buffers, streams, ms and the host copy as update_triangles.
     void update_spheres(const double* s, size_t first, size_t n, bool device, void* stream, double* ms);
+    // rt_scene_update_materials / rt_scene_update_textures: new values (5 doubles per material: albedo, fuzz, ir; 4 per
+    // texture: colour, scale) for records [first, first + n) of flat().mats / flat().texs.  A record takes what its type
+    // uses (k_update_materials, k_update_textures); then every material of the scene gets its copies refreshed
+    // (k_derive_materials): the solid colour inlined into a MATF_SOLID record, and the LDS scene image's shading-table
+    // entries.  Types, links, boxes and the tree stay.  Buffers, streams, ms and the host copy as update_triangles.
+    void update_materials(const double* m, size_t first, size_t n, bool device, void* stream, double* ms);
+    void update_textures(const double* t, size_t first, size_t n, bool device, void* stream, double* ms);
     // rt_scene_lds_image_get: kLdsImageBytes + sizeof(TileReps), or 0 when the scene has no LDS image; out (may be null:
     // the size only) receives the device's bytes, or with `rebuilt` what build_lds_image makes of current_flat().
     size_t lds_image_get(bool rebuilt, uint8_t* out);
     uint64_t generation() const;
-    // flat() with the sphere centres and radii, the triangle vertices and the 24 box floats of every node as the device holds them now (fetched when an
-    // update happened since the last fetch; waits for the device).  Node order and child codes are the compiled ones.
+    // flat() with the sphere centres and radii, the triangle vertices, the 24 box floats of every node and the material and
+    // texture fields an update can write (a metal's albedo and fuzz, a dielectric's ir, a solid texture's colour, a noise
+    // texture's scale) as the device holds them now (fetched when an update happened since the last fetch; waits for the
+    // device).  Node order and child codes are the compiled ones.
     const FlatScene& current_flat();
     // rt_scene_bvh_get: the device's nodes (n_nodes x 128 bytes, as uploaded) and primitive references; either may be
     // null (both null: the counts only).  Uploads the scene if no call has yet; blocking.

@@ -18,6 +18,7 @@
 
 #include "call_plan.h"
 #include "launch.h"
+#include "lds_image.h"
 #include "options.h"
 #include "pass_plan.h"
 #include "refit.h"
@@ -37,7 +38,7 @@ struct Renderer::Impl {
     DeviceBuffer ws{true};  // the workspace, with the test.fault_workspace_bytes fault point
     hipEvent_t ev[2] = {nullptr, nullptr};
     std::vector<ViewRec> view_table;  // rt_render_views: the camera table of the last call, as uploaded
-    uint64_t gen = 0, fetched_gen = 0;  // rt_scene_update_triangles calls so far / the one `flat` was last fetched after
+    uint64_t gen = 0, fetched_gen = 0;  // rt_scene_update_* calls so far / the one `flat` was last fetched after
 
     ~Impl() {
         s64.release();
@@ -932,6 +933,56 @@ void Renderer::update_spheres(const double* s, size_t first, size_t n, bool devi
     if (ms) *ms = done.ms;
 }
 
+// What a scene's first material or texture update makes: with an image, the entry code of every material on the
+// device.  (No slot boxes: nothing moves.)
+static void prepare_appearance(const FlatScene& f, DeviceScene& ds) {
+    if (!ds.lds_scene || ds.mat_entry_dev) return;
+    std::vector<int32_t> entry(f.mats.size(), -1);
+    bool complete = false;
+    // f.primrefs: what build_lds_image walked (an image scene is never pair-aligned, so these are the device's slots)
+    image_material_entries(f.primrefs.data(), f.primrefs.size(), f.spheres.data(), f.mats.data(), f.mats.size(), f.texs.data(), f.texs.size(),
+                           entry.data(), complete);
+    ds.mat_entry_dev = ds.upload(entry);
+}
+
+// The common part of update_materials and update_textures (the scene is uploaded): `width` doubles per record of
+// [first, first + n)
+static void update_appearance(Renderer::Impl& I, const double* v, size_t width, size_t first, size_t n, bool device, void* stream, double* ms,
+                              void (*launch)(hipStream_t, const AppearanceJob&)) {
+    DeviceScene& ds = I.s64;
+    prepare_appearance(I.flat, ds);
+    Call call(I.own_stream, I.ev, device, stream, ms != nullptr);
+    AppearanceJob job{};
+    call.carve(I.ws, [&](Carver& c) { job.v = call.in(c, v, width * n); }, 1);  // host values: through the workspace
+    job.first = static_cast<uint32_t>(first), job.n = static_cast<uint32_t>(n);
+    // the arrays build_device_scene uploaded: const in the kernels' view only, the DeviceScene owns them
+    job.mats = const_cast<MatRec*>(ds.view.mats);
+    job.texs = const_cast<TexRec*>(ds.view.texs);
+    job.n_mats = ds.view.n_mats;
+    job.entry = ds.mat_entry_dev;
+    job.image = ds.lds_scene ? const_cast<uint8_t*>(ds.view.lds_image) : nullptr;
+    call.begin();
+    launch(call.st, job);
+    call.end();
+    ++I.gen;
+    const Call::Done done = call.finish();  // (a device call on the caller's stream without ms returns enqueued)
+    if (ms) *ms = done.ms;
+}
+
+void Renderer::update_materials(const double* m, size_t first, size_t n, bool device, void* stream, double* ms) {
+    upload();
+    if (n == 0) return;
+    if (first + n > impl_->flat.mats.size()) throw std::runtime_error("update_materials: range beyond the scene's materials");
+    update_appearance(*impl_, m, 5, first, n, device, stream, ms, launch_update_materials);
+}
+
+void Renderer::update_textures(const double* t, size_t first, size_t n, bool device, void* stream, double* ms) {
+    upload();
+    if (n == 0) return;
+    if (first + n > impl_->flat.texs.size()) throw std::runtime_error("update_textures: range beyond the scene's textures");
+    update_appearance(*impl_, t, 4, first, n, device, stream, ms, launch_update_textures);
+}
+
 size_t Renderer::lds_image_get(bool rebuilt, uint8_t* out) {
     upload();
     Impl& I = *impl_;
@@ -969,6 +1020,22 @@ const FlatScene& Renderer::current_flat() {
     for (size_t k = 0; k < spheres.size(); ++k) {
         std::memcpy(I.flat.spheres[k].c, spheres[k].c, sizeof spheres[k].c);
         I.flat.spheres[k].r = spheres[k].r;
+    }
+    // of a material and a texture, the fields an update writes -- not the solid colour the upload inlined into a
+    // lambertian's, a light's or an isotropic's device record (MATF_SOLID)
+    std::vector<MatRec> mats(I.flat.mats.size());
+    if (!mats.empty()) HIP_OK(hipMemcpy(mats.data(), ds.view.mats, sizeof(MatRec) * mats.size(), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < mats.size(); ++k) {
+        MatRec& m = I.flat.mats[k];
+        if (m.type == MAT_METAL) std::memcpy(m.albedo, mats[k].albedo, sizeof m.albedo), m.fuzz = mats[k].fuzz;
+        if (m.type == MAT_DIELECTRIC) m.ir = mats[k].ir;
+    }
+    std::vector<TexRec> texs(I.flat.texs.size());
+    if (!texs.empty()) HIP_OK(hipMemcpy(texs.data(), ds.view.texs, sizeof(TexRec) * texs.size(), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < texs.size(); ++k) {
+        TexRec& t = I.flat.texs[k];
+        if (t.type == TEX_SOLID) std::memcpy(t.c, texs[k].c, sizeof t.c);
+        if (t.type == TEX_NOISE) t.scale = texs[k].scale;
     }
     std::vector<BvhNode> nodes(I.flat.nodes.size());
     if (!nodes.empty()) HIP_OK(hipMemcpy(nodes.data(), ds.view.nodes, sizeof(BvhNode) * nodes.size(), hipMemcpyDeviceToHost));

@@ -39,6 +39,9 @@
  *                                                                    scene's triangles, BVH boxes refitted on the device)
  *                                                                  rt_scene_update_spheres (new centres and radii; the BVH
  *                                                                    boxes and the LDS scene image refitted on the device)
+ *                                                                  rt_scene_update_materials, rt_scene_update_textures
+ *                                                                    (new colours, fuzz, ir, noise scale; every device
+ *                                                                    copy of them refreshed, the image's shading table too)
  *   (none: engine_mode::adaptive interpolates     engine.h:96-333  rt_render_guides + rt_denoise, or rt_render_denoised
  *    untraced pixels; there is no denoiser)                          (first-hit guides, variance-guided a-trous filter)
  *   (none: tracer_constants::samples_per_pixel is   tracer_constants.h:12  rt_render_noise_target (per-pixel sample counts:
@@ -77,7 +80,9 @@ extern "C" {
  * rt_render_views (many cameras of one scene in one persistent launch), option views.max_paths; rt_tile_candidates (the
  * per-tile sphere lists of a render, as counts), option render.tile_lists; rt_scene_update_triangles, rt_update_params,
  * rt_scene_triangles_get, rt_scene_bvh_get (new vertices for a compiled scene's triangles and a BVH refit on the device);
- * rt_scene_update_spheres, rt_scene_spheres_get, rt_scene_lds_image_get (new centres and radii for its spheres). */
+ * rt_scene_update_spheres, rt_scene_spheres_get, rt_scene_lds_image_get (new centres and radii for its spheres);
+ * rt_scene_update_materials, rt_scene_update_textures, rt_scene_materials_get, rt_scene_textures_get, RT_MATERIAL_DOUBLES,
+ * RT_TEXTURE_DOUBLES, RT_MAT_*, RT_TEX_* (new values for its materials and textures). */
 #define RT_ABI_VERSION 5
 
 /* return codes */
@@ -230,8 +235,8 @@ typedef struct rt_update_params {   /* zero-initialised = host buffer, scene's s
 /* rt_scene_update_triangles: new vertices for triangles [first, first + n) (9 doubles each, as rt_scene_triangles_get
  * orders them), then a refit of every BVH box on the device -- a cloth step, a morph target, a mesh whose vertices come
  * out of an optimiser -- where the only other way to move a vertex is a new graph, a full SAH build and a new upload.
- * Materials, texture coordinates and topology stay; spheres move by rt_scene_update_spheres (below), rects and boxes
- * cannot be updated; rt_multi is not covered.
+ * Materials (rt_scene_update_materials / _textures change their values), texture coordinates and topology stay; spheres
+ * move by rt_scene_update_spheres (below), rects and boxes cannot be updated; rt_multi is not covered.
  * Equality with a fresh compile: let scene A be compiled from triangles P0 and updated to P1, and scene B be compiled
  *   from the same graph with P1.  Every later call on A gives the bits it gives on B: rt_render, rt_render_views,
  *   rt_query_rays (all 12 doubles, prim included: the compiled triangle order is the same), rt_radiance_rays, and the
@@ -291,6 +296,57 @@ int rt_scene_update_spheres(rt_scene* scene, const rt_update_params* u, const do
  * builder makes now from the scene as the device holds it (the fetched sphere records and node boxes) -- equal byte for
  * byte after any update.  Uploads the scene if needed.  Host buffer, blocking. */
 int64_t rt_scene_lds_image_get(rt_scene* scene, int32_t rebuilt, uint8_t* out, int64_t cap);
+
+/* ---- appearance: the values of a compiled scene's materials and textures ----
+ * Indices: a compiled material index is the graph's material id (what rt_mat_* returned; for a builtin scene, creation
+ * order), a compiled texture index the graph's texture id (rt_tex_*): compiling copies both lists in order and merges
+ * nothing.  The material index is the `mat` value rt_query_rays reports.  The isotropic material rt_obj_constant_medium
+ * creates is an ordinary entry, made when the medium is.  rt_scene_info.materials / .textures are the counts. */
+#define RT_MATERIAL_DOUBLES 5   /* albedo r, g, b; fuzz; ir */
+#define RT_TEXTURE_DOUBLES  4   /* colour r, g, b; scale */
+#define RT_MAT_LAMBERTIAN    0
+#define RT_MAT_METAL         1
+#define RT_MAT_DIELECTRIC    2
+#define RT_MAT_DIFFUSE_LIGHT 3
+#define RT_MAT_ISOTROPIC     4
+#define RT_TEX_SOLID      0
+#define RT_TEX_CHECKER    1
+#define RT_TEX_NOISE      2
+#define RT_TEX_IMAGE      3
+#define RT_TEX_BARY_IMAGE 4
+/* The scene's materials / textures as it holds them now.  Both return the count.  Either out pointer may be NULL; one
+ * that is given holds cap >= count rows (RT_E_INVALID otherwise).  Host buffers; no device is needed unless the scene
+ * has been updated.  params_out rows: RT_MATERIAL_DOUBLES (albedo r, g, b; fuzz; ir) or RT_TEXTURE_DOUBLES (colour r, g,
+ * b; scale) doubles; a field the record's type does not use comes back as the host record holds it.  desc_out rows: a
+ * material's {RT_MAT_* type, texture index or -1 where the material has none (metal, dielectric)}; a texture's
+ * {RT_TEX_* type, even, odd}, the two children's texture indices for a checker and -1, -1 otherwise. */
+int64_t rt_scene_materials_get(rt_scene* scene, double* params_out, int32_t* desc_out, int64_t cap);
+int64_t rt_scene_textures_get(rt_scene* scene, double* params_out, int32_t* desc_out, int64_t cap);
+/* rt_scene_update_materials / rt_scene_update_textures: new values for materials / textures [first, first + n), rows as
+ * the getters give them -- a light an optimiser drives, material parameters for inverse rendering, look-dev on the
+ * material rt_query_rays reported, a flickering emitter across rt_render_views frames -- without a new graph, SAH build
+ * and upload.  What a record takes from its row, by its type:
+ *   metal                                   albedo; fuzz, stored as fuzz < 1 ? fuzz : 1 (material.h:47)   (ir ignored)
+ *   dielectric                              ir                                                 (the rest ignored)
+ *   lambertian / diffuse_light / isotropic  nothing: their colour is their texture's
+ *   solid texture                           colour                                             (scale ignored)
+ *   noise texture                           scale; the perlin table stays                      (colour ignored)
+ *   checker / image / barycentric image     nothing
+ * Ignored fields are left untouched, so a get followed by an update of the same rows changes no bit.  Types, texture
+ *   links, checker children, images and texcoords never change.  Every device copy of a value follows: a solid colour
+ *   shared by a lambertian, a light and a checker updates all three, whichever range the call named, and so does the
+ *   LDS scene image's shading table.
+ * Everything else is rt_scene_update_spheres' contract: scene A compiled with values V0 and updated to V1 gives, in
+ *   every later call, the bits scene B compiled from the same graph call sequence with V1 gives -- rt_render in every
+ *   variant, rt_render_views, rt_radiance_rays, rt_render_guides (albedo included), rt_render_noise_target,
+ *   rt_query_rays and the segment counts; A's rt_stats.kernel_* and extend_variant do not change (no kernel choice
+ *   depends on a value).  rt_update_params, streams and waiting, ordering, the blocking upload at the first call, ms and
+ *   the host copies (the getters and rt_scene_save fetch from the device first; rt_scene_dump refuses an updated scene)
+ *   are as there.  rt_multi is not covered.
+ * RT_E_INVALID, before any device work: the rows of rt_scene_update_triangles; in a host buffer a non-finite value in
+ *   any of a row's doubles, used or ignored.  A device buffer is not inspected.  n = 0 is RT_OK and touches nothing. */
+int rt_scene_update_materials(rt_scene* scene, const rt_update_params* u, const double* m, int64_t first, int64_t n, double* ms);
+int rt_scene_update_textures(rt_scene* scene, const rt_update_params* u, const double* t, int64_t first, int64_t n, double* ms);
 
 /* ---- render (engine::run; the engine_mode is in rt_params.flags: RT_ADAPTIVE, RT_PARALLEL_IMAGES, or neither for
  * single and parallel_stripes, which compute the same image) ----

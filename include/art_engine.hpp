@@ -266,6 +266,46 @@ inline void update_spheres(const scene& world, const double* s, std::int64_t fir
     u.stream = stream;
     check(rt_scene_update_spheres(world.objects.get(), &u, s, first, n, ms), "update_spheres");
 }
+// A compiled world's materials and textures (rt_scene_materials_get / rt_scene_textures_get): RT_MATERIAL_DOUBLES /
+// RT_TEXTURE_DOUBLES doubles per row, indexed by the graph's material / texture ids; desc (optional) receives the rows
+// {type, tex} / {type, even, odd}.  update_materials / update_textures write new values for rows [first, first + n); each
+// record takes what its type uses, and every device copy of a value follows (rt_scene_update_materials).
+inline std::vector<double> scene_materials(const scene& world, std::vector<std::int32_t>* desc = nullptr) {
+    const std::int64_t n = rt_scene_materials_get(world.objects.get(), nullptr, nullptr, 0);
+    check(n < 0 ? static_cast<int>(n) : RT_OK, "scene_materials");
+    std::vector<double> m(static_cast<std::size_t>(RT_MATERIAL_DOUBLES * n));
+    if (desc) desc->assign(static_cast<std::size_t>(2 * n), 0);
+    if (n > 0) {
+        const std::int64_t got = rt_scene_materials_get(world.objects.get(), m.data(), desc ? desc->data() : nullptr, n);
+        check(got < 0 ? static_cast<int>(got) : RT_OK, "scene_materials");
+    }
+    return m;
+}
+inline std::vector<double> scene_textures(const scene& world, std::vector<std::int32_t>* desc = nullptr) {
+    const std::int64_t n = rt_scene_textures_get(world.objects.get(), nullptr, nullptr, 0);
+    check(n < 0 ? static_cast<int>(n) : RT_OK, "scene_textures");
+    std::vector<double> t(static_cast<std::size_t>(RT_TEXTURE_DOUBLES * n));
+    if (desc) desc->assign(static_cast<std::size_t>(3 * n), 0);
+    if (n > 0) {
+        const std::int64_t got = rt_scene_textures_get(world.objects.get(), t.data(), desc ? desc->data() : nullptr, n);
+        check(got < 0 ? static_cast<int>(got) : RT_OK, "scene_textures");
+    }
+    return t;
+}
+inline void update_materials(const scene& world, const double* m, std::int64_t first, std::int64_t n, std::int32_t flags = 0, void* stream = nullptr,
+                             double* ms = nullptr) {
+    rt_update_params u{};
+    u.flags = flags;
+    u.stream = stream;
+    check(rt_scene_update_materials(world.objects.get(), &u, m, first, n, ms), "update_materials");
+}
+inline void update_textures(const scene& world, const double* t, std::int64_t first, std::int64_t n, std::int32_t flags = 0, void* stream = nullptr,
+                            double* ms = nullptr) {
+    rt_update_params u{};
+    u.flags = flags;
+    u.stream = stream;
+    check(rt_scene_update_textures(world.objects.get(), &u, t, first, n, ms), "update_textures");
+}
 
 // The engine with a runtime image size (the reference fixes W, H, C at compile time: engine<W,H,C> below); samples
 // per pixel and max depth are the reference's tracer_constants (tracer_constants.h:12-13) as arguments with the same
