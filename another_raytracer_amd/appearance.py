@@ -16,24 +16,11 @@ fuzz (clamped to 1), a dielectric ir, a solid texture its colour, a noise textur
 ignored and stays, so get -> update changes nothing.  Every later call gives the bits a scene compiled fresh with the
 same values gives.
 """
-import ctypes
-
 import numpy as np
 
-from ._lib import RT_OUT_DEVICE, check, lib, rt_update_params
-from ._buffers import address, stream_handle
-from .rays import _native_scene
+from . import _update
 
 MATERIAL_DOUBLES, TEXTURE_DOUBLES = 5, 4   # art.h RT_MATERIAL_DOUBLES, RT_TEXTURE_DOUBLES
-
-
-def _get(world, fn, name, width, desc_width):
-    handle = _native_scene(world)
-    n = check(fn(handle, None, None, 0), name)
-    params, desc = np.empty((n, width), np.float64), np.empty((n, desc_width), np.int32)
-    if n:
-        check(fn(handle, ctypes.c_void_p(params.ctypes.data), ctypes.c_void_p(desc.ctypes.data), n), name)
-    return params, desc
 
 
 def scene_materials(world):
@@ -41,30 +28,14 @@ def scene_materials(world):
     now (a field the material's type does not use as the host record holds it); desc (M, 2) int32: type (0 lambertian,
     1 metal, 2 dielectric, 3 diffuse_light, 4 isotropic), texture id or -1.  Row k is the material with id k.  Needs no
     device unless the scene has been updated."""
-    return _get(world, lib.rt_scene_materials_get, "scene_materials", MATERIAL_DOUBLES, 2)
+    return _update.get(world, "scene_materials", ((MATERIAL_DOUBLES,), np.float64), ((2,), np.int32))
 
 
 def scene_textures(world):
     """rt_scene_textures_get: (params, desc) -- params (T, 4) float64: colour r, g, b; scale; desc (T, 3) int32: type
     (0 solid, 1 checker, 2 noise, 3 image, 4 barycentric image), a checker's even and odd texture ids (-1, -1 otherwise).
     Row k is the texture with id k.  Needs no device unless the scene has been updated."""
-    return _get(world, lib.rt_scene_textures_get, "scene_textures", TEXTURE_DOUBLES, 3)
-
-
-def _update(world, v, arg, width, what, fn, name, first, stream, timing):
-    handle = _native_scene(world)
-    if not hasattr(v, "shape"):
-        raise TypeError(f"{arg} must be a numpy array or a torch tensor")
-    shape = tuple(int(x) for x in v.shape)
-    if not (len(shape) == 2 and shape[1] == width):
-        raise ValueError(f"{arg} must have shape (n, {width}): {what}")
-    ptr, dev = address(v, arg, ("float64",), shape=shape, device_index=handle.device)
-    u = rt_update_params()
-    u.flags = RT_OUT_DEVICE if dev else 0
-    u.stream = stream_handle(stream, v.device if dev else None)
-    ms = ctypes.c_double()
-    check(fn(handle, ctypes.byref(u), ctypes.c_void_p(ptr), int(first), shape[0], ctypes.byref(ms) if timing else None), name)
-    return ms.value if timing else None
+    return _update.get(world, "scene_textures", ((TEXTURE_DOUBLES,), np.float64), ((3,), np.int32))
 
 
 def update_materials(world, m, first=0, stream=None, timing=False):
@@ -75,8 +46,7 @@ def update_materials(world, m, first=0, stream=None, timing=False):
     m, stream and timing are update_spheres': a numpy array copies and blocks (a non-finite value anywhere in a row is
     refused), a contiguous float64 torch tensor on the scene's device is read in place on `stream` (default: torch's current
     stream) and is not inspected; timing=True returns the device time in milliseconds."""
-    return _update(world, m, "m", MATERIAL_DOUBLES, "albedo r, g, b; fuzz; ir per material", lib.rt_scene_update_materials, "update_materials",
-                   first, stream, timing)
+    return _update.update(world, m, "m", ((MATERIAL_DOUBLES,),), "shape (n, 5): albedo r, g, b; fuzz; ir per material", "update_materials", first, stream, timing)
 
 
 def update_textures(world, t, first=0, stream=None, timing=False):
@@ -84,5 +54,4 @@ def update_textures(world, t, first=0, stream=None, timing=False):
     in scene_textures' order.  A solid_color takes the colour, a noise_texture the scale (its perlin table stays); checker,
     image and barycentric image textures take nothing.  Every material that uses the texture -- directly or through a
     checker -- shows the new value.  t, stream and timing as update_materials."""
-    return _update(world, t, "t", TEXTURE_DOUBLES, "colour r, g, b; scale per texture", lib.rt_scene_update_textures, "update_textures",
-                   first, stream, timing)
+    return _update.update(world, t, "t", ((TEXTURE_DOUBLES,),), "shape (n, 4): colour r, g, b; scale per texture", "update_textures", first, stream, timing)

@@ -33,10 +33,8 @@ struct rt_scene {
     int device = 0;
     std::unique_ptr<art::Renderer> renderer;  // created on first render (scene build/dump works without a GPU)
     art::Renderer& device_renderer() { return renderer ? *renderer : *(renderer = std::make_unique<art::Renderer>(flat, device)); }
-    // rt_scene_update_triangles, _spheres, _materials and _textures leave `flat` stale: the renderer counts the updates,
-    // and whoever reads the vertices, the spheres, the boxes, the materials or the textures of `flat`
-    // (rt_scene_triangles_get, rt_scene_spheres_get, rt_scene_materials_get, rt_scene_textures_get, rt_scene_save) takes
-    // them from the device first
+    // the rt_scene_update_* calls leave `flat` stale: the renderer counts the updates, and whoever reads from `flat` what
+    // an update writes (the getters through get_begin, rt_scene_save) takes it from the device first
     uint64_t synced = 0;
     bool updated() const { return renderer && renderer->generation() > 0; }
     void sync_flat() {
@@ -251,52 +249,75 @@ int rt_scene_save(const rt_scene* s, const char* path) {
     });
 }
 
-int64_t rt_scene_triangles_get(rt_scene* s, double* p_out, int64_t cap) {
-    if (!s) return fail(RT_E_INVALID, "rt_scene_triangles_get: scene is NULL");
-    const int64_t count = static_cast<int64_t>(s->flat.tris.size());
-    if (!p_out) return count;
-    if (cap < count) return fail(RT_E_INVALID, "rt_scene_triangles_get: p_out holds " + std::to_string(cap) + " triangles, the scene has " + std::to_string(count));
+// ---- rt_scene_update_* and rt_scene_*_get, driven by update_kinds.h's table
+static_assert(art::kUpdateRows[2].width == RT_MATERIAL_DOUBLES && art::kUpdateRows[3].width == RT_TEXTURE_DOUBLES, "art.h's row widths are update_kinds.h's");
+
+// Every refusal of an update call, all before any device work; RT_OK: go on
+static int update_check(art::UpdateKind kind, rt_scene* s, const rt_update_params* u, const double* v, int64_t first, int64_t n) {
+    const art::UpdateRow& row = art::update_row(kind);
+    const std::string f = std::string("rt_scene_update_") + row.nouns;
+    if (!s || !u) return fail(RT_E_INVALID, f + ": scene and params must be non-NULL");
+    const int64_t count = static_cast<int64_t>(art::update_count(s->flat, kind));
+    if (first < 0 || n < 0 || first > count || n > count - first)
+        return fail(RT_E_INVALID, f + ": [first, first + n) must lie within the scene's " + std::to_string(count) + " " + row.nouns);
+    if (u->flags & ~RT_OUT_DEVICE) return fail(RT_E_INVALID, f + " takes RT_OUT_DEVICE only");
+    if (u->stream && !(u->flags & RT_OUT_DEVICE)) return fail(RT_E_INVALID, f + ": stream needs RT_OUT_DEVICE (host buffers run on the scene's own stream)");
+    if (n > 0 && !v) return fail(RT_E_INVALID, f + ": the value buffer is NULL");
+    if (u->flags & RT_OUT_DEVICE) return RT_OK;  // a device buffer is not inspected
+    const auto refuse = [&](int64_t k, const std::string& subject, const char* fault) {
+        return fail(RT_E_INVALID, f + ": " + subject + " of " + row.noun + " " + std::to_string(first + k) + " " + fault);
+    };
+    for (int64_t k = 0; k < n; ++k) {
+        const double* record = v + row.width * static_cast<size_t>(k);
+        for (size_t field = 0; field < row.width; ++field)
+            if (!std::isfinite(record[field])) return refuse(k, "value " + std::to_string(field), "is not finite");
+        if (row.ok && !row.ok(record)) return refuse(k, row.subject, row.fault);
+    }
+    return RT_OK;
+}
+
+static int scene_update(art::UpdateKind kind, rt_scene* s, const rt_update_params* u, const double* v, int64_t first, int64_t n, double* ms) {
+    const int rc = update_check(kind, s, u, v, first, n);
+    if (rc != RT_OK) return rc;
+    if (ms) *ms = 0;
+    if (n == 0) return RT_OK;
+    return guard(RT_E_DEVICE, [&] {
+        s->device_renderer().update(kind, v, static_cast<size_t>(first), static_cast<size_t>(n), (u->flags & RT_OUT_DEVICE) != 0, u->stream, ms);
+        return RT_OK;
+    });
+}
+
+// A getter's common part: the count when no out pointer was passed (any_out false), the capacity check, then the host
+// copy as the device holds it.  Returns the count (the caller fills its buffers when any_out) or the error.
+static int64_t get_begin(art::UpdateKind kind, rt_scene* s, bool any_out, int64_t cap) {
+    const art::UpdateRow& row = art::update_row(kind);
+    const std::string f = std::string("rt_scene_") + row.nouns + "_get";
+    if (!s) return fail(RT_E_INVALID, f + ": scene is NULL");
+    const int64_t count = static_cast<int64_t>(art::update_count(s->flat, kind));
+    if (!any_out) return count;
+    if (cap < count)
+        return fail(RT_E_INVALID, f + ": the out buffers hold " + std::to_string(cap) + " " + row.nouns + ", the scene has " + std::to_string(count));
     const int rc = guard(RT_E_DEVICE, [&] {
         s->sync_flat();
         return RT_OK;
     });
-    if (rc != RT_OK) return rc;
+    return rc != RT_OK ? rc : count;
+}
+
+int64_t rt_scene_triangles_get(rt_scene* s, double* p_out, int64_t cap) {
+    const int64_t count = get_begin(art::UpdateKind::Triangles, s, p_out != nullptr, cap);
+    if (count < 0 || !p_out) return count;
     for (int64_t t = 0; t < count; ++t) std::memcpy(p_out + 9 * t, s->flat.tris[static_cast<size_t>(t)].p, 9 * sizeof(double));
     return count;
 }
 
 int rt_scene_update_triangles(rt_scene* s, const rt_update_params* u, const double* p, int64_t first, int64_t n, double* ms) {
-    if (!s || !u) return fail(RT_E_INVALID, "rt_scene_update_triangles: scene and params must be non-NULL");
-    const int64_t count = static_cast<int64_t>(s->flat.tris.size());
-    if (first < 0 || n < 0 || first > count || n > count - first)
-        return fail(RT_E_INVALID, "rt_scene_update_triangles: [first, first + n) must lie within the scene's " + std::to_string(count) + " triangles");
-    if (u->flags & ~RT_OUT_DEVICE) return fail(RT_E_INVALID, "rt_scene_update_triangles takes RT_OUT_DEVICE only");
-    if (u->stream && !(u->flags & RT_OUT_DEVICE))
-        return fail(RT_E_INVALID, "rt_scene_update_triangles: stream needs RT_OUT_DEVICE (host buffers run on the scene's own stream)");
-    if (n > 0 && !p) return fail(RT_E_INVALID, "rt_scene_update_triangles: p is NULL");
-    const bool device = (u->flags & RT_OUT_DEVICE) != 0;
-    if (!device)
-        for (int64_t i = 0; i < 9 * n; ++i)
-            if (!std::isfinite(p[i]))
-                return fail(RT_E_INVALID, "rt_scene_update_triangles: vertex value " + std::to_string(i % 9) + " of triangle " + std::to_string(first + i / 9) + " is not finite");
-    if (ms) *ms = 0;
-    if (n == 0) return RT_OK;
-    return guard(RT_E_DEVICE, [&] {
-        s->device_renderer().update_triangles(p, static_cast<size_t>(first), static_cast<size_t>(n), device, u->stream, ms);
-        return RT_OK;
-    });
+    return scene_update(art::UpdateKind::Triangles, s, u, p, first, n, ms);
 }
 
 int64_t rt_scene_spheres_get(rt_scene* s, double* s_out, int64_t cap) {
-    if (!s) return fail(RT_E_INVALID, "rt_scene_spheres_get: scene is NULL");
-    const int64_t count = static_cast<int64_t>(s->flat.spheres.size());
-    if (!s_out) return count;
-    if (cap < count) return fail(RT_E_INVALID, "rt_scene_spheres_get: s_out holds " + std::to_string(cap) + " spheres, the scene has " + std::to_string(count));
-    const int rc = guard(RT_E_DEVICE, [&] {
-        s->sync_flat();
-        return RT_OK;
-    });
-    if (rc != RT_OK) return rc;
+    const int64_t count = get_begin(art::UpdateKind::Spheres, s, s_out != nullptr, cap);
+    if (count < 0 || !s_out) return count;
     for (int64_t k = 0; k < count; ++k) {
         const art::SphereRec& sp = s->flat.spheres[static_cast<size_t>(k)];
         s_out[4 * k] = sp.c[0], s_out[4 * k + 1] = sp.c[1], s_out[4 * k + 2] = sp.c[2], s_out[4 * k + 3] = sp.r;
@@ -305,28 +326,7 @@ int64_t rt_scene_spheres_get(rt_scene* s, double* s_out, int64_t cap) {
 }
 
 int rt_scene_update_spheres(rt_scene* s, const rt_update_params* u, const double* v, int64_t first, int64_t n, double* ms) {
-    if (!s || !u) return fail(RT_E_INVALID, "rt_scene_update_spheres: scene and params must be non-NULL");
-    const int64_t count = static_cast<int64_t>(s->flat.spheres.size());
-    if (first < 0 || n < 0 || first > count || n > count - first)
-        return fail(RT_E_INVALID, "rt_scene_update_spheres: [first, first + n) must lie within the scene's " + std::to_string(count) + " spheres");
-    if (u->flags & ~RT_OUT_DEVICE) return fail(RT_E_INVALID, "rt_scene_update_spheres takes RT_OUT_DEVICE only");
-    if (u->stream && !(u->flags & RT_OUT_DEVICE))
-        return fail(RT_E_INVALID, "rt_scene_update_spheres: stream needs RT_OUT_DEVICE (host buffers run on the scene's own stream)");
-    if (n > 0 && !v) return fail(RT_E_INVALID, "rt_scene_update_spheres: s is NULL");
-    const bool device = (u->flags & RT_OUT_DEVICE) != 0;
-    if (!device)
-        for (int64_t i = 0; i < 4 * n; ++i) {
-            if (!std::isfinite(v[i]))
-                return fail(RT_E_INVALID, "rt_scene_update_spheres: value " + std::to_string(i % 4) + " of sphere " + std::to_string(first + i / 4) + " is not finite");
-            if (i % 4 == 3 && !(v[i] > 0.0))
-                return fail(RT_E_INVALID, "rt_scene_update_spheres: the radius of sphere " + std::to_string(first + i / 4) + " is not positive");
-        }
-    if (ms) *ms = 0;
-    if (n == 0) return RT_OK;
-    return guard(RT_E_DEVICE, [&] {
-        s->device_renderer().update_spheres(v, static_cast<size_t>(first), static_cast<size_t>(n), device, u->stream, ms);
-        return RT_OK;
-    });
+    return scene_update(art::UpdateKind::Spheres, s, u, v, first, n, ms);
 }
 
 int64_t rt_scene_lds_image_get(rt_scene* s, int32_t rebuilt, uint8_t* out, int64_t cap) {
@@ -351,23 +351,9 @@ static_assert(RT_TEX_SOLID == art::TEX_SOLID && RT_TEX_CHECKER == art::TEX_CHECK
                   RT_TEX_BARY_IMAGE == art::TEX_BARY_IMAGE,
               "art.h's RT_TEX_* are layout.h's TexType");
 
-// The getters' common part: the count without out pointers, the capacity check, then the host copy as the device holds it
-static int64_t appearance_get(rt_scene* s, const char* fn, const char* what, int64_t count, bool any_out, int64_t cap) {
-    if (!any_out) return count;
-    if (cap < count)
-        return fail(RT_E_INVALID, std::string(fn) + ": the out buffers hold " + std::to_string(cap) + " " + what + ", the scene has " + std::to_string(count));
-    const int rc = guard(RT_E_DEVICE, [&] {
-        s->sync_flat();
-        return RT_OK;
-    });
-    return rc != RT_OK ? rc : count;
-}
-
 int64_t rt_scene_materials_get(rt_scene* s, double* params_out, int32_t* desc_out, int64_t cap) {
-    if (!s) return fail(RT_E_INVALID, "rt_scene_materials_get: scene is NULL");
-    const int64_t count = static_cast<int64_t>(s->flat.mats.size());
-    const int64_t rc = appearance_get(s, "rt_scene_materials_get", "materials", count, params_out || desc_out, cap);
-    if (rc < 0 || (!params_out && !desc_out)) return rc;
+    const int64_t count = get_begin(art::UpdateKind::Materials, s, params_out || desc_out, cap);
+    if (count < 0 || (!params_out && !desc_out)) return count;
     for (int64_t k = 0; k < count; ++k) {
         const art::MatRec& m = s->flat.mats[static_cast<size_t>(k)];
         if (params_out) {
@@ -383,10 +369,8 @@ int64_t rt_scene_materials_get(rt_scene* s, double* params_out, int32_t* desc_ou
 }
 
 int64_t rt_scene_textures_get(rt_scene* s, double* params_out, int32_t* desc_out, int64_t cap) {
-    if (!s) return fail(RT_E_INVALID, "rt_scene_textures_get: scene is NULL");
-    const int64_t count = static_cast<int64_t>(s->flat.texs.size());
-    const int64_t rc = appearance_get(s, "rt_scene_textures_get", "textures", count, params_out || desc_out, cap);
-    if (rc < 0 || (!params_out && !desc_out)) return rc;
+    const int64_t count = get_begin(art::UpdateKind::Textures, s, params_out || desc_out, cap);
+    if (count < 0 || (!params_out && !desc_out)) return count;
     for (int64_t k = 0; k < count; ++k) {
         const art::TexRec& t = s->flat.texs[static_cast<size_t>(k)];
         if (params_out) {
@@ -401,43 +385,12 @@ int64_t rt_scene_textures_get(rt_scene* s, double* params_out, int32_t* desc_out
     return count;
 }
 
-// The refusals rt_scene_update_materials and rt_scene_update_textures share (all before any device work); RT_OK: go on
-static int appearance_update_check(const char* fn, const char* what, rt_scene* s, const rt_update_params* u, const double* v, int width, int64_t count,
-                                   int64_t first, int64_t n) {
-    const std::string f(fn);
-    if (!s || !u) return fail(RT_E_INVALID, f + ": scene and params must be non-NULL");
-    if (first < 0 || n < 0 || first > count || n > count - first)
-        return fail(RT_E_INVALID, f + ": [first, first + n) must lie within the scene's " + std::to_string(count) + " " + what + "s");
-    if (u->flags & ~RT_OUT_DEVICE) return fail(RT_E_INVALID, f + " takes RT_OUT_DEVICE only");
-    if (u->stream && !(u->flags & RT_OUT_DEVICE)) return fail(RT_E_INVALID, f + ": stream needs RT_OUT_DEVICE (host buffers run on the scene's own stream)");
-    if (n > 0 && !v) return fail(RT_E_INVALID, f + ": the value buffer is NULL");
-    if (!(u->flags & RT_OUT_DEVICE))
-        for (int64_t i = 0; i < width * n; ++i)
-            if (!std::isfinite(v[i]))
-                return fail(RT_E_INVALID, f + ": value " + std::to_string(i % width) + " of " + what + " " + std::to_string(first + i / width) + " is not finite");
-    return RT_OK;
-}
-
 int rt_scene_update_materials(rt_scene* s, const rt_update_params* u, const double* m, int64_t first, int64_t n, double* ms) {
-    const int rc = appearance_update_check("rt_scene_update_materials", "material", s, u, m, RT_MATERIAL_DOUBLES, s ? static_cast<int64_t>(s->flat.mats.size()) : 0, first, n);
-    if (rc != RT_OK) return rc;
-    if (ms) *ms = 0;
-    if (n == 0) return RT_OK;
-    return guard(RT_E_DEVICE, [&] {
-        s->device_renderer().update_materials(m, static_cast<size_t>(first), static_cast<size_t>(n), (u->flags & RT_OUT_DEVICE) != 0, u->stream, ms);
-        return RT_OK;
-    });
+    return scene_update(art::UpdateKind::Materials, s, u, m, first, n, ms);
 }
 
 int rt_scene_update_textures(rt_scene* s, const rt_update_params* u, const double* t, int64_t first, int64_t n, double* ms) {
-    const int rc = appearance_update_check("rt_scene_update_textures", "texture", s, u, t, RT_TEXTURE_DOUBLES, s ? static_cast<int64_t>(s->flat.texs.size()) : 0, first, n);
-    if (rc != RT_OK) return rc;
-    if (ms) *ms = 0;
-    if (n == 0) return RT_OK;
-    return guard(RT_E_DEVICE, [&] {
-        s->device_renderer().update_textures(t, static_cast<size_t>(first), static_cast<size_t>(n), (u->flags & RT_OUT_DEVICE) != 0, u->stream, ms);
-        return RT_OK;
-    });
+    return scene_update(art::UpdateKind::Textures, s, u, t, first, n, ms);
 }
 
 int rt_scene_bvh_get(rt_scene* s, void* nodes_out, int64_t node_cap, uint32_t* primrefs_out, int64_t ref_cap, int64_t* n_nodes, int64_t* n_primrefs) {

@@ -140,48 +140,38 @@ __global__ void __launch_bounds__(kRefitBlock) k_refit_level(BvhNode* nodes, uin
     if (n < end) refit_child(nodes, n_nodes, slot_box, n_slots, n, static_cast<int>(i & 3u));
 }
 
-void launch_update_tris(hipStream_t st, const UpdateJob& j) {
-    const uint32_t threads = std::max(std::max(j.n_slots, j.n), j.n_objs);
+// One thread per item in blocks of kRefitBlock; nothing to do is no launch
+template <class... Params, class... Args>
+static void launch_1d(void (*kernel)(Params...), uint32_t threads, hipStream_t st, const Args&... args) {
     if (threads == 0) return;
-    hipLaunchKernelGGL(k_update_tris, dim3((threads + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, j);
+    hipLaunchKernelGGL(kernel, dim3((threads + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, args...);
 }
 
-void launch_update_spheres(hipStream_t st, const SphereJob& j) {
-    const uint32_t threads = std::max(std::max(j.n_slots, j.n), j.n_objs);
-    if (threads == 0) return;
-    hipLaunchKernelGGL(k_update_spheres, dim3((threads + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, j);
-}
+void launch_update_tris(hipStream_t st, const UpdateJob& j) { launch_1d(k_update_tris, std::max(std::max(j.n_slots, j.n), j.n_objs), st, j); }
+
+void launch_update_spheres(hipStream_t st, const SphereJob& j) { launch_1d(k_update_spheres, std::max(std::max(j.n_slots, j.n), j.n_objs), st, j); }
 
 void launch_image_nodes(hipStream_t st, uint8_t* image, const BvhNode* nodes, uint32_t n_nodes) {
-    if (!image || n_nodes == 0) return;
-    hipLaunchKernelGGL(k_image_nodes, dim3((n_nodes + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, image, nodes, n_nodes);
-}
-
-static void launch_derive_materials(hipStream_t st, const AppearanceJob& j) {
-    if (j.n_mats == 0) return;
-    hipLaunchKernelGGL(k_derive_materials, dim3((j.n_mats + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, j);
+    if (image) launch_1d(k_image_nodes, n_nodes, st, image, nodes, n_nodes);
 }
 
 void launch_update_materials(hipStream_t st, const AppearanceJob& j) {
     if (j.n == 0) return;
-    hipLaunchKernelGGL(k_update_materials, dim3((j.n + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, j);
-    launch_derive_materials(st, j);
+    launch_1d(k_update_materials, j.n, st, j);
+    launch_1d(k_derive_materials, j.n_mats, st, j);
 }
 
 void launch_update_textures(hipStream_t st, const AppearanceJob& j) {
     if (j.n == 0) return;
-    hipLaunchKernelGGL(k_update_textures, dim3((j.n + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, j);
-    launch_derive_materials(st, j);
+    launch_1d(k_update_textures, j.n, st, j);
+    launch_1d(k_derive_materials, j.n_mats, st, j);
 }
 
 void launch_refit_levels(hipStream_t st, BvhNode* nodes, uint32_t n_nodes, const double* slot_box, uint32_t n_slots,
                          const std::vector<uint32_t>& level_begin) {
     for (size_t l = level_begin.size(); l-- > 1;) {
         const uint32_t begin = level_begin[l - 1], end = level_begin[l];
-        if (end <= begin) continue;
-        const uint32_t threads = 4u * (end - begin);
-        hipLaunchKernelGGL(k_refit_level, dim3((threads + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, nodes, n_nodes, slot_box,
-                           n_slots, begin, end);
+        if (end > begin) launch_1d(k_refit_level, 4u * (end - begin), st, nodes, n_nodes, slot_box, n_slots, begin, end);
     }
 }
 

@@ -7,6 +7,7 @@
 #include "layout.h"
 #include "noise_target.h"
 #include "scene.h"
+#include "update_kinds.h"
 
 namespace art {
 
@@ -93,26 +94,23 @@ public:
     // the number of tiles, or 0 when render() would build no lists (the scene, the option, the mode or the sample
     // count).  counts may be null (the number only); otherwise it holds at least `cap` >= tiles entries.
     int tile_candidates(const CameraRec& cam, const RenderParams& p, uint16_t* counts, size_t cap);
-    // rt_scene_update_triangles: new vertices p (9 doubles each) for triangles [first, first + n) of flat().tris, written
-    // into every device array that holds a triangle (k_update_tris), then a refit of every BVH box, one launch per tree
-    // level from the deepest up (k_refit_level; refit.h).  device: p is a device pointer read in place on `stream` (null:
-    // the scene's own, and the call waits); a host p goes through the workspace: a copy, the kernels, a wait, as
-    // query_rays.  ms (may be null: then a device call on the caller's stream returns once enqueued): HIP events around
-    // the kernels.  The scene's first update makes the slot boxes and the level table (blocking).  Leaves the host copy
-    // stale: generation() counts the updates, current_flat() fetches before it answers.
-    void update_triangles(const double* p, size_t first, size_t n, bool device, void* stream, double* ms);
-    // rt_scene_update_spheres: new (cx, cy, cz, r) s (4 doubles each) for spheres [first, first + n) of flat().spheres,
-    // written into every device array that holds a sphere, the LDS scene image's sphere planes included
-    // (k_update_spheres), then the same refit, then the image's box planes from the refitted nodes (k_image_nodes).
-    // mat, flags and a moving sphere's d, t0, dt stay.  Buffers, streams, ms and the host copy as update_triangles.
-    void update_spheres(const double* s, size_t first, size_t n, bool device, void* stream, double* ms);
-    // rt_scene_update_materials / rt_scene_update_textures: new values (5 doubles per material: albedo, fuzz, ir; 4 per
-    // texture: colour, scale) for records [first, first + n) of flat().mats / flat().texs.  A record takes what its type
-    // uses (k_update_materials, k_update_textures); then every material of the scene gets its copies refreshed
-    // (k_derive_materials): the solid colour inlined into a MATF_SOLID record, and the LDS scene image's shading-table
-    // entries.  Types, links, boxes and the tree stay.  Buffers, streams, ms and the host copy as update_triangles.
-    void update_materials(const double* m, size_t first, size_t n, bool device, void* stream, double* ms);
-    void update_textures(const double* t, size_t first, size_t n, bool device, void* stream, double* ms);
+    // rt_scene_update_triangles / _spheres / _materials / _textures (update_kinds.h): new values v for records
+    // [first, first + n) of the kind's array in flat(), written into every device array that holds such a record.  device: v is a device pointer
+    // read in place on `stream` (null: the scene's own, and the call waits); a host v goes through the workspace: a copy,
+    // the kernels, a wait, as query_rays.  ms (may be null: then a device call on the caller's stream returns once
+    // enqueued): HIP events around the kernels.  A scene's first update of a geometry kind, and of an appearance kind,
+    // makes what the kind's kernels need beside the scene (blocking).  Leaves the host copy stale: generation() counts the
+    // updates, current_flat() fetches before it answers.
+    //   Triangles: 9 doubles, the vertices (k_update_tris); then a refit of every BVH box, one launch per tree level from
+    //     the deepest up (k_refit_level; refit.h).  First: the slot boxes, the pad flags and the level table.
+    //   Spheres: 4 doubles, cx, cy, cz, r, the LDS scene image's sphere planes included (k_update_spheres); then the same
+    //     refit, then the image's box planes from the refitted nodes (k_image_nodes).  mat, flags and a moving sphere's
+    //     d, t0, dt stay.  First: as Triangles (whichever comes first makes them for both).
+    //   Materials (5 doubles: albedo, fuzz, ir), Textures (4: colour, scale): a record takes what its type uses
+    //     (k_update_materials, k_update_textures); then every material of the scene gets its copies refreshed
+    //     (k_derive_materials): the solid colour inlined into a MATF_SOLID record, and the image's shading-table entries.
+    //     Types, links, boxes and the tree stay.  First: with an image, every material's entry code.
+    void update(UpdateKind kind, const double* v, size_t first, size_t n, bool device, void* stream, double* ms);
     // rt_scene_lds_image_get: kLdsImageBytes + sizeof(TileReps), or 0 when the scene has no LDS image; out (may be null:
     // the size only) receives the device's bytes, or with `rebuilt` what build_lds_image makes of current_flat().
     size_t lds_image_get(bool rebuilt, uint8_t* out);

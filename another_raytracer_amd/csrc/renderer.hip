@@ -847,7 +847,7 @@ void Renderer::render_noise_target(const CameraRec& cam, const RenderParams& p, 
     result.rounds = rounds, result.converged_pixels = nconv;
 }
 
-// ------------------------------------------------------------------------------------------------ rt_scene_update_triangles
+// ------------------------------------------------------------------------------------------------ rt_scene_update_*
 // What a scene's first update makes: the f64 box of every leaf slot's primitive from the host records (refit.h; a
 // pad slot of the pair-aligned copy gets the empty box), uploaded once -- after that only k_update_tris writes it --
 // and the level ranges of the node array.
@@ -873,66 +873,6 @@ static void prepare_refit(const FlatScene& f, DeviceScene& ds) {
     ds.slot_pad_dev = ds.upload(ds.slot_pad);
 }
 
-void Renderer::update_triangles(const double* p, size_t first, size_t n, bool device, void* stream, double* ms) {
-    upload();
-    Impl& I = *impl_;
-    DeviceScene& ds = I.s64;
-    if (n == 0) return;
-    if (first + n > I.flat.tris.size()) throw std::runtime_error("update_triangles: range beyond the scene's triangles");
-    prepare_refit(I.flat, ds);
-    Call call(I.own_stream, I.ev, device, stream, ms != nullptr);
-    hipStream_t st = call.st;
-    UpdateJob job{};
-    call.carve(I.ws, [&](Carver& c) { job.p = call.in(c, p, 9 * n); }, 1);  // host vertices: through the workspace
-    job.first = static_cast<uint32_t>(first), job.n = static_cast<uint32_t>(n);
-    job.primrefs = ds.view.primrefs, job.objs = ds.view.objs;
-    job.n_slots = ds.view.n_primrefs, job.n_objs = ds.view.n_objs;
-    // the arrays build_device_scene uploaded: const in the kernels' view only, the DeviceScene owns them
-    job.tris = const_cast<TriRec*>(ds.view.tris);
-    job.leaf_tris = const_cast<TriRec*>(ds.view.leaf_tris);
-    job.leaf_tris112 = const_cast<TriRec112*>(ds.view.leaf_tris112);
-    job.leaf_prims = const_cast<PrimRec80*>(ds.view.leaf_prims);
-    job.obj_prims = const_cast<PrimRec80*>(ds.view.obj_prims);
-    job.slot_box = ds.slot_box;
-    call.begin();
-    launch_update_tris(st, job);
-    if (ds.slot_box) launch_refit_levels(st, const_cast<BvhNode*>(ds.view.nodes), ds.view.n_nodes, ds.slot_box, ds.view.n_primrefs, ds.level_begin);
-    call.end();
-    ++I.gen;
-    const Call::Done done = call.finish();  // (a device call on the caller's stream without ms returns enqueued)
-    if (ms) *ms = done.ms;
-}
-
-void Renderer::update_spheres(const double* s, size_t first, size_t n, bool device, void* stream, double* ms) {
-    upload();
-    Impl& I = *impl_;
-    DeviceScene& ds = I.s64;
-    if (n == 0) return;
-    if (first + n > I.flat.spheres.size()) throw std::runtime_error("update_spheres: range beyond the scene's spheres");
-    prepare_refit(I.flat, ds);
-    Call call(I.own_stream, I.ev, device, stream, ms != nullptr);
-    hipStream_t st = call.st;
-    SphereJob job{};
-    call.carve(I.ws, [&](Carver& c) { job.s = call.in(c, s, 4 * n); }, 1);  // host values: through the workspace
-    job.first = static_cast<uint32_t>(first), job.n = static_cast<uint32_t>(n);
-    job.primrefs = ds.view.primrefs, job.slot_pad = ds.slot_pad_dev, job.objs = ds.view.objs;
-    job.n_slots = ds.slot_box ? ds.view.n_primrefs : 0u, job.n_objs = ds.view.n_objs;
-    // the arrays build_device_scene uploaded: const in the kernels' view only, the DeviceScene owns them
-    job.spheres = const_cast<SphereRec*>(ds.view.spheres);
-    job.leaf_prims = const_cast<PrimRec80*>(ds.view.leaf_prims);
-    job.obj_prims = const_cast<PrimRec80*>(ds.view.obj_prims);
-    job.slot_box = ds.slot_box;
-    job.image = ds.lds_scene ? const_cast<uint8_t*>(ds.view.lds_image) : nullptr;
-    call.begin();
-    launch_update_spheres(st, job);
-    if (ds.slot_box) launch_refit_levels(st, const_cast<BvhNode*>(ds.view.nodes), ds.view.n_nodes, ds.slot_box, ds.view.n_primrefs, ds.level_begin);
-    launch_image_nodes(st, job.image, ds.view.nodes, ds.view.n_nodes);
-    call.end();
-    ++I.gen;
-    const Call::Done done = call.finish();  // (a device call on the caller's stream without ms returns enqueued)
-    if (ms) *ms = done.ms;
-}
-
 // What a scene's first material or texture update makes: with an image, the entry code of every material on the
 // device.  (No slot boxes: nothing moves.)
 static void prepare_appearance(const FlatScene& f, DeviceScene& ds) {
@@ -945,42 +885,74 @@ static void prepare_appearance(const FlatScene& f, DeviceScene& ds) {
     ds.mat_entry_dev = ds.upload(entry);
 }
 
-// The common part of update_materials and update_textures (the scene is uploaded): `width` doubles per record of
-// [first, first + n)
-static void update_appearance(Renderer::Impl& I, const double* v, size_t width, size_t first, size_t n, bool device, void* stream, double* ms,
-                              void (*launch)(hipStream_t, const AppearanceJob&)) {
+// The kind's job struct from the device scene and its launches: the kind's kernel, then for geometry the refit of every
+// box (once a first update made the slot boxes) and, for spheres, the image's box planes from the refitted nodes.  The
+// arrays build_device_scene uploaded are const in the kernels' view only: the DeviceScene owns them.
+static void enqueue_update(UpdateKind kind, hipStream_t st, const DeviceScene& ds, const double* v, uint32_t first, uint32_t n) {
+    const auto& w = ds.view;
+    uint8_t* image = ds.lds_scene ? const_cast<uint8_t*>(w.lds_image) : nullptr;
+    switch (kind) {
+        case UpdateKind::Triangles: {
+            UpdateJob job{};
+            job.p = v, job.first = first, job.n = n;
+            job.primrefs = w.primrefs, job.objs = w.objs;
+            job.n_slots = w.n_primrefs, job.n_objs = w.n_objs;
+            job.tris = const_cast<TriRec*>(w.tris);
+            job.leaf_tris = const_cast<TriRec*>(w.leaf_tris);
+            job.leaf_tris112 = const_cast<TriRec112*>(w.leaf_tris112);
+            job.leaf_prims = const_cast<PrimRec80*>(w.leaf_prims);
+            job.obj_prims = const_cast<PrimRec80*>(w.obj_prims);
+            job.slot_box = ds.slot_box;
+            launch_update_tris(st, job);
+            break;
+        }
+        case UpdateKind::Spheres: {
+            SphereJob job{};
+            job.s = v, job.first = first, job.n = n;
+            job.primrefs = w.primrefs, job.slot_pad = ds.slot_pad_dev, job.objs = w.objs;
+            job.n_slots = ds.slot_box ? w.n_primrefs : 0u, job.n_objs = w.n_objs;
+            job.spheres = const_cast<SphereRec*>(w.spheres);
+            job.leaf_prims = const_cast<PrimRec80*>(w.leaf_prims);
+            job.obj_prims = const_cast<PrimRec80*>(w.obj_prims);
+            job.slot_box = ds.slot_box;
+            job.image = image;
+            launch_update_spheres(st, job);
+            break;
+        }
+        default: {
+            AppearanceJob job{};
+            job.v = v, job.first = first, job.n = n;
+            job.mats = const_cast<MatRec*>(w.mats);
+            job.texs = const_cast<TexRec*>(w.texs);
+            job.n_mats = w.n_mats;
+            job.entry = ds.mat_entry_dev;
+            job.image = image;
+            (kind == UpdateKind::Materials ? launch_update_materials : launch_update_textures)(st, job);
+            return;  // nothing moved
+        }
+    }
+    if (ds.slot_box) launch_refit_levels(st, const_cast<BvhNode*>(w.nodes), w.n_nodes, ds.slot_box, w.n_primrefs, ds.level_begin);
+    if (kind == UpdateKind::Spheres) launch_image_nodes(st, image, w.nodes, w.n_nodes);
+}
+
+void Renderer::update(UpdateKind kind, const double* v, size_t first, size_t n, bool device, void* stream, double* ms) {
+    const UpdateRow& row = update_row(kind);
+    upload();
+    Impl& I = *impl_;
     DeviceScene& ds = I.s64;
-    prepare_appearance(I.flat, ds);
+    if (n == 0) return;
+    if (first + n > update_count(I.flat, kind)) throw std::runtime_error(std::string("update_") + row.nouns + ": range beyond the scene's " + row.nouns);
+    if (row.geometry) prepare_refit(I.flat, ds);
+    else prepare_appearance(I.flat, ds);
     Call call(I.own_stream, I.ev, device, stream, ms != nullptr);
-    AppearanceJob job{};
-    call.carve(I.ws, [&](Carver& c) { job.v = call.in(c, v, width * n); }, 1);  // host values: through the workspace
-    job.first = static_cast<uint32_t>(first), job.n = static_cast<uint32_t>(n);
-    // the arrays build_device_scene uploaded: const in the kernels' view only, the DeviceScene owns them
-    job.mats = const_cast<MatRec*>(ds.view.mats);
-    job.texs = const_cast<TexRec*>(ds.view.texs);
-    job.n_mats = ds.view.n_mats;
-    job.entry = ds.mat_entry_dev;
-    job.image = ds.lds_scene ? const_cast<uint8_t*>(ds.view.lds_image) : nullptr;
+    const double* in = nullptr;
+    call.carve(I.ws, [&](Carver& c) { in = call.in(c, v, row.width * n); }, 1);  // host values: through the workspace
     call.begin();
-    launch(call.st, job);
+    enqueue_update(kind, call.st, ds, in, static_cast<uint32_t>(first), static_cast<uint32_t>(n));
     call.end();
     ++I.gen;
     const Call::Done done = call.finish();  // (a device call on the caller's stream without ms returns enqueued)
     if (ms) *ms = done.ms;
-}
-
-void Renderer::update_materials(const double* m, size_t first, size_t n, bool device, void* stream, double* ms) {
-    upload();
-    if (n == 0) return;
-    if (first + n > impl_->flat.mats.size()) throw std::runtime_error("update_materials: range beyond the scene's materials");
-    update_appearance(*impl_, m, 5, first, n, device, stream, ms, launch_update_materials);
-}
-
-void Renderer::update_textures(const double* t, size_t first, size_t n, bool device, void* stream, double* ms) {
-    upload();
-    if (n == 0) return;
-    if (first + n > impl_->flat.texs.size()) throw std::runtime_error("update_textures: range beyond the scene's textures");
-    update_appearance(*impl_, t, 4, first, n, device, stream, ms, launch_update_textures);
 }
 
 size_t Renderer::lds_image_get(bool rebuilt, uint8_t* out) {

@@ -16,8 +16,8 @@ import ctypes
 
 import numpy as np
 
-from ._lib import RT_OUT_DEVICE, check, lib, rt_update_params
-from ._buffers import address, stream_handle
+from . import _update
+from ._lib import check, lib
 from .rays import _native_scene
 
 # layout.h BvhNode as uploaded: the four child boxes as planes, the 32-bit child codes, the 16-bit codes in pad
@@ -30,12 +30,7 @@ def scene_triangles(world):
     """rt_scene_triangles_get: the scene's triangles as it holds them now, (n, 3, 3) float64 -- triangle, vertex (pt1, pt2,
     pt3), xyz -- in compiled order: the order the triangles are met walking the world list.  Takes a scene_manager scene,
     its .objects or a compile_world handle.  Needs no device unless the scene has been updated."""
-    handle = _native_scene(world)
-    n = check(lib.rt_scene_triangles_get(handle, None, 0), "scene_triangles")
-    out = np.empty((n, 3, 3), np.float64)
-    if n:
-        check(lib.rt_scene_triangles_get(handle, ctypes.c_void_p(out.ctypes.data), n), "scene_triangles")
-    return out
+    return _update.get(world, "scene_triangles", ((3, 3), np.float64))[0]
 
 
 def update_triangles(world, p, first=0, stream=None, timing=False):
@@ -47,32 +42,14 @@ def update_triangles(world, p, first=0, stream=None, timing=False):
     call then returns once the work is enqueued, unless timing is asked for.  The update writes the arrays the render
     kernels read: order the calls on one scene on one stream, or synchronise between them.  timing=True returns the
     device time of the update's kernels in milliseconds (HIP events; waits), otherwise None."""
-    handle = _native_scene(world)
-    if not hasattr(p, "shape"):
-        raise TypeError("p must be a numpy array or a torch tensor")
-    shape = tuple(int(x) for x in p.shape)
-    if not (len(shape) == 3 and shape[1:] == (3, 3)) and not (len(shape) == 2 and shape[1] == 9):
-        raise ValueError("p must have shape (n, 3, 3) or (n, 9): three vertices per triangle")
-    ptr, dev = address(p, "p", ("float64",), shape=shape, device_index=handle.device)
-    u = rt_update_params()
-    u.flags = RT_OUT_DEVICE if dev else 0
-    u.stream = stream_handle(stream, p.device if dev else None)
-    ms = ctypes.c_double()
-    check(lib.rt_scene_update_triangles(handle, ctypes.byref(u), ctypes.c_void_p(ptr), int(first), shape[0], ctypes.byref(ms) if timing else None),
-          "update_triangles")
-    return ms.value if timing else None
+    return _update.update(world, p, "p", ((3, 3), (9,)), "shape (n, 3, 3) or (n, 9): three vertices per triangle", "update_triangles", first, stream, timing)
 
 
 def scene_spheres(world):
     """rt_scene_spheres_get: the scene's spheres as it holds them now, (n, 4) float64 -- cx, cy, cz, r; center0 for a
     moving_sphere -- in compiled order: the order the spheres are met walking the world list.  Needs no device unless the
     scene has been updated."""
-    handle = _native_scene(world)
-    n = check(lib.rt_scene_spheres_get(handle, None, 0), "scene_spheres")
-    out = np.empty((n, 4), np.float64)
-    if n:
-        check(lib.rt_scene_spheres_get(handle, ctypes.c_void_p(out.ctypes.data), n), "scene_spheres")
-    return out
+    return _update.get(world, "scene_spheres", ((4,), np.float64))[0]
 
 
 def update_spheres(world, s, first=0, stream=None, timing=False):
@@ -86,20 +63,7 @@ def update_spheres(world, s, first=0, stream=None, timing=False):
 
     s, stream and timing are update_triangles': a numpy array copies and blocks (a non-finite value or a radius <= 0 is
     refused), a contiguous float64 torch tensor on the scene's device is read in place on `stream` and is not inspected."""
-    handle = _native_scene(world)
-    if not hasattr(s, "shape"):
-        raise TypeError("s must be a numpy array or a torch tensor")
-    shape = tuple(int(x) for x in s.shape)
-    if not (len(shape) == 2 and shape[1] == 4):
-        raise ValueError("s must have shape (n, 4): cx, cy, cz, r per sphere")
-    ptr, dev = address(s, "s", ("float64",), shape=shape, device_index=handle.device)
-    u = rt_update_params()
-    u.flags = RT_OUT_DEVICE if dev else 0
-    u.stream = stream_handle(stream, s.device if dev else None)
-    ms = ctypes.c_double()
-    check(lib.rt_scene_update_spheres(handle, ctypes.byref(u), ctypes.c_void_p(ptr), int(first), shape[0], ctypes.byref(ms) if timing else None),
-          "update_spheres")
-    return ms.value if timing else None
+    return _update.update(world, s, "s", ((4,),), "shape (n, 4): cx, cy, cz, r per sphere", "update_spheres", first, stream, timing)
 
 
 def scene_lds_image(world, rebuilt=False):

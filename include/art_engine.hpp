@@ -225,86 +225,76 @@ inline void render_views(const scene& world, const std::vector<camera>& cams, in
           "render_views");
 }
 
+namespace detail {
+// rt_scene_update_*: the params from flags and stream, the call, the check
+template <class Fn>
+void scene_update(Fn fn, const char* where, const scene& world, const double* v, std::int64_t first, std::int64_t n, std::int32_t flags, void* stream,
+                  double* ms) {
+    rt_update_params u{};
+    u.flags = flags;
+    u.stream = stream;
+    check(fn(world.objects.get(), &u, v, first, n, ms), where);
+}
+// rt_scene_*_get: the count, then the fill of `width` doubles per record; get(out, cap) makes the call (out null: the count)
+template <class Get>
+std::vector<double> scene_get(Get get, const char* where, int width) {
+    const std::int64_t n = get(nullptr, 0);
+    check(n < 0 ? static_cast<int>(n) : RT_OK, where);
+    std::vector<double> v(static_cast<std::size_t>(width * n));
+    if (n > 0) {
+        const std::int64_t got = get(v.data(), n);
+        check(got < 0 ? static_cast<int>(got) : RT_OK, where);
+    }
+    return v;
+}
+// ... with the optional descriptions, desc_width int32 per record
+template <class Fn>
+std::vector<double> scene_get(Fn fn, const char* where, const scene& world, int width, std::vector<std::int32_t>* desc, int desc_width) {
+    return scene_get([&](double* out, std::int64_t cap) {
+        if (desc) desc->assign(static_cast<std::size_t>(desc_width * cap), 0);
+        return fn(world.objects.get(), out, desc && out ? desc->data() : nullptr, cap);
+    }, where, width);
+}
+}  // namespace detail
+
 // Deforming a compiled scene (rt_scene_update_triangles).  scene_triangles: the world's triangles as it holds them now, 9
 // doubles each (pt1, pt2, pt3) in compiled order.  update_triangles: new vertices p (9 doubles each, that order) for
 // triangles [first, first + n), then a refit of every BVH box on the device; every later call on the world gives the bits
 // a world compiled fresh from those vertices gives.  flags: RT_OUT_DEVICE with `stream` for a device buffer -- the call
 // then returns once enqueued on a non-null stream unless ms (the device time of the update, milliseconds) is asked for.
 inline std::vector<double> scene_triangles(const scene& world) {
-    const std::int64_t n = rt_scene_triangles_get(world.objects.get(), nullptr, 0);
-    check(n < 0 ? static_cast<int>(n) : RT_OK, "scene_triangles");
-    std::vector<double> p(static_cast<std::size_t>(9 * n));
-    if (n > 0) {
-        const std::int64_t got = rt_scene_triangles_get(world.objects.get(), p.data(), n);
-        check(got < 0 ? static_cast<int>(got) : RT_OK, "scene_triangles");
-    }
-    return p;
+    return detail::scene_get([&](double* out, std::int64_t cap) { return rt_scene_triangles_get(world.objects.get(), out, cap); }, "scene_triangles", 9);
 }
 inline void update_triangles(const scene& world, const double* p, std::int64_t first, std::int64_t n, std::int32_t flags = 0, void* stream = nullptr,
                              double* ms = nullptr) {
-    rt_update_params u{};
-    u.flags = flags;
-    u.stream = stream;
-    check(rt_scene_update_triangles(world.objects.get(), &u, p, first, n, ms), "update_triangles");
+    detail::scene_update(rt_scene_update_triangles, "update_triangles", world, p, first, n, flags, stream, ms);
 }
 // The same for spheres (rt_scene_update_spheres): 4 doubles each (cx, cy, cz, r; center0 of a moving_sphere, whose motion
 // stays) in compiled order; the BVH boxes and, where the world runs out of it, the LDS scene image are refitted.
 inline std::vector<double> scene_spheres(const scene& world) {
-    const std::int64_t n = rt_scene_spheres_get(world.objects.get(), nullptr, 0);
-    check(n < 0 ? static_cast<int>(n) : RT_OK, "scene_spheres");
-    std::vector<double> s(static_cast<std::size_t>(4 * n));
-    if (n > 0) {
-        const std::int64_t got = rt_scene_spheres_get(world.objects.get(), s.data(), n);
-        check(got < 0 ? static_cast<int>(got) : RT_OK, "scene_spheres");
-    }
-    return s;
+    return detail::scene_get([&](double* out, std::int64_t cap) { return rt_scene_spheres_get(world.objects.get(), out, cap); }, "scene_spheres", 4);
 }
 inline void update_spheres(const scene& world, const double* s, std::int64_t first, std::int64_t n, std::int32_t flags = 0, void* stream = nullptr,
                            double* ms = nullptr) {
-    rt_update_params u{};
-    u.flags = flags;
-    u.stream = stream;
-    check(rt_scene_update_spheres(world.objects.get(), &u, s, first, n, ms), "update_spheres");
+    detail::scene_update(rt_scene_update_spheres, "update_spheres", world, s, first, n, flags, stream, ms);
 }
 // A compiled world's materials and textures (rt_scene_materials_get / rt_scene_textures_get): RT_MATERIAL_DOUBLES /
 // RT_TEXTURE_DOUBLES doubles per row, indexed by the graph's material / texture ids; desc (optional) receives the rows
 // {type, tex} / {type, even, odd}.  update_materials / update_textures write new values for rows [first, first + n); each
 // record takes what its type uses, and every device copy of a value follows (rt_scene_update_materials).
 inline std::vector<double> scene_materials(const scene& world, std::vector<std::int32_t>* desc = nullptr) {
-    const std::int64_t n = rt_scene_materials_get(world.objects.get(), nullptr, nullptr, 0);
-    check(n < 0 ? static_cast<int>(n) : RT_OK, "scene_materials");
-    std::vector<double> m(static_cast<std::size_t>(RT_MATERIAL_DOUBLES * n));
-    if (desc) desc->assign(static_cast<std::size_t>(2 * n), 0);
-    if (n > 0) {
-        const std::int64_t got = rt_scene_materials_get(world.objects.get(), m.data(), desc ? desc->data() : nullptr, n);
-        check(got < 0 ? static_cast<int>(got) : RT_OK, "scene_materials");
-    }
-    return m;
+    return detail::scene_get(rt_scene_materials_get, "scene_materials", world, RT_MATERIAL_DOUBLES, desc, 2);
 }
 inline std::vector<double> scene_textures(const scene& world, std::vector<std::int32_t>* desc = nullptr) {
-    const std::int64_t n = rt_scene_textures_get(world.objects.get(), nullptr, nullptr, 0);
-    check(n < 0 ? static_cast<int>(n) : RT_OK, "scene_textures");
-    std::vector<double> t(static_cast<std::size_t>(RT_TEXTURE_DOUBLES * n));
-    if (desc) desc->assign(static_cast<std::size_t>(3 * n), 0);
-    if (n > 0) {
-        const std::int64_t got = rt_scene_textures_get(world.objects.get(), t.data(), desc ? desc->data() : nullptr, n);
-        check(got < 0 ? static_cast<int>(got) : RT_OK, "scene_textures");
-    }
-    return t;
+    return detail::scene_get(rt_scene_textures_get, "scene_textures", world, RT_TEXTURE_DOUBLES, desc, 3);
 }
 inline void update_materials(const scene& world, const double* m, std::int64_t first, std::int64_t n, std::int32_t flags = 0, void* stream = nullptr,
                              double* ms = nullptr) {
-    rt_update_params u{};
-    u.flags = flags;
-    u.stream = stream;
-    check(rt_scene_update_materials(world.objects.get(), &u, m, first, n, ms), "update_materials");
+    detail::scene_update(rt_scene_update_materials, "update_materials", world, m, first, n, flags, stream, ms);
 }
 inline void update_textures(const scene& world, const double* t, std::int64_t first, std::int64_t n, std::int32_t flags = 0, void* stream = nullptr,
                             double* ms = nullptr) {
-    rt_update_params u{};
-    u.flags = flags;
-    u.stream = stream;
-    check(rt_scene_update_textures(world.objects.get(), &u, t, first, n, ms), "update_textures");
+    detail::scene_update(rt_scene_update_textures, "update_textures", world, t, first, n, flags, stream, ms);
 }
 
 // The engine with a runtime image size (the reference fixes W, H, C at compile time: engine<W,H,C> below); samples

@@ -12,43 +12,19 @@ V1 (v1()): every solid colour and metal albedo redrawn, seeded, in [0.05, 0.95]^
 fuzz in [0, 0.6] and the last metal's 1.5 (which must behave as 1), ir in [1.2, 2.4] and the last dielectric's 0.75, noise
 scale 4 -> 1.5.  Fields a record's type ignores keep V0's values."""
 import functools
-import os
 
 import numpy as np
 import pytest
 
 import another_raytracer_amd as art
 from another_raytracer_amd._lib import lib
+from tests.update_common import (ASSETS, H, NQ, OFF_INVR, OFF_MAT, SKY, SPP, W, bits, engine_for, frame_camera, grid_triangles, image_spheres,
+                                 kernel_of, make_sphere, quant, render, same_render, v3)
 
 pytestmark = pytest.mark.gpu
 
-W, H, SPP = 64, 36, 8
-NQ = 4096
-SKY = (0.6, 0.7, 0.9)
-ASSETS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
 LAMBERTIAN, METAL, DIELECTRIC, LIGHT, ISOTROPIC = range(5)
 SOLID, CHECKER, NOISE, IMAGE, BARY = range(5)
-
-# csrc/layout.h: the LDS scene image's planes (ART_LDS_NODE_CAP 272, 1024 slots, 512 material entries)
-NODE_CAP, SLOT_CAP = 272, 1024
-OFF_SPH = 10 * NODE_CAP * 16
-OFF_MOV = OFF_SPH + 2 * SLOT_CAP * 16
-OFF_REF = OFF_MOV + SLOT_CAP * 8
-OFF_MATIDX = OFF_REF + SLOT_CAP * 4
-OFF_MAT = OFF_MATIDX + SLOT_CAP * 2
-OFF_INVR = OFF_MAT + 512 * 32
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.int64)
-
-
-def quant(a):
-    return np.round(np.asarray(a, np.float64) * 2.0 ** 20) / 2.0 ** 20
-
-
-def v3(x):
-    return tuple(float(t) for t in x)
 
 
 # ------------------------------------------------------------------------------------------------ worlds
@@ -106,28 +82,6 @@ def sphere_mats(mk):
             mk.light(mk.solid((4.0, 4.0, 4.0))), mk.light(shared), mk.metal((0.8, 0.8, 0.8), 0.0), mk.dielectric(1.5)], shared
 
 
-def make_sphere(s, d, mat):
-    if d.any():
-        return art.moving_sphere(v3(s[:3]), v3(s[:3] + d), 0.0, 1.0, float(s[3]), mat)
-    return art.sphere(v3(s[:3]), float(s[3]), mat)
-
-
-def image_spheres():
-    """tests/test_gpu_update_spheres.py image_spec's 49 spheres: the ground and 48 small ones, 6 of them moving along y."""
-    rng = np.random.default_rng(21)
-    s0, d = np.zeros((49, 4)), np.zeros((49, 3))
-    s0[0] = (0.0, -100.0, 0.0, 100.0)
-    k = 1
-    for i in range(8):
-        for j in range(6):
-            r = rng.uniform(0.2, 0.3)
-            s0[k] = (-3.5 + i + rng.uniform(-0.2, 0.2), r, -2.5 + j + rng.uniform(-0.2, 0.2), r)
-            if k % 8 == 3:
-                d[k, 1] = 0.25 + 0.125 * (k % 3)
-            k += 1
-    return quant(s0), d
-
-
 IMAGE_S0, IMAGE_D = image_spheres()
 
 
@@ -143,20 +97,6 @@ def build_image(M=None, T=None, S=None):
     world = art.hittable_list(native=art.compile_world(w, 0))
     world.shared_id, world.counts = shared.id, (mk.nm, mk.nt)
     return world
-
-
-def grid_triangles():
-    """A 12 x 12 height field over [-3, 3]^2 with seeded random heights in [0, 1.5]: 288 triangles."""
-    rng = np.random.default_rng(7)
-    xs = np.linspace(-3.0, 3.0, 13)
-    y = rng.uniform(0.0, 1.5, (13, 13))
-    v = lambda i, j: (xs[i], y[i, j], xs[j])  # noqa: E731
-    tris = []
-    for i in range(12):
-        for j in range(12):
-            tris.append((v(i, j), v(i + 1, j), v(i, j + 1)))
-            tris.append((v(i + 1, j), v(i + 1, j + 1), v(i, j + 1)))
-    return np.array(tris, np.float64)
 
 
 def mixed_spheres():
@@ -196,12 +136,6 @@ def build_mixed(M=None, T=None, S=None):
 BUILD = {"image": build_image, "mixed": build_mixed}
 
 
-def frame_camera(name):
-    return {"image": art.camera((0.0, 3.0, 9.0), (0.0, 0.3, 0.0), (0, 1, 0), 40.0, W / H, 0.0, 10.0, 0.0, 1.0),
-            "mixed": art.camera((1.0, 7.0, 12.0), (0.0, 1.5, 0.0), (0, 1, 0), 40.0, W / H, 0.0, 10.0, 0.0, 1.0),
-            "side": art.camera((9.0, 4.0, 3.0), (0.0, 1.0, 0.0), (0, 1, 0), 40.0, W / H, 0.0, 10.0, 0.0, 1.0)}[name]
-
-
 def v1(M0, Md, T0, Td, seed=41):
     """V1 from V0 and the descriptions (module docstring); fields a record ignores keep V0's values."""
     rng = np.random.default_rng(seed)
@@ -229,29 +163,6 @@ def held(M):
     out = np.array(M)
     out[:, 3] = np.where(out[:, 3] < 1.0, out[:, 3], 1.0)
     return out
-
-
-def engine_for(world, cam, background=SKY, **form):
-    eng = art.engine(cam, art.engine_mode.single, width=W, height=H, samples_per_pixel=SPP, seed=5)
-    for k, v in form.items():
-        setattr(eng, k, v)
-    eng.set_scene(world, background)
-    return eng
-
-
-def render(world, cam, background=SKY, **form):
-    eng = engine_for(world, cam, background, **form)
-    img, acc = np.zeros((H, W, 3), np.uint8), np.zeros((H, W, 3), np.float64)
-    eng.run(img, accum=acc)
-    return img, acc, eng.stats
-
-
-def same_render(a, b):
-    return (a[0] == b[0]).all() and (bits(a[1]) == bits(b[1])).all() and a[2]["segments"] == b[2]["segments"]
-
-
-def kernel_of(stats):
-    return stats["kernel_features"], stats["kernel_textures"], stats["kernel_lds_mode"], stats["extend_variant"]
 
 
 @functools.lru_cache(maxsize=None)

@@ -11,91 +11,32 @@ Counts used for `image`: a ground sphere of radius 100 and 48 small ones (6 of t
 spheres; the ground is hoisted (no node leaf holds its slot), the scene runs k_paths (extend_variant 3, LDS mode 3)
 and has tile representatives (rt_tile_candidates > 0 under render.tile_lists = 2)."""
 import functools
-import os
 
 import numpy as np
 import pytest
 
 import another_raytracer_amd as art
 from another_raytracer_amd._lib import lib
+from tests.update_common import (ASSETS, F_LEAF2, F32, H, IMAGE_BYTES, NODE_CAP, NQ, OFF_INVR, OFF_MAT, OFF_MATIDX, OFF_MOV, OFF_REF, OFF_SPH,
+                                 REPS_BYTES, SKY, SLOT_CAP, SPP, W, bits, conservative_box_np, covered_slots, engine_for, frame_camera,
+                                 grid_triangles, image_spheres, kernel_of, make_sphere, quant, render, same_queries, same_render, v3)
 
 pytestmark = pytest.mark.gpu
 
-W, H, SPP = 64, 36, 8
-NQ = 4096
-SKY = (0.6, 0.7, 0.9)
-F_LEAF2 = 256
-F32 = np.float32
-ASSETS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
-
-# csrc/layout.h: the LDS scene image's planes (ART_LDS_NODE_CAP 272, 1024 slots, 512 material entries), tile_lists.h TileReps
-NODE_CAP, SLOT_CAP = 272, 1024
-OFF_SPH = 10 * NODE_CAP * 16
-OFF_MOV = OFF_SPH + 2 * SLOT_CAP * 16
-OFF_REF = OFF_MOV + SLOT_CAP * 8
-OFF_MATIDX = OFF_REF + SLOT_CAP * 4
-OFF_MAT = OFF_MATIDX + SLOT_CAP * 2
-OFF_INVR = OFF_MAT + 512 * 32
-IMAGE_BYTES = OFF_INVR + SLOT_CAP * 8
-REPS_BYTES = 4 + 2 * SLOT_CAP + 12
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.int64)
-
-
-def quant(a):
-    """Multiples of 2^-20: c + d and (c + d) - c of a moving sphere are then exact, so the fresh compile's center1 - center0
-    is the motion the updated scene kept."""
-    return np.round(np.asarray(a, np.float64) * 2.0 ** 20) / 2.0 ** 20
-
-
-def v3(x):
-    return tuple(float(t) for t in x)
+XF_ANGLE, XF_OFFSET = 15.0, np.array([-1.0, 0.5, -2.0])
 
 
 # ------------------------------------------------------------------------------------------------ worlds
 # A world is (S0, D, build): S0 (n, 4) its spheres in compiled order, D (n, 3) the motion center1 - center0 of the moving
 # ones (0 rows otherwise), build(S) the compiled world with spheres S -- the same call sequence for every S, so that
 # material ids agree between A and B.
-def grid_triangles():
-    """A 12 x 12 height field over [-3, 3]^2 with seeded random heights in [0, 1.5]: 288 triangles."""
-    rng = np.random.default_rng(7)
-    xs = np.linspace(-3.0, 3.0, 13)
-    y = rng.uniform(0.0, 1.5, (13, 13))
-    v = lambda i, j: (xs[i], y[i, j], xs[j])  # noqa: E731
-    tris = []
-    for i in range(12):
-        for j in range(12):
-            tris.append((v(i, j), v(i + 1, j), v(i, j + 1)))
-            tris.append((v(i + 1, j), v(i + 1, j + 1), v(i, j + 1)))
-    return np.array(tris, np.float64)
-
-
-def make_sphere(s, d, mat):
-    if d.any():
-        return art.moving_sphere(v3(s[:3]), v3(s[:3] + d), 0.0, 1.0, float(s[3]), mat)
-    return art.sphere(v3(s[:3]), float(s[3]), mat)
-
-
 def sphere_mats():
     return [art.lambertian((0.8, 0.3, 0.3)), art.lambertian(art.checker_texture((0.2, 0.3, 0.1), (0.9, 0.9, 0.9))), art.metal((0.7, 0.6, 0.5), 0.1),
             art.dielectric(1.5), art.diffuse_light((4.0, 4.0, 4.0))]
 
 
 def image_spec():
-    rng = np.random.default_rng(21)
-    s0, d = np.zeros((49, 4)), np.zeros((49, 3))
-    s0[0] = (0.0, -100.0, 0.0, 100.0)
-    k = 1
-    for i in range(8):
-        for j in range(6):
-            r = rng.uniform(0.2, 0.3)
-            s0[k] = (-3.5 + i + rng.uniform(-0.2, 0.2), r, -2.5 + j + rng.uniform(-0.2, 0.2), r)
-            if k % 8 == 3:
-                d[k, 1] = 0.25 + 0.125 * (k % 3)  # y motion over the unit shutter: the image's moving spheres
-            k += 1
-    s0 = quant(s0)
+    s0, d = image_spheres()
 
     def build(s):
         art.reset_scene_rng()
@@ -130,9 +71,6 @@ def mixed_spec():
         w.add(make_sphere(s[21], d[21], mirror))
         return art.hittable_list(native=art.compile_world(w, 0))
     return s0, d, build
-
-
-XF_ANGLE, XF_OFFSET = 15.0, np.array([-1.0, 0.5, -2.0])
 
 
 def xform_media_spec():
@@ -199,35 +137,6 @@ def solid(name, n):
     return keep
 
 
-def frame_camera(name):
-    return {"image": art.camera((0.0, 3.0, 9.0), (0.0, 0.3, 0.0), (0, 1, 0), 40.0, W / H, 0.0, 10.0, 0.0, 1.0),
-            "mixed": art.camera((1.0, 7.0, 12.0), (0.0, 1.5, 0.0), (0, 1, 0), 40.0, W / H, 0.0, 10.0, 0.0, 1.0),
-            "xform_media": art.camera((1.0, 5.0, 13.0), (0.0, 1.0, 0.0), (0, 1, 0), 40.0, W / H, 0.0, 10.0, 0.0, 1.0)}[name]
-
-
-def engine_for(world, cam, background=SKY, **form):
-    eng = art.engine(cam, art.engine_mode.single, width=W, height=H, samples_per_pixel=SPP, seed=5)
-    for k, v in form.items():
-        setattr(eng, k, v)
-    eng.set_scene(world, background)
-    return eng
-
-
-def render(world, cam, background=SKY, **form):
-    eng = engine_for(world, cam, background, **form)
-    img, acc = np.zeros((H, W, 3), np.uint8), np.zeros((H, W, 3), np.float64)
-    eng.run(img, accum=acc)
-    return img, acc, eng.stats
-
-
-def same_render(a, b):
-    return (a[0] == b[0]).all() and (bits(a[1]) == bits(b[1])).all() and a[2]["segments"] == b[2]["segments"]
-
-
-def kernel_of(stats):
-    return stats["kernel_features"], stats["kernel_textures"], stats["kernel_lds_mode"], stats["extend_variant"]
-
-
 def rays_to(points, origin, tm=0.5):
     origin = np.broadcast_to(np.asarray(origin, np.float64), points.shape)
     rays = np.zeros((len(points), 7))
@@ -244,15 +153,6 @@ def random_rays(lo, hi, seed=11):
     rays = np.zeros((NQ, 7))
     rays[:, 0:3], rays[:, 3:6], rays[:, 6] = o, target - o, rng.uniform(0, 1, NQ)
     return rays
-
-
-def same_queries(a, b, rays, **kw):
-    ra, rb = art.query_rays(a, rays, **kw).records, art.query_rays(b, rays, **kw).records
-    oa, ob = art.query_rays(a, rays, any_hit=True, **kw), art.query_rays(b, rays, any_hit=True, **kw)
-    assert ra.shape == (len(rays), 12)
-    assert (bits(ra) == bits(rb)).all(), int((bits(ra) != bits(rb)).any(1).sum())
-    assert (oa == ob).all()
-    return ra
 
 
 def small_box(s):
@@ -276,16 +176,6 @@ def updated_pair(name):
     art.update_spheres(a, s1)
     b = build(s1)
     return a, b, s1, cam, before, bvh_before, image_before
-
-
-def covered_slots(nodes, n_refs):
-    seen = np.zeros(n_refs, bool)
-    for code in nodes["child"].ravel():
-        code = int(code)
-        if code < -1:
-            first, count = ~code & 0xFFFFFF, (~code >> 24) & 0x7F
-            seen[first:first + count] = True
-    return seen
 
 
 # ------------------------------------------------------------------------------------------------ 1. equality with a fresh compile
@@ -445,15 +335,6 @@ def test_the_image_is_the_host_builders_byte_for_byte(gpu):
 
 
 # ------------------------------------------------------------------------------------------------ 4. the boxes are the specified ones
-def conservative_box_np(mn, mx):
-    """refit.h conservative_box in numpy float32 arithmetic."""
-    l, h = mn.astype(F32), mx.astype(F32)
-    l = np.where(l.astype(np.float64) > mn, np.nextafter(l, F32(-np.inf)), l)
-    h = np.where(h.astype(np.float64) < mx, np.nextafter(h, F32(np.inf)), h)
-    pad = F32(1e-6) * np.maximum(np.maximum(np.abs(l), np.abs(h)), h - l) + F32(1e-30)
-    return l - pad, h + pad
-
-
 def sphere_boxes_np(s, d):
     """refit.h sphere_box: c -+ r, or for a moving sphere (unit shutter here) the union of the boxes at t = 0 and t = 1."""
     c, r = s[:, :3], s[:, 3:4]

@@ -5,42 +5,18 @@ a split BVH's duplicated references (dino).  Equality alone would pass a refit t
 only grows, one that keeps stale boxes: rays toward a mesh moved far away (they must hit it, and miss where it was) and a
 numpy restatement of every box of the refitted tree rule those out.  Frames are 64 x 36 x 8, queries 4096 rays."""
 import functools
-import os
 
 import numpy as np
 import pytest
 
 import another_raytracer_amd as art
 from another_raytracer_amd._lib import lib
+from tests.update_common import ASSETS, F_LEAF2, H, NQ, SKY, SPP, W, bits, conservative_box_np, grid_triangles, render, same_queries, same_render
 
 pytestmark = pytest.mark.gpu
 
-W, H, SPP = 64, 36, 8
-NQ = 4096
-SKY = (0.6, 0.7, 0.9)
-F_LEAF2 = 256
-ASSETS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.int64)
-
 
 # ------------------------------------------------------------------------------------------------ meshes and worlds
-def grid_triangles():
-    """A 12 x 12 height field over [-3, 3]^2 with seeded random heights: 288 triangles, no coplanar neighbours."""
-    rng = np.random.default_rng(7)
-    xs = np.linspace(-3.0, 3.0, 13)
-    y = rng.uniform(0.0, 1.5, (13, 13))
-    v = lambda i, j: (xs[i], y[i, j], xs[j])  # noqa: E731
-    tris = []
-    for i in range(12):
-        for j in range(12):
-            tris.append((v(i, j), v(i + 1, j), v(i, j + 1)))
-            tris.append((v(i + 1, j), v(i + 1, j + 1), v(i, j + 1)))
-    return np.array(tris, np.float64)
-
-
 @functools.lru_cache(maxsize=None)
 def mesh(name):
     """P0 of a mesh, read-only: the grid, or the triangles of a builtin scene as scene_triangles gives them."""
@@ -90,18 +66,6 @@ def frame_camera(p_frame):
     return art.camera((c[0] + 0.4 * ext, c[1] + 0.9 * ext, c[2] + 2.2 * ext), tuple(c), (0, 1, 0), 40.0, W / H, 0.0, 10.0, 0.0, 1.0)
 
 
-def render(world, cam, background=SKY):
-    eng = art.engine(cam, art.engine_mode.single, width=W, height=H, samples_per_pixel=SPP, seed=5)
-    eng.set_scene(world, background)
-    img, acc = np.zeros((H, W, 3), np.uint8), np.zeros((H, W, 3), np.float64)
-    eng.run(img, accum=acc)
-    return img, acc, eng.stats
-
-
-def same_render(a, b):
-    return (a[0] == b[0]).all() and (bits(a[1]) == bits(b[1])).all() and a[2]["segments"] == b[2]["segments"]
-
-
 def kernel_of(stats):
     return stats["kernel_features"], stats["kernel_textures"], stats["kernel_lds_mode"]
 
@@ -130,15 +94,6 @@ def random_rays(p, seed=11):
     rays = np.zeros((NQ, 7))
     rays[:, 0:3], rays[:, 3:6], rays[:, 6] = o, target - o, rng.uniform(0, 1, NQ)
     return rays
-
-
-def same_queries(a, b, rays):
-    ra, rb = art.query_rays(a, rays).records, art.query_rays(b, rays).records
-    oa, ob = art.query_rays(a, rays, any_hit=True), art.query_rays(b, rays, any_hit=True)
-    assert ra.shape == (len(rays), 12)
-    assert (bits(ra) == bits(rb)).all(), int((bits(ra) != bits(rb)).any(1).sum())
-    assert (oa == ob).all()
-    return ra
 
 
 EXPECT = {"grid": lambda k, w: k[2] == 1, "cow": lambda k, w: k[2] == 2, "capsule": lambda k, w: k[0] & F_LEAF2,
@@ -309,16 +264,6 @@ def test_loose_triangles_of_an_unmerged_world_are_updated(gpu, options):
 
 
 # ------------------------------------------------------------------------------------------------ 6. the boxes are the specified ones
-def conservative_box_np(mn, mx):
-    """refit.h conservative_box in numpy float32 arithmetic."""
-    f32 = np.float32
-    l, h = mn.astype(f32), mx.astype(f32)
-    l = np.where(l.astype(np.float64) > mn, np.nextafter(l, f32(-np.inf)), l)
-    h = np.where(h.astype(np.float64) < mx, np.nextafter(h, f32(np.inf)), h)
-    pad = f32(1e-6) * np.maximum(np.maximum(np.abs(l), np.abs(h)), h - l) + f32(1e-30)
-    return l - pad, h + pad
-
-
 @pytest.mark.parametrize("name", ["grid", "capsule"])
 def test_the_refitted_boxes_are_the_specified_ones(gpu, name):
     a, _, p1, _, _, (nodes0, refs0) = updated_pair(name)

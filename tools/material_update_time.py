@@ -22,19 +22,10 @@ Prints one JSON line (kept as profiles/material_update_time.json).
 
   python tools/material_update_time.py [--scenes spheres,mixed] [--shape 1920x1080x16] [--runs 15] [--warmup 3]
 """
-import argparse
-import json
-import os
-import sys
-import time
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-from sphere_update_time import SKY, compiled, mixed_scene, spheres_scene, summary  # noqa: E402
+import _update_timing as ut
+from sphere_update_time import mixed_scene, spheres_scene
 
 LAMBERTIAN, METAL, DIELECTRIC, LIGHT = 0, 1, 2, 3
 SOLID = 0
@@ -94,55 +85,26 @@ def new_values(M0, Md, T0, Td, seed=4):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--scenes", default="spheres,mixed")
-    ap.add_argument("--shape", default="1920x1080x16", help="WxHxSPP of the rendered frames")
-    ap.add_argument("--runs", type=int, default=15)
-    ap.add_argument("--warmup", type=int, default=3)
-    args = ap.parse_args()
-
-    import torch
-
-    import another_raytracer_amd as art
-    if art.lib.rt_device_count() < 1:
-        raise SystemExit("material_update_time: no HIP device")
-    W, H, k = (int(x) for x in args.shape.split("x"))
-    result = {"tool": "material_update_time", "runs": args.runs, "warmup": args.warmup, "W": W, "H": H, "spp": k,
-              "clock": {"update_device_ms": "HIP events around each call's kernels, update_materials + update_textures",
-                        "update_wall_ms": "host wall time of the two calls (timing=True: each waits)",
-                        "fresh_compile_upload_ms": "host wall time of rt_graph_compile + the upload", "render": "segments / rt_stats.ms (HIP events)"},
-              "kernel_build_id": art._lib.kernel_build_id(), "scenes": {}}
+    art, torch, args, (W, H, k), result = ut.start("material_update_time", "scenes", "spheres,mixed", 15, {
+        "update_device_ms": "HIP events around each call's kernels, update_materials + update_textures",
+        "update_wall_ms": "host wall time of the two calls (timing=True: each waits)"})
     for name in args.scenes.split(","):
         s0, graph0, (lookfrom, lookat, vfov) = {"spheres": spheres_scene, "mixed": mixed_scene}[name](art)
-        a = compiled(art, graph0(s0))
+        a = ut.compiled(art, graph0(s0))
         (M0, Md), (T0, Td) = art.scene_materials(a), art.scene_textures(a)
         M1, T1 = new_values(M0, Md, T0, Td)
         # the same graph function over the package with V1 in its constructors
         _, graph1, _ = {"spheres": spheres_scene, "mixed": mixed_scene}[name](WithValues(art, M1, T1))
-        cam = art.camera(lookfrom, lookat, (0, 1, 0), vfov, W / H, 0.0, 10.0, 0.0, 1.0)
-
-        def render(world):
-            eng = art.engine(cam, art.engine_mode.single, width=W, height=H, samples_per_pixel=k, seed=1)
-            eng.set_scene(world, SKY)
-            img = np.zeros((H, W, 3), np.uint8)
-            eng.run(img)
-            return img, eng.stats["segments"] / eng.stats["ms"], eng.stats
-
+        render = ut.renderer(art, art.camera(lookfrom, lookat, (0, 1, 0), vfov, W / H, 0.0, 10.0, 0.0, 1.0), (W, H, k))
         has_image = art.scene_lds_image(a) is not None
         img_v0 = render(a)[0]
         dev = [torch.from_numpy(np.array(x)).cuda() for x in (M0, T0, M1, T1)]
         torch.cuda.synchronize()
-        ms = {f: [] for f in ("update_device_ms", "update_wall_ms", "graph_python_ms", "fresh_compile_upload_ms")}
-        rate = {f: [] for f in ("updated", "fresh")}
         kernel = None
+        ms, rate = {}, {}
         for r in range(args.warmup + args.runs):
-            t0 = time.perf_counter()
-            dev_ms = art.update_materials(a, dev[2], timing=True) + art.update_textures(a, dev[3], timing=True)
-            t1 = time.perf_counter()
-            w = graph1(s0)
-            t2 = time.perf_counter()
-            b = compiled(art, w)
-            t3 = time.perf_counter()
+            m, b, w = ut.update_then_fresh(art, lambda: art.update_materials(a, dev[2], timing=True) + art.update_textures(a, dev[3], timing=True),
+                                           lambda: graph1(s0))
             img_a, rate_a, st = render(a)
             img_b, rate_b, _ = render(b)
             assert (img_a == img_b).all(), f"{name}, round {r}: the updated scene's frame differs from the fresh compile's"
@@ -154,28 +116,13 @@ def main():
             torch.cuda.synchronize()
             kernel = [st["kernel_features"], st["kernel_textures"], st["kernel_lds_mode"], st["extend_variant"]]
             del b, w
-            if r < args.warmup:
-                continue
-            for f, v in (("update_device_ms", dev_ms), ("update_wall_ms", 1e3 * (t1 - t0)), ("graph_python_ms", 1e3 * (t2 - t1)),
-                         ("fresh_compile_upload_ms", 1e3 * (t3 - t2))):
-                ms[f].append(v)
-            rate["updated"].append(rate_a)
-            rate["fresh"].append(rate_b)
+            ut.record(args, r, ms, m, rate, {"updated": rate_a, "fresh": rate_b})
         entry = {"materials": int(len(M0)), "textures": int(len(T0)), "metals": int((Md[:, 0] == METAL).sum()), "dielectrics": int((Md[:, 0] == DIELECTRIC).sum()),
                  "solid_colours": int((Td[:, 0] == SOLID).sum()), "lds_image": has_image, "kernel": kernel, "frames_equal_bit_for_bit": True}
-        entry.update({f: summary(v) for f, v in ms.items()})
-        entry["segments_per_ms"] = {f: summary(v) for f, v in rate.items()}
-        entry["update_device_over_fresh"] = entry["update_device_ms"]["median"] / entry["fresh_compile_upload_ms"]["median"]
-        entry["update_wall_over_fresh"] = entry["update_wall_ms"]["median"] / entry["fresh_compile_upload_ms"]["median"]
-        entry["update_is_faster"] = bool(entry["update_wall_ms"]["max"] < entry["fresh_compile_upload_ms"]["min"])
-        sx, sy = entry["segments_per_ms"]["updated"], entry["segments_per_ms"]["fresh"]
-        spread = max(sx["max"] - sx["min"], sy["max"] - sy["min"])
-        entry["render_rate_updated_over_fresh"] = sx["median"] / sy["median"]
-        entry["render_rate_difference_exceeds_spread"] = bool(abs(sx["median"] - sy["median"]) > spread)
-        result["scenes"][name] = entry
+        result["scenes"][name] = ut.finish(entry, ms, rate, [("updated", "fresh", "updated", "")])
         del a
         torch.cuda.empty_cache()
-    print(json.dumps(result))
+    ut.report(result)
 
 
 if __name__ == "__main__":

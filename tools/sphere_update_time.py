@@ -21,20 +21,9 @@ Prints one JSON line (kept as profiles/sphere_update_time.json).
 
   python tools/sphere_update_time.py [--scenes spheres,mixed] [--shape 1920x1080x16] [--runs 15] [--warmup 3]
 """
-import argparse
-import ctypes
-import json
-import os
-import statistics
-import sys
-import time
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-SKY = (0.6, 0.7, 0.9)
+import _update_timing as ut
 
 
 def quant(a):
@@ -93,36 +82,9 @@ def mixed_scene(art):
     return s0, graph, ((c[0] + 0.4 * ext, c[1] + 1.2 * ext, c[2] + 2.4 * ext), tuple(c), 40.0)
 
 
-def compiled(art, w, upload=True):
-    h = art.hittable_list(native=art.compile_world(w, 0))
-    if upload:
-        n = ctypes.c_int64()
-        art._lib.check(art.lib.rt_scene_bvh_get(h._native, None, 0, None, 0, ctypes.byref(n), None), "upload")
-    return h
-
-
-def summary(v):
-    return {"median": statistics.median(v), "min": min(v), "max": max(v)}
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--scenes", default="spheres,mixed")
-    ap.add_argument("--shape", default="1920x1080x16", help="WxHxSPP of the rendered frames")
-    ap.add_argument("--runs", type=int, default=15)
-    ap.add_argument("--warmup", type=int, default=3)
-    args = ap.parse_args()
-
-    import torch
-
-    import another_raytracer_amd as art
-    if art.lib.rt_device_count() < 1:
-        raise SystemExit("sphere_update_time: no HIP device")
-    W, H, k = (int(x) for x in args.shape.split("x"))
-    result = {"tool": "sphere_update_time", "runs": args.runs, "warmup": args.warmup, "W": W, "H": H, "spp": k,
-              "clock": {"update_device_ms": "HIP events around the update's kernels", "update_wall_ms": "host wall time of update_spheres(timing=True)",
-                        "fresh_compile_upload_ms": "host wall time of rt_graph_compile + the upload", "render": "segments / rt_stats.ms (HIP events)"},
-              "kernel_build_id": art._lib.kernel_build_id(), "scenes": {}}
+    art, torch, args, (W, H, k), result = ut.start("sphere_update_time", "scenes", "spheres,mixed", 15, {
+        "update_device_ms": "HIP events around the update's kernels", "update_wall_ms": "host wall time of update_spheres(timing=True)"})
     for name in args.scenes.split(","):
         s0, graph, (lookfrom, lookat, vfov) = {"spheres": spheres_scene, "mixed": mixed_scene}[name](art)
         rng = np.random.default_rng(3)
@@ -131,32 +93,16 @@ def main():
         s1[small, 0] += rng.uniform(-0.5, 0.5, int(small.sum()))
         s1[small, 2] += rng.uniform(-0.5, 0.5, int(small.sum()))
         s1 = quant(s1)
-        cam = art.camera(lookfrom, lookat, (0, 1, 0), vfov, W / H, 0.0, 10.0, 0.0, 1.0)
-
-        def render(world):
-            eng = art.engine(cam, art.engine_mode.single, width=W, height=H, samples_per_pixel=k, seed=1)
-            eng.set_scene(world, SKY)
-            img = np.zeros((H, W, 3), np.uint8)
-            eng.run(img)
-            return img, eng.stats["segments"] / eng.stats["ms"], eng.stats
-
-        a = compiled(art, graph(s0))
+        render = ut.renderer(art, art.camera(lookfrom, lookat, (0, 1, 0), vfov, W / H, 0.0, 10.0, 0.0, 1.0), (W, H, k))
+        a = ut.compiled(art, graph(s0))
         nodes, refs = art.scene_bvh(a)
         has_image = art.scene_lds_image(a) is not None
         t_s0, t_s1 = torch.from_numpy(np.array(s0)).cuda(), torch.from_numpy(s1).cuda()
         torch.cuda.synchronize()
-        ms = {f: [] for f in ("update_device_ms", "update_wall_ms", "graph_python_ms", "fresh_compile_upload_ms")}
-        rate = {f: [] for f in ("refit_moved", "fresh_moved")}
-        equal = True
-        kernel = None
+        equal, kernel = True, None
+        ms, rate = {}, {}
         for r in range(args.warmup + args.runs):
-            t0 = time.perf_counter()
-            dev_ms = art.update_spheres(a, t_s1, timing=True)
-            t1 = time.perf_counter()
-            w = graph(s1)
-            t2 = time.perf_counter()
-            b = compiled(art, w)
-            t3 = time.perf_counter()
+            m, b, w = ut.update_then_fresh(art, lambda: art.update_spheres(a, t_s1, timing=True), lambda: graph(s1))
             img_a, rate_a, st = render(a)
             img_b, rate_b, _ = render(b)
             art.update_spheres(a, t_s0)  # back to S0: the next round's update is this round's
@@ -164,28 +110,13 @@ def main():
             equal = equal and bool((img_a == img_b).all())
             kernel = [st["kernel_features"], st["kernel_textures"], st["kernel_lds_mode"], st["extend_variant"]]
             del b, w
-            if r < args.warmup:
-                continue
-            for f, v in (("update_device_ms", dev_ms), ("update_wall_ms", 1e3 * (t1 - t0)), ("graph_python_ms", 1e3 * (t2 - t1)),
-                         ("fresh_compile_upload_ms", 1e3 * (t3 - t2))):
-                ms[f].append(v)
-            rate["refit_moved"].append(rate_a)
-            rate["fresh_moved"].append(rate_b)
+            ut.record(args, r, ms, m, rate, {"refit_moved": rate_a, "fresh_moved": rate_b})
         entry = {"spheres": int(len(s0)), "bvh_nodes": int(len(nodes)), "leaf_slots": int(len(refs)), "lds_image": has_image, "kernel": kernel,
                  "frames_equal_bit_for_bit": equal}
-        entry.update({f: summary(v) for f, v in ms.items()})
-        entry["segments_per_ms"] = {f: summary(v) for f, v in rate.items()}
-        entry["update_device_over_fresh"] = entry["update_device_ms"]["median"] / entry["fresh_compile_upload_ms"]["median"]
-        entry["update_wall_over_fresh"] = entry["update_wall_ms"]["median"] / entry["fresh_compile_upload_ms"]["median"]
-        entry["update_is_faster"] = bool(entry["update_wall_ms"]["max"] < entry["fresh_compile_upload_ms"]["min"])
-        sx, sy = entry["segments_per_ms"]["refit_moved"], entry["segments_per_ms"]["fresh_moved"]
-        spread = max(sx["max"] - sx["min"], sy["max"] - sy["min"])
-        entry["render_rate_refit_over_fresh"] = sx["median"] / sy["median"]
-        entry["render_rate_difference_exceeds_spread"] = bool(abs(sx["median"] - sy["median"]) > spread)
-        result["scenes"][name] = entry
+        result["scenes"][name] = ut.finish(entry, ms, rate, [("refit_moved", "fresh_moved", "refit", "")])
         del a
         torch.cuda.empty_cache()
-    print(json.dumps(result))
+    ut.report(result)
 
 
 if __name__ == "__main__":
