@@ -34,6 +34,9 @@ enum class Opt : int {
                      // default: off; a group is never less than one view; diagnostic: the results do not depend on it)
     TileLists,       // render.tile_lists: k_paths' batches test a per-tile sphere list instead of walking the tree (tile_lists.h):
                      // 0 off, 1 (default) when a pass holds enough samples per pixel to pay for the table, 2 always
+    AccumOverlap,    // render.accum_overlap: a whole-image k_paths pass runs as two launches and the first one's radiance
+                     // records are summed on a second stream while the second traces (pass_plan.h split_pass): 0 off,
+                     // 1 (default) when the records are large enough to pay for the extra launch, 2 whenever k >= 2
     // multi-GPU
     MultiTimeoutMs,  // multi.timeout_ms: deadline of RCCL init / gather waits (unset: ART_MULTI_TIMEOUT_MS, else 120000;
                      // inf, or anything beyond ~292 years, means no deadline)

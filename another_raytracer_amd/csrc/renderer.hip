@@ -39,12 +39,55 @@ struct Renderer::Impl {
     hipEvent_t ev[2] = {nullptr, nullptr};
     std::vector<ViewRec> view_table;  // rt_render_views: the camera table of the last call, as uploaded
     uint64_t gen = 0, fetched_gen = 0;  // rt_scene_update_* calls so far / the one `flat` was last fetched after
+    // The second stream of a split pass (pass_plan.h split_pass) and its events: fork[0] the head's k_paths launch has
+    // ended, fork[1] the head's sums are in.  Created by the first split.  The stream has the lowest priority, so that
+    // of two dispatches that become ready together -- the tail's k_paths and the head's k_accum -- the path kernel's
+    // blocks are placed first.
+    hipStream_t accum_stream = nullptr;
+    hipEvent_t fork[2] = {nullptr, nullptr};
 
+    void need_accum_stream() {
+        if (!accum_stream) {
+            int least = 0, greatest = 0;
+            HIP_OK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+            HIP_OK(hipStreamCreateWithPriority(&accum_stream, hipStreamNonBlocking, least));
+        }
+        for (auto& e : fork)
+            if (!e) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
     ~Impl() {
         s64.release();
         ws.release();
         for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+        for (auto& e : fork) if (e) (void)hipEventDestroy(e);
+        if (accum_stream) (void)hipStreamDestroy(accum_stream);
         if (own_stream) (void)hipStreamDestroy(own_stream);
+    }
+};
+
+// A split pass between its fork and its join.  join() orders the frame's stream after the second stream's work; an exit
+// that never reaches it (a thrown HIP_OK) waits on the host instead, so the workspace is never handed to the next call
+// while the second stream still reads it.
+struct AccumFork {
+    Renderer::Impl& I;
+    bool open = false;
+    explicit AccumFork(Renderer::Impl& I) : I(I) {}
+    AccumFork(const AccumFork&) = delete;
+    AccumFork& operator=(const AccumFork&) = delete;
+    ~AccumFork() {
+        if (open) (void)hipStreamSynchronize(I.accum_stream);
+    }
+    // after `from`'s work so far, the second stream may run
+    void fork(hipStream_t from) {
+        I.need_accum_stream();
+        HIP_OK(hipEventRecord(I.fork[0], from));
+        open = true;  // (before the wait: from here on the second stream may hold work)
+        HIP_OK(hipStreamWaitEvent(I.accum_stream, I.fork[0], 0));
+    }
+    void join(hipStream_t into) {
+        HIP_OK(hipEventRecord(I.fork[1], I.accum_stream));
+        HIP_OK(hipStreamWaitEvent(into, I.fork[1], 0));
+        open = false;
     }
 };
 
@@ -311,7 +354,8 @@ static bool begin_frame(Frame& f, RenderStats& stats, int spp, bool spread, int 
     f.counter_bytes = f.mega ? 4u * kCounterStride : 4ull * counter_words(p.max_depth);
     f.call.carve(I.ws, carve);
     if (p.flags & RT_PROFILE) {  // (a pixel-list level never needs more passes than k gives)
-        f.marks.reserve(static_cast<size_t>(profile_levels) * f.npasses * (f.mega ? 2 : 3 * p.max_depth));
+        // (a k_paths pass may run as two launches: split_pass)
+        f.marks.reserve(static_cast<size_t>(profile_levels) * f.npasses * (f.variant == EXT_MEGA ? 4 : f.mega ? 2 : 3 * p.max_depth));
         f.mark = [&f]() { f.marks.mark(f.stream); };
     }
     f.call.begin();
@@ -322,21 +366,24 @@ static bool begin_frame(Frame& f, RenderStats& stats, int spp, bool spread, int 
 
 // One pass of g through the variant's kernels: the counters' clear (unless the caller cleared them), then max_depth
 // wavefront bounces, or one persistent launch claiming from counter line `line`.  A pass at max_depth 0 launches
-// nothing and still counts.
-static void run_pass(Frame& f, PassGeom g, int line = 0, bool clear = true) {
+// nothing and still counts.  RT_PROFILE's marks enclose the persistent launch alone.  res_first: the pass's records
+// begin at that record of the workspace's (the tail of a split pass; persistent kernels only).
+static void run_pass(Frame& f, PassGeom g, int line = 0, bool clear = true, size_t res_first = 0) {
+    Work w = f.w;
+    w.res += res_first;
     if (clear) HIP_OK(hipMemsetAsync(f.w.counters, 0, f.counter_bytes, f.stream));
     if (!f.mega) {
-        for (int d = 0; d < f.p.max_depth; ++d) bounce(f.ds, f.variant, f.I.num_cu, f.stream, g, f.cam, f.w, d, f.mark);
+        for (int d = 0; d < f.p.max_depth; ++d) bounce(f.ds, f.variant, f.I.num_cu, f.stream, g, f.cam, w, d, f.mark);
         f.launches += static_cast<uint64_t>(f.p.max_depth);
     } else if (f.p.max_depth > 0) {
         g.chunk = path_chunk(g.P, f.I.num_cu);
         if (f.mark) f.mark();
         if (f.variant == EXT_MEGA) {
-            launch_paths(f.I.num_cu, f.stream, f.ds.view, g, f.cam, f.w, counter(f.w, line, 0, 0));
+            launch_paths(f.I.num_cu, f.stream, f.ds.view, g, f.cam, w, counter(w, line, 0, 0));
             f.kid = KernelId{kFeatSpheres, 0, 3};
         } else {
             f.kid = launch_paths_g(f.ds.features, f.ds.tex_basic, f.ds.tex_bary, f.ds.codes16, f.ds.leaf_shift, f.I.num_cu, f.stream, f.ds.view, g,
-                                   f.cam, f.w, counter(f.w, line, 0, 0));
+                                   f.cam, w, counter(w, line, 0, 0));
         }
         if (f.mark) f.mark();
         ++f.launches;
@@ -407,11 +454,39 @@ static int trace_samples(Frame& f, const RenderBufs& b, const uint32_t* list, ui
     if (b.qsum) HIP_OK(hipMemsetAsync(b.qsum, 0, sizeof(double) * 3 * npix, f.stream));
     const uint32_t spp_t = static_cast<uint32_t>(b.spp_t);
     int done = 0;
+    // a split pass (pass_plan.h split_pass): the head's sums run on the second stream while the tail traces
+    const bool can_split = f.variant == EXT_MEGA && !list && !p.on_pass && !b.qsum;
+    int split_mode = static_cast<int>(opt(Opt::AccumOverlap));
+    if (split_mode == 1 && p.samples_per_pass > 0) split_mode = 0;  // auto keeps a caller's own passes at one launch each
+    AccumFork fork(f.I);
+    const auto sized = [&](PassGeom s, uint32_t first, uint32_t k) {  // samples [first, first + k) of g's pass
+        s.sample_base = g.sample_base + first, s.k = k;
+        s.P = k * s.npix_pad, s.live = k * npix;
+        return s;
+    };
     for (uint32_t sb = 0; sb < spp_t; sb += kk) {
         g.sample_base = sb, g.k = std::min<uint32_t>(kk, spp_t - sb);
         g.P = g.k * g.npix_pad, g.live = g.k * npix;
-        run_pass(f, g);
-        launch_accum(f.stream, g, f.w, b.qsum, spp_t / 4);
+        const PassSplit split = split_pass(g.k, g.npix_pad, split_mode, can_split);
+        if (split.tail == 0) {
+            run_pass(f, g);
+            launch_accum(f.stream, g, f.w, b.qsum, spp_t / 4);
+        } else {
+            run_pass(f, sized(g, 0, split.head));
+            fork.fork(f.stream);
+            // sums continue from the stored value in sample order, launch after launch, as they do pass after pass
+            for (uint32_t s0 = 0; s0 < split.head; s0 += kAccumLaunchSamples) {
+                Work w = f.w;
+                w.res += static_cast<size_t>(s0) * g.npix_pad;
+                launch_accum(f.I.accum_stream, sized(g, s0, std::min(kAccumLaunchSamples, split.head - s0)), w, nullptr, 0);
+            }
+            const size_t tail_first = static_cast<size_t>(split.head) * g.npix_pad;
+            run_pass(f, sized(g, split.head, split.tail), 0, true, tail_first);
+            fork.join(f.stream);
+            Work w = f.w;
+            w.res += tail_first;
+            launch_accum(f.stream, sized(g, split.head, split.tail), w, nullptr, 0);
+        }
         done = static_cast<int>(sb + g.k);
         // progressive snapshot: write_color of the sums so far, with the samples so far
         if (!list && p.on_pass) {

@@ -194,6 +194,10 @@ int rt_device_count(void);
  *   render.tile_lists (1; the batches of 64 camera rays of the LDS-scene path kernel test a per-tile list of the spheres
  *   their 8x8 tile can reach instead of walking the tree: 0 = off, 1 = when a pass holds at least 72 samples per pixel, so
  *   that the table's one launch per rt_render call is below 1 % of it, 2 = always; the frames are identical either way);
+ *   render.accum_overlap (1; a whole-image pass of the LDS-scene path kernel runs as two launches and the first one's
+ *   radiance records are summed on a second stream while the second, the pass's last 128 samples, traces: 0 = off, 1 =
+ *   when those records are at least 8 GiB and samples_per_pass is 0, 2 = whenever a pass holds two samples or more; the
+ *   frames are identical either way; rt_stats.passes and extend_launches count both launches of a split pass);
  *   multi.timeout_ms (the RCCL deadline; inf = none), multi.rccl_blocking (0; 1 = blocking communicators, diagnosis:
  *   gives up the deadline and the error-path protection);
  *   test.fault_workspace_bytes (0 = off; N refuses workspace growth beyond N bytes), test.fault_gather_abort (0; 1 = the
