@@ -132,6 +132,12 @@ SIGNATURES = {
     "rt_scene_textures_get": (ctypes.c_int64, [_P, _P, _P, ctypes.c_int64]),
     "rt_scene_update_materials": (_I, [_P, ctypes.POINTER(rt_update_params), _P, ctypes.c_int64, ctypes.c_int64, _DP]),
     "rt_scene_update_textures": (_I, [_P, ctypes.POINTER(rt_update_params), _P, ctypes.c_int64, ctypes.c_int64, _DP]),
+    "rt_scene_rects_get": (ctypes.c_int64, [_P, _P, _P, ctypes.c_int64]),
+    "rt_scene_boxes_get": (ctypes.c_int64, [_P, _P, _P, ctypes.c_int64]),
+    "rt_scene_objects_get": (ctypes.c_int64, [_P, _P, _P, ctypes.c_int64]),
+    "rt_scene_update_rects": (_I, [_P, ctypes.POINTER(rt_update_params), _P, ctypes.c_int64, ctypes.c_int64, _DP]),
+    "rt_scene_update_boxes": (_I, [_P, ctypes.POINTER(rt_update_params), _P, ctypes.c_int64, ctypes.c_int64, _DP]),
+    "rt_scene_update_objects": (_I, [_P, ctypes.POINTER(rt_update_params), _P, ctypes.c_int64, ctypes.c_int64, _DP]),
     "rt_render": (_I, [_P, ctypes.POINTER(rt_camera), ctypes.POINTER(rt_params), _P, _P, ctypes.POINTER(rt_stats)]),
     "rt_render_progressive": (_I, [_P, ctypes.POINTER(rt_camera), ctypes.POINTER(rt_params), _P, _P, rt_progress_fn, _P,
                                    ctypes.POINTER(rt_stats)]),

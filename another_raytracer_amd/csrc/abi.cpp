@@ -45,6 +45,9 @@ struct rt_scene {
         flat.nodes = now.nodes;
         flat.mats = now.mats;
         flat.texs = now.texs;
+        flat.rects = now.rects;
+        flat.boxes = now.boxes;
+        flat.objs = now.objs;
         synced = renderer->generation();
     }
 };
@@ -223,7 +226,7 @@ size_t rt_scene_dump(const rt_scene* s, char* buf, size_t cap) {
         return 0;
     }
     if (s->updated()) {
-        fail(RT_E_SCENE, "the scene's triangles, spheres, materials or textures were updated (rt_scene_update_triangles, _spheres, _materials, _textures): its object graph no longer describes it");
+        fail(RT_E_SCENE, "the scene was updated (rt_scene_update_triangles, _spheres, _materials, _textures, _rects, _boxes, _objects): its object graph no longer describes it");
         return 0;
     }
     try {
@@ -391,6 +394,66 @@ int rt_scene_update_materials(rt_scene* s, const rt_update_params* u, const doub
 
 int rt_scene_update_textures(rt_scene* s, const rt_update_params* u, const double* t, int64_t first, int64_t n, double* ms) {
     return scene_update(art::UpdateKind::Textures, s, u, t, first, n, ms);
+}
+
+static_assert(art::kUpdateRows[4].width == RT_RECT_DOUBLES && art::kUpdateRows[5].width == RT_BOX_DOUBLES && art::kUpdateRows[6].width == RT_OBJECT_DOUBLES,
+              "art.h's row widths are update_kinds.h's");
+static_assert(RT_OBJ_PRIM == art::OBJ_PRIM && RT_OBJ_BVH == art::OBJ_BVH && RT_OBJ_TRANSLATE == art::OBJ_TRANSLATE && RT_OBJ_ROTATE_Y == art::OBJ_ROTATE_Y &&
+                  RT_OBJ_MEDIUM == art::OBJ_MEDIUM,
+              "art.h's RT_OBJ_* are layout.h's ObjKind");
+
+int64_t rt_scene_rects_get(rt_scene* s, double* values_out, int32_t* desc_out, int64_t cap) {
+    const int64_t count = get_begin(art::UpdateKind::Rects, s, values_out || desc_out, cap);
+    if (count < 0 || (!values_out && !desc_out)) return count;
+    for (int64_t k = 0; k < count; ++k) {
+        const art::RectRec& r = s->flat.rects[static_cast<size_t>(k)];
+        if (values_out) {
+            double* p = values_out + RT_RECT_DOUBLES * k;
+            p[0] = r.a0, p[1] = r.a1, p[2] = r.b0, p[3] = r.b1, p[4] = r.k;
+        }
+        if (desc_out) desc_out[2 * k] = static_cast<int32_t>(r.axis), desc_out[2 * k + 1] = static_cast<int32_t>(r.mat);
+    }
+    return count;
+}
+
+int64_t rt_scene_boxes_get(rt_scene* s, double* values_out, int32_t* desc_out, int64_t cap) {
+    const int64_t count = get_begin(art::UpdateKind::Boxes, s, values_out || desc_out, cap);
+    if (count < 0 || (!values_out && !desc_out)) return count;
+    for (int64_t k = 0; k < count; ++k) {
+        const art::BoxRec& b = s->flat.boxes[static_cast<size_t>(k)];
+        if (values_out)
+            for (int a = 0; a < 3; ++a) values_out[RT_BOX_DOUBLES * k + a] = b.mn[a], values_out[RT_BOX_DOUBLES * k + 3 + a] = b.mx[a];
+        if (desc_out) desc_out[k] = static_cast<int32_t>(b.mat);
+    }
+    return count;
+}
+
+int64_t rt_scene_objects_get(rt_scene* s, double* values_out, int32_t* desc_out, int64_t cap) {
+    const int64_t count = get_begin(art::UpdateKind::Objects, s, values_out || desc_out, cap);
+    if (count < 0 || (!values_out && !desc_out)) return count;
+    for (int64_t k = 0; k < count; ++k) {
+        const art::ObjRec& o = s->flat.objs[static_cast<size_t>(k)];
+        if (values_out) std::memcpy(values_out + RT_OBJECT_DOUBLES * k, o.p, sizeof o.p);
+        if (desc_out) desc_out[4 * k] = o.kind, desc_out[4 * k + 1] = o.a, desc_out[4 * k + 2] = o.b, desc_out[4 * k + 3] = -1;
+    }
+    if (desc_out)
+        for (size_t w = 0; w < s->flat.world.size(); ++w) {
+            const int32_t o = s->flat.world[w];
+            if (o >= 0 && o < count) desc_out[4 * o + 3] = static_cast<int32_t>(w);
+        }
+    return count;
+}
+
+int rt_scene_update_rects(rt_scene* s, const rt_update_params* u, const double* v, int64_t first, int64_t n, double* ms) {
+    return scene_update(art::UpdateKind::Rects, s, u, v, first, n, ms);
+}
+
+int rt_scene_update_boxes(rt_scene* s, const rt_update_params* u, const double* v, int64_t first, int64_t n, double* ms) {
+    return scene_update(art::UpdateKind::Boxes, s, u, v, first, n, ms);
+}
+
+int rt_scene_update_objects(rt_scene* s, const rt_update_params* u, const double* v, int64_t first, int64_t n, double* ms) {
+    return scene_update(art::UpdateKind::Objects, s, u, v, first, n, ms);
 }
 
 int rt_scene_bvh_get(rt_scene* s, void* nodes_out, int64_t node_cap, uint32_t* primrefs_out, int64_t ref_cap, int64_t* n_nodes, int64_t* n_primrefs) {

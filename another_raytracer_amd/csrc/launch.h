@@ -145,6 +145,33 @@ struct AppearanceJob {
 };
 void launch_update_materials(hipStream_t st, const AppearanceJob& j);
 void launch_update_textures(hipStream_t st, const AppearanceJob& j);
+// One rt_scene_update_rects / rt_scene_update_boxes call as k_update_rects / k_update_boxes see it: new values v (5
+// doubles per rect -- a0, a1, b0, b1, k -- or 6 per box -- min xyz, max xyz) for records [first, first + n), written
+// into every array of the uploaded scene that holds one (axis and mat stay).  A scene without a BVH has no slots:
+// n_slots 0, and only the records and obj_prims are written.
+struct RigidJob {
+    const double* v;
+    uint32_t first, n;
+    const uint32_t* primrefs;
+    const uint8_t* slot_pad;
+    const ObjRec* objs;
+    uint32_t n_slots, n_objs;
+    RectRec* rects;                // k_update_rects
+    BoxRec* boxes;                 // k_update_boxes
+    PrimRec80* leaf_prims;
+    PrimRec80* obj_prims;
+    double* slot_box;
+};
+void launch_update_rects(hipStream_t st, const RigidJob& j);
+void launch_update_boxes(hipStream_t st, const RigidJob& j);
+// One rt_scene_update_objects call as k_update_objects sees it: new p (4 doubles each) for objects [first, first + n);
+// a record takes what its kind uses (a translate p[0..2], a rotate_y p[0..1], a medium p[0]; a prim and a BVH nothing)
+struct ObjectJob {
+    const double* v;
+    uint32_t first, n;
+    ObjRec* objs;
+};
+void launch_update_objects(hipStream_t st, const ObjectJob& j);
 // k_refit_level over every level [level_begin[l], level_begin[l + 1]) (refit.h refit_levels), the deepest first
 void launch_refit_levels(hipStream_t st, BvhNode* nodes, uint32_t n_nodes, const double* slot_box, uint32_t n_slots,
                          const std::vector<uint32_t>& level_begin);

@@ -8,6 +8,10 @@
 // rt_scene_update_materials / rt_scene_update_textures: k_update_materials / k_update_textures write the fields a record's
 // type takes, then k_derive_materials refreshes, for every material of the scene, the two copies made of them at upload:
 // the solid colour inlined into a MATF_SOLID record and the image's shading-table entries (lds_image.h).
+// rt_scene_update_rects / rt_scene_update_boxes: k_update_rects / k_update_boxes are k_update_spheres without an image
+// (the records, the leaf-ordered copy, the prim objects' copies, the slot boxes), followed by the levels.
+// rt_scene_update_objects: k_update_objects writes ObjRec::p by the object's kind -- where an instance stands, how it is
+// turned, how dense a medium is; none of those has a box, so nothing is refitted.
 #include "launch.h"
 #include "lds_image.h"
 #include "refit.h"
@@ -132,6 +136,70 @@ __global__ void __launch_bounds__(kRefitBlock) k_derive_materials(AppearanceJob 
     if (j.image) image_put_material(j.image, j.entry[i], m, j.texs);
 }
 
+// (a0, a1, b0, b1, k) into a rect record, (min xyz, max xyz) into a box record; axis and mat stay
+__device__ __forceinline__ void put_rect(RectRec& r, const double* v) { r.a0 = v[0], r.a1 = v[1], r.b0 = v[2], r.b1 = v[3], r.k = v[4]; }
+__device__ __forceinline__ void put_box(BoxRec& x, const double* v) {
+    for (int a = 0; a < 3; ++a) x.mn[a] = v[a], x.mx[a] = v[3 + a];
+}
+
+// k_update_spheres' shape for rects: thread i is leaf slot i, rect first + i and object i at once.  No image: an image
+// scene holds spheres only.
+__global__ void __launch_bounds__(kRefitBlock) k_update_rects(RigidJob j) {
+    const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (i < j.n_slots && !j.slot_pad[i]) {
+        const uint32_t ref = j.primrefs[i];
+        const uint32_t t = primref_index(ref) - j.first;  // (wraps above n for a rect below `first`)
+        if (primref_type(ref) == PRIM_RECT && t < j.n) {
+            RectRec& r = *reinterpret_cast<RectRec*>(j.leaf_prims[i].b);
+            put_rect(r, j.v + 5 * static_cast<size_t>(t));
+            const RectRec now = r;
+            rect_box(now, j.slot_box + 6 * static_cast<size_t>(i));
+        }
+    }
+    if (i < j.n) put_rect(j.rects[j.first + i], j.v + 5 * static_cast<size_t>(i));  // rect first + i: its record
+    if (i < j.n_objs && j.objs[i].kind == OBJ_PRIM) {  // a loose rect of the world, or one under a transform chain
+        const uint32_t ref = static_cast<uint32_t>(j.objs[i].a);
+        const uint32_t t = primref_index(ref) - j.first;
+        if (primref_type(ref) == PRIM_RECT && t < j.n) put_rect(*reinterpret_cast<RectRec*>(j.obj_prims[i].b), j.v + 5 * static_cast<size_t>(t));
+    }
+}
+
+// ... and for boxes (a box under a transform chain, a constant_medium's boundary included, is an OBJ_PRIM object)
+__global__ void __launch_bounds__(kRefitBlock) k_update_boxes(RigidJob j) {
+    const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (i < j.n_slots && !j.slot_pad[i]) {
+        const uint32_t ref = j.primrefs[i];
+        const uint32_t t = primref_index(ref) - j.first;
+        if (primref_type(ref) == PRIM_BOX && t < j.n) {
+            BoxRec& x = *reinterpret_cast<BoxRec*>(j.leaf_prims[i].b);
+            put_box(x, j.v + 6 * static_cast<size_t>(t));
+            const BoxRec now = x;
+            box_box(now, j.slot_box + 6 * static_cast<size_t>(i));
+        }
+    }
+    if (i < j.n) put_box(j.boxes[j.first + i], j.v + 6 * static_cast<size_t>(i));
+    if (i < j.n_objs && j.objs[i].kind == OBJ_PRIM) {
+        const uint32_t ref = static_cast<uint32_t>(j.objs[i].a);
+        const uint32_t t = primref_index(ref) - j.first;
+        if (primref_type(ref) == PRIM_BOX && t < j.n) put_box(*reinterpret_cast<BoxRec*>(j.obj_prims[i].b), j.v + 6 * static_cast<size_t>(t));
+    }
+}
+
+// One thread per record of [first, first + n): p by the object's kind; kind, a and b stay
+__global__ void __launch_bounds__(kRefitBlock) k_update_objects(ObjectJob j) {
+    const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (i >= j.n) return;
+    const double* v = j.v + 4 * static_cast<size_t>(i);
+    ObjRec& o = j.objs[j.first + i];
+    if (o.kind == OBJ_TRANSLATE) {
+        o.p[0] = v[0], o.p[1] = v[1], o.p[2] = v[2];
+    } else if (o.kind == OBJ_ROTATE_Y) {
+        o.p[0] = v[0], o.p[1] = v[1];
+    } else if (o.kind == OBJ_MEDIUM) {
+        o.p[0] = v[0];
+    }
+}
+
 // Four lanes per node of [begin, end), one per child
 __global__ void __launch_bounds__(kRefitBlock) k_refit_level(BvhNode* nodes, uint32_t n_nodes, const double* slot_box, uint32_t n_slots,
                                                              uint32_t begin, uint32_t end) {
@@ -166,6 +234,12 @@ void launch_update_textures(hipStream_t st, const AppearanceJob& j) {
     launch_1d(k_update_textures, j.n, st, j);
     launch_1d(k_derive_materials, j.n_mats, st, j);
 }
+
+void launch_update_rects(hipStream_t st, const RigidJob& j) { launch_1d(k_update_rects, std::max(std::max(j.n_slots, j.n), j.n_objs), st, j); }
+
+void launch_update_boxes(hipStream_t st, const RigidJob& j) { launch_1d(k_update_boxes, std::max(std::max(j.n_slots, j.n), j.n_objs), st, j); }
+
+void launch_update_objects(hipStream_t st, const ObjectJob& j) { launch_1d(k_update_objects, j.n, st, j); }
 
 void launch_refit_levels(hipStream_t st, BvhNode* nodes, uint32_t n_nodes, const double* slot_box, uint32_t n_slots,
                          const std::vector<uint32_t>& level_begin) {

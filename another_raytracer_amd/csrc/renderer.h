@@ -94,7 +94,7 @@ public:
     // the number of tiles, or 0 when render() would build no lists (the scene, the option, the mode or the sample
     // count).  counts may be null (the number only); otherwise it holds at least `cap` >= tiles entries.
     int tile_candidates(const CameraRec& cam, const RenderParams& p, uint16_t* counts, size_t cap);
-    // rt_scene_update_triangles / _spheres / _materials / _textures (update_kinds.h): new values v for records
+    // rt_scene_update_triangles / _spheres / _materials / _textures / _rects / _boxes / _objects (update_kinds.h): new values v for records
     // [first, first + n) of the kind's array in flat(), written into every device array that holds such a record.  device: v is a device pointer
     // read in place on `stream` (null: the scene's own, and the call waits); a host v goes through the workspace: a copy,
     // the kernels, a wait, as query_rays.  ms (may be null: then a device call on the caller's stream returns once
@@ -110,6 +110,12 @@ public:
     //     (k_update_materials, k_update_textures); then every material of the scene gets its copies refreshed
     //     (k_derive_materials): the solid colour inlined into a MATF_SOLID record, and the image's shading-table entries.
     //     Types, links, boxes and the tree stay.  First: with an image, every material's entry code.
+    //   Rects (5 doubles: a0, a1, b0, b1, k), Boxes (6: min xyz, max xyz): the records, their leaf-ordered copies and the
+    //     prim objects' copies (k_update_rects, k_update_boxes); then the same refit.  axis and mat stay.  First: as
+    //     Triangles.  A scene without a BVH has no slots and nothing to refit.
+    //   Objects (4 doubles: ObjRec::p): a record takes what its kind uses -- a translate's offset, a rotate_y's sin and
+    //     cos, a medium's neg_inv_density; a prim and a BVH nothing (k_update_objects).  Nothing is prepared or refitted:
+    //     no box depends on them.
     void update(UpdateKind kind, const double* v, size_t first, size_t n, bool device, void* stream, double* ms);
     // rt_scene_lds_image_get: kLdsImageBytes + sizeof(TileReps), or 0 when the scene has no LDS image; out (may be null:
     // the size only) receives the device's bytes, or with `rebuilt` what build_lds_image makes of current_flat().
@@ -117,7 +123,7 @@ public:
     uint64_t generation() const;
     // flat() with the sphere centres and radii, the triangle vertices, the 24 box floats of every node and the material and
     // texture fields an update can write (a metal's albedo and fuzz, a dielectric's ir, a solid texture's colour, a noise
-    // texture's scale) as the device holds them now (fetched when an update happened since the last fetch; waits for the
+    // texture's scale), a rect's a0, a1, b0, b1, k, a box's min and max and an object's p as the device holds them now (fetched when an update happened since the last fetch; waits for the
     // device).  Node order and child codes are the compiled ones.
     const FlatScene& current_flat();
     // rt_scene_bvh_get: the device's nodes (n_nodes x 128 bytes, as uploaded) and primitive references; either may be

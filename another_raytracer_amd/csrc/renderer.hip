@@ -924,8 +924,8 @@ void Renderer::render_noise_target(const CameraRec& cam, const RenderParams& p, 
 
 // ------------------------------------------------------------------------------------------------ rt_scene_update_*
 // What a scene's first update makes: the f64 box of every leaf slot's primitive from the host records (refit.h; a
-// pad slot of the pair-aligned copy gets the empty box), uploaded once -- after that only k_update_tris writes it --
-// and the level ranges of the node array.
+// pad slot of the pair-aligned copy gets the empty box), uploaded once -- after that only the update kernels of the
+// Refit kinds write it -- and the level ranges of the node array.
 static void prepare_refit(const FlatScene& f, DeviceScene& ds) {
     if (ds.slot_box || ds.slot_refs.empty()) return;
     ds.level_begin = refit_levels(f.nodes, f.objs);
@@ -961,7 +961,8 @@ static void prepare_appearance(const FlatScene& f, DeviceScene& ds) {
 }
 
 // The kind's job struct from the device scene and its launches: the kind's kernel, then for geometry the refit of every
-// box (once a first update made the slot boxes) and, for spheres, the image's box planes from the refitted nodes.  The
+// box (once a first update made the slot boxes) and, for spheres, the image's box planes from the refitted nodes; an
+// appearance kind and the objects kind move no box and return after their kernels.  The
 // arrays build_device_scene uploaded are const in the kernels' view only: the DeviceScene owns them.
 static void enqueue_update(UpdateKind kind, hipStream_t st, const DeviceScene& ds, const double* v, uint32_t first, uint32_t n) {
     const auto& w = ds.view;
@@ -994,6 +995,27 @@ static void enqueue_update(UpdateKind kind, hipStream_t st, const DeviceScene& d
             launch_update_spheres(st, job);
             break;
         }
+        case UpdateKind::Rects:
+        case UpdateKind::Boxes: {
+            RigidJob job{};
+            job.v = v, job.first = first, job.n = n;
+            job.primrefs = w.primrefs, job.slot_pad = ds.slot_pad_dev, job.objs = w.objs;
+            job.n_slots = ds.slot_box ? w.n_primrefs : 0u, job.n_objs = w.n_objs;  // (a scene without a BVH has no slots)
+            job.rects = const_cast<RectRec*>(w.rects);
+            job.boxes = const_cast<BoxRec*>(w.boxes);
+            job.leaf_prims = const_cast<PrimRec80*>(w.leaf_prims);
+            job.obj_prims = const_cast<PrimRec80*>(w.obj_prims);
+            job.slot_box = ds.slot_box;
+            (kind == UpdateKind::Rects ? launch_update_rects : launch_update_boxes)(st, job);
+            break;
+        }
+        case UpdateKind::Objects: {
+            ObjectJob job{};
+            job.v = v, job.first = first, job.n = n;
+            job.objs = const_cast<ObjRec*>(w.objs);
+            launch_update_objects(st, job);
+            return;  // no box depends on an object's parameters
+        }
         default: {
             AppearanceJob job{};
             job.v = v, job.first = first, job.n = n;
@@ -1017,8 +1039,8 @@ void Renderer::update(UpdateKind kind, const double* v, size_t first, size_t n, 
     DeviceScene& ds = I.s64;
     if (n == 0) return;
     if (first + n > update_count(I.flat, kind)) throw std::runtime_error(std::string("update_") + row.nouns + ": range beyond the scene's " + row.nouns);
-    if (row.geometry) prepare_refit(I.flat, ds);
-    else prepare_appearance(I.flat, ds);
+    if (row.cls == UpdateClass::Refit) prepare_refit(I.flat, ds);
+    if (row.cls == UpdateClass::Appearance) prepare_appearance(I.flat, ds);
     Call call(I.own_stream, I.ev, device, stream, ms != nullptr);
     const double* in = nullptr;
     call.carve(I.ws, [&](Carver& c) { in = call.in(c, v, row.width * n); }, 1);  // host values: through the workspace
@@ -1084,6 +1106,22 @@ const FlatScene& Renderer::current_flat() {
         if (t.type == TEX_SOLID) std::memcpy(t.c, texs[k].c, sizeof t.c);
         if (t.type == TEX_NOISE) t.scale = texs[k].scale;
     }
+    std::vector<RectRec> rects(I.flat.rects.size());
+    if (!rects.empty()) HIP_OK(hipMemcpy(rects.data(), ds.view.rects, sizeof(RectRec) * rects.size(), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < rects.size(); ++k) {
+        RectRec& r = I.flat.rects[k];
+        r.a0 = rects[k].a0, r.a1 = rects[k].a1, r.b0 = rects[k].b0, r.b1 = rects[k].b1, r.k = rects[k].k;
+    }
+    std::vector<BoxRec> boxes(I.flat.boxes.size());
+    if (!boxes.empty()) HIP_OK(hipMemcpy(boxes.data(), ds.view.boxes, sizeof(BoxRec) * boxes.size(), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < boxes.size(); ++k) {
+        std::memcpy(I.flat.boxes[k].mn, boxes[k].mn, sizeof boxes[k].mn);
+        std::memcpy(I.flat.boxes[k].mx, boxes[k].mx, sizeof boxes[k].mx);
+    }
+    // of an object, p only: the device's b may be a pair-aligned leaf code, the host's addresses the compiled slots
+    std::vector<ObjRec> objs(I.flat.objs.size());
+    if (!objs.empty()) HIP_OK(hipMemcpy(objs.data(), ds.view.objs, sizeof(ObjRec) * objs.size(), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < objs.size(); ++k) std::memcpy(I.flat.objs[k].p, objs[k].p, sizeof objs[k].p);
     std::vector<BvhNode> nodes(I.flat.nodes.size());
     if (!nodes.empty()) HIP_OK(hipMemcpy(nodes.data(), ds.view.nodes, sizeof(BvhNode) * nodes.size(), hipMemcpyDeviceToHost));
     // the 24 box floats only: the device's leaf codes address the pair-aligned slots, the host's the compiled ones

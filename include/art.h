@@ -42,6 +42,10 @@
  *                                                                  rt_scene_update_materials, rt_scene_update_textures
  *                                                                    (new colours, fuzz, ir, noise scale; every device
  *                                                                    copy of them refreshed, the image's shading table too)
+ *                                                                  rt_scene_update_rects, rt_scene_update_boxes (new
+ *                                                                    extents, BVH boxes refitted), rt_scene_update_objects
+ *                                                                    (where a translate / rotate_y instance stands and how
+ *                                                                    it is turned, a constant_medium's density)
  *   (none: engine_mode::adaptive interpolates     engine.h:96-333  rt_render_guides + rt_denoise, or rt_render_denoised
  *    untraced pixels; there is no denoiser)                          (first-hit guides, variance-guided a-trous filter)
  *   (none: tracer_constants::samples_per_pixel is   tracer_constants.h:12  rt_render_noise_target (per-pixel sample counts:
@@ -82,7 +86,10 @@ extern "C" {
  * rt_scene_triangles_get, rt_scene_bvh_get (new vertices for a compiled scene's triangles and a BVH refit on the device);
  * rt_scene_update_spheres, rt_scene_spheres_get, rt_scene_lds_image_get (new centres and radii for its spheres);
  * rt_scene_update_materials, rt_scene_update_textures, rt_scene_materials_get, rt_scene_textures_get, RT_MATERIAL_DOUBLES,
- * RT_TEXTURE_DOUBLES, RT_MAT_*, RT_TEX_* (new values for its materials and textures). */
+ * RT_TEXTURE_DOUBLES, RT_MAT_*, RT_TEX_* (new values for its materials and textures); rt_scene_update_rects,
+ * rt_scene_update_boxes, rt_scene_update_objects, rt_scene_rects_get, rt_scene_boxes_get, rt_scene_objects_get,
+ * RT_RECT_DOUBLES, RT_BOX_DOUBLES, RT_OBJECT_DOUBLES, RT_OBJ_* (new extents for its rects and boxes, new offsets, angles
+ * and densities for its translate, rotate_y and constant_medium objects). */
 #define RT_ABI_VERSION 5
 
 /* return codes */
@@ -240,7 +247,8 @@ typedef struct rt_update_params {   /* zero-initialised = host buffer, scene's s
  * orders them), then a refit of every BVH box on the device -- a cloth step, a morph target, a mesh whose vertices come
  * out of an optimiser -- where the only other way to move a vertex is a new graph, a full SAH build and a new upload.
  * Materials (rt_scene_update_materials / _textures change their values), texture coordinates and topology stay; spheres
- * move by rt_scene_update_spheres (below), rects and boxes cannot be updated; rt_multi is not covered.
+ * move by rt_scene_update_spheres, rects, boxes and instances by rt_scene_update_rects / _boxes / _objects (below);
+ * rt_multi is not covered.
  * Equality with a fresh compile: let scene A be compiled from triangles P0 and updated to P1, and scene B be compiled
  *   from the same graph with P1.  Every later call on A gives the bits it gives on B: rt_render, rt_render_views,
  *   rt_query_rays (all 12 doubles, prim included: the compiled triangle order is the same), rt_radiance_rays, and the
@@ -281,8 +289,8 @@ int64_t rt_scene_spheres_get(rt_scene* scene, double* s_out, int64_t cap);
  * image (the spheres-only scenes: the benchmark scene among them), of the image -- bouncing spheres, a particle or
  * physics step, a light or probe sphere an optimiser moves -- without a new graph, SAH build and upload.
  * What stays: materials and flags, and a moving sphere's motion (center1 - center0, time0, time1): it translates with
- *   its motion, which is also what keeps an image scene on its kernel.  Topology stays; rects and boxes cannot be
- *   updated; rt_multi is not covered.
+ *   its motion, which is also what keeps an image scene on its kernel.  Topology stays; rects, boxes and instances
+ *   have calls of their own (rt_scene_update_rects below); rt_multi is not covered.
  * Everything else is rt_scene_update_triangles' contract with "sphere" for "triangle": scene A compiled with spheres S0
  *   and updated to S1 gives, in every later call, the bits scene B compiled from the same graph with S1 gives --
  *   rt_render in every variant, rt_render_views, rt_query_rays (all 12 doubles), rt_radiance_rays, rt_render_guides,
@@ -351,6 +359,62 @@ int64_t rt_scene_textures_get(rt_scene* scene, double* params_out, int32_t* desc
  *   any of a row's doubles, used or ignored.  A device buffer is not inspected.  n = 0 is RT_OK and touches nothing. */
 int rt_scene_update_materials(rt_scene* scene, const rt_update_params* u, const double* m, int64_t first, int64_t n, double* ms);
 int rt_scene_update_textures(rt_scene* scene, const rt_update_params* u, const double* t, int64_t first, int64_t n, double* ms);
+
+/* ---- rigid scenes: rects, boxes and the objects that place them (translate, rotate_y, constant_medium) ----
+ * The Cornell box, the Cornell smoke box, the simple-light scene and the Next-Week final scene are made of these.
+ * Indices: rects and boxes are numbered in compiled order, the order they are met walking the world list (a box under
+ *   translate(rotate_y(...)) or inside a constant_medium included).  An object index is an index into the compiled
+ *   object list: the world list walked in order, where a wrapper is numbered AFTER what it wraps -- for
+ *   constant_medium(translate(rotate_y(box))) the box's prim object k, the rotate_y k + 1, the translate k + 2, the medium
+ *   k + 3 -- and a run of consecutive world entries that world merging made one BVH is one object.  Only world-level
+ *   objects and what they wrap are objects; primitives inside a bvh_node are not.
+ * Getters, as rt_scene_materials_get: the count; either out pointer may be NULL, one that is given holds cap >= count
+ *   rows.  values_out rows: RT_RECT_DOUBLES (a0, a1, b0, b1, k -- for an xy_rect x0, x1, y0, y1, k; xz_rect x0, x1, z0,
+ *   z1, k; yz_rect y0, y1, z0, z1, k), RT_BOX_DOUBLES (min xyz, max xyz) or RT_OBJECT_DOUBLES (the object's four
+ *   parameter doubles p: a translate's offset xyz in p[0..2]; a rotate_y's sin and cos of its angle in p[0..1]; a
+ *   constant_medium's -1 / density in p[0]; what a kind does not use is 0).  desc_out rows: a rect's {axis (0 xy_rect,
+ *   1 xz_rect, 2 yz_rect), material index}; a box's {material index}; an object's {RT_OBJ_* kind, a, b, world slot}: a
+ *   is a prim's primitive reference (type:2 | index:30; type 2 a rect, 3 a box), a BVH's root node, a translate's, a
+ *   rotate_y's and a medium's child object; b a medium's phase material, a BVH's hoisted-leaf code or -1; world slot the
+ *   object's place in the world list, or -1 for an object that another one wraps. */
+#define RT_RECT_DOUBLES   5
+#define RT_BOX_DOUBLES    6
+#define RT_OBJECT_DOUBLES 4
+#define RT_OBJ_PRIM      0
+#define RT_OBJ_BVH       1
+#define RT_OBJ_TRANSLATE 2
+#define RT_OBJ_ROTATE_Y  3
+#define RT_OBJ_MEDIUM    4
+int64_t rt_scene_rects_get(rt_scene* scene, double* values_out, int32_t* desc_out, int64_t cap);
+int64_t rt_scene_boxes_get(rt_scene* scene, double* values_out, int32_t* desc_out, int64_t cap);
+int64_t rt_scene_objects_get(rt_scene* scene, double* values_out, int32_t* desc_out, int64_t cap);
+/* rt_scene_update_rects / rt_scene_update_boxes: new extents for rects / boxes [first, first + n), rows as the getters
+ * give them -- a wall, the ceiling light, a box's size -- then the refit of every BVH box, as for triangles.  axis and
+ * material stay.  Every device copy follows: the record, its copy in a BVH leaf, the copy of a loose primitive of the
+ * world or of one under a transform chain (a constant_medium's boundary included).
+ * rt_scene_update_objects: new parameters for objects [first, first + n), rows as rt_scene_objects_get gives them.  What
+ * a record takes from its row, by its kind:
+ *   RT_OBJ_TRANSLATE   p[0..2], the offset
+ *   RT_OBJ_ROTATE_Y    p[0..1], sin and cos of the angle: to get the bits a compile gives, sin(d * pi / 180.0) and
+ *                      cos(d * pi / 180.0) of libm for an angle of d degrees (hittable.cpp:27-29)
+ *   RT_OBJ_MEDIUM      p[0], -1 / density (constant_medium.h:14)
+ *   RT_OBJ_PRIM / RT_OBJ_BVH   nothing
+ *   Ignored fields are left untouched, so a get followed by an update changes no bit.  Kinds and links never change.  A
+ *   transformed object has no box anywhere -- a hit transforms the ray and tests the child -- so moving or turning an
+ *   instance, a whole bvh_node mesh under translate(rotate_y(...)) included, refits nothing: it is one small launch, and
+ *   the child's tree is the one a fresh compile builds.
+ * Everything else is rt_scene_update_spheres' contract: scene A compiled with values V0 and updated to V1 gives, in
+ *   every later call, the bits scene B compiled from the same graph call sequence with V1 gives, up to the exact-t ties
+ *   any two trees can differ in (rects and boxes; an objects update keeps the very tree B has); A's rt_stats.kernel_*
+ *   and extend_variant do not change.  rt_update_params, streams and waiting, ordering, the blocking upload at the first
+ *   call, ms and the host copies (the getters and rt_scene_save fetch from the device first; rt_scene_dump refuses an
+ *   updated scene) are as there.  rt_multi is not covered.
+ * RT_E_INVALID, before any device work: the rows of rt_scene_update_triangles; in a host buffer a non-finite value in
+ *   any of a row's doubles, used or ignored.  No other rule (the reference's constructors check none either: a rect with
+ *   a0 > a1 is what it is at compile).  A device buffer is not inspected.  n = 0 is RT_OK and touches nothing. */
+int rt_scene_update_rects(rt_scene* scene, const rt_update_params* u, const double* v, int64_t first, int64_t n, double* ms);
+int rt_scene_update_boxes(rt_scene* scene, const rt_update_params* u, const double* v, int64_t first, int64_t n, double* ms);
+int rt_scene_update_objects(rt_scene* scene, const rt_update_params* u, const double* v, int64_t first, int64_t n, double* ms);
 
 /* ---- render (engine::run; the engine_mode is in rt_params.flags: RT_ADAPTIVE, RT_PARALLEL_IMAGES, or neither for
  * single and parallel_stripes, which compute the same image) ----

@@ -296,6 +296,33 @@ inline void update_textures(const scene& world, const double* t, std::int64_t fi
                             double* ms = nullptr) {
     detail::scene_update(rt_scene_update_textures, "update_textures", world, t, first, n, flags, stream, ms);
 }
+// A compiled world's rects, boxes and objects (rt_scene_rects_get / _boxes_get / _objects_get): RT_RECT_DOUBLES (a0, a1,
+// b0, b1, k), RT_BOX_DOUBLES (min xyz, max xyz) and RT_OBJECT_DOUBLES (the parameters p: a translate's offset, a
+// rotate_y's sin and cos, a constant_medium's -1 / density) per row in compiled order; desc (optional) receives the rows
+// {axis, mat} / {mat} / {kind, a, b, world slot}.  update_rects / update_boxes write new extents for rows
+// [first, first + n) and refit the BVH boxes; update_objects moves, turns or thins an instance without any refit
+// (rt_scene_update_rects).
+inline std::vector<double> scene_rects(const scene& world, std::vector<std::int32_t>* desc = nullptr) {
+    return detail::scene_get(rt_scene_rects_get, "scene_rects", world, RT_RECT_DOUBLES, desc, 2);
+}
+inline std::vector<double> scene_boxes(const scene& world, std::vector<std::int32_t>* desc = nullptr) {
+    return detail::scene_get(rt_scene_boxes_get, "scene_boxes", world, RT_BOX_DOUBLES, desc, 1);
+}
+inline std::vector<double> scene_objects(const scene& world, std::vector<std::int32_t>* desc = nullptr) {
+    return detail::scene_get(rt_scene_objects_get, "scene_objects", world, RT_OBJECT_DOUBLES, desc, 4);
+}
+inline void update_rects(const scene& world, const double* v, std::int64_t first, std::int64_t n, std::int32_t flags = 0, void* stream = nullptr,
+                         double* ms = nullptr) {
+    detail::scene_update(rt_scene_update_rects, "update_rects", world, v, first, n, flags, stream, ms);
+}
+inline void update_boxes(const scene& world, const double* v, std::int64_t first, std::int64_t n, std::int32_t flags = 0, void* stream = nullptr,
+                         double* ms = nullptr) {
+    detail::scene_update(rt_scene_update_boxes, "update_boxes", world, v, first, n, flags, stream, ms);
+}
+inline void update_objects(const scene& world, const double* v, std::int64_t first, std::int64_t n, std::int32_t flags = 0, void* stream = nullptr,
+                           double* ms = nullptr) {
+    detail::scene_update(rt_scene_update_objects, "update_objects", world, v, first, n, flags, stream, ms);
+}
 
 // The engine with a runtime image size (the reference fixes W, H, C at compile time: engine<W,H,C> below); samples
 // per pixel and max depth are the reference's tracer_constants (tracer_constants.h:12-13) as arguments with the same
