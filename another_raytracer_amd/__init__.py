@@ -24,7 +24,9 @@ triangles with a BVH refit on the device (animated or optimised meshes): update_
 for its spheres: update_spheres(world, s) -- see deform.py.  New values for its materials and textures (colours, fuzz,
 ir, noise scale): update_materials(world, m), update_textures(world, t) -- see appearance.py.  New extents for its rects
 and boxes, and new offsets, angles and densities for its translate, rotate_y and constant_medium objects (rigid animation
-without a refit): update_rects, update_boxes, update_objects -- see rigid.py.
+without a refit): update_rects, update_boxes, update_objects -- see rigid.py.  The exact gradient of radiance_rays'
+radiance with respect to the solid texture colours, the metal albedos and the background: radiance_grad(world, rays,
+weights), render_grad, and the torch operation differentiable_radiance -- see grad.py.
 All compute runs in libart.so (HIP, gfx950) behind include/art.h.
 """
 from ._lib import RTError, get_option, lib, set_option  # noqa: F401  (fails loudly when libart.so is missing)
@@ -42,11 +44,12 @@ from .rigid import (  # noqa: F401
     OBJ_BVH, OBJ_MEDIUM, OBJ_PRIM, OBJ_ROTATE_Y, OBJ_TRANSLATE, medium_density, rotation, scene_boxes, scene_objects, scene_rects, update_boxes,
     update_objects, update_rects,
 )
+from .grad import differentiable_radiance, radiance_grad, render_grad  # noqa: F401
 from . import imageio  # noqa: F401
 
 __all__ = [
     "RTError", "set_option", "get_option", "camera", "denoise", "engine", "engine_mode", "tracer_constants", "scene", "scene_alias", "scene_manager",
-    "query_rays", "radiance_rays", "camera_rays", "render_views", "scene_triangles", "update_triangles", "scene_bvh", "scene_spheres", "update_spheres", "scene_lds_image", "scene_materials", "scene_textures", "update_materials", "update_textures", "scene_rects", "scene_boxes", "scene_objects", "update_rects", "update_boxes", "update_objects", "rotation", "medium_density",
+    "query_rays", "radiance_rays", "radiance_grad", "render_grad", "differentiable_radiance", "camera_rays", "render_views", "scene_triangles", "update_triangles", "scene_bvh", "scene_spheres", "update_spheres", "scene_lds_image", "scene_materials", "scene_textures", "update_materials", "update_textures", "scene_rects", "scene_boxes", "scene_objects", "update_rects", "update_boxes", "update_objects", "rotation", "medium_density",
     "OBJ_PRIM", "OBJ_BVH", "OBJ_TRANSLATE", "OBJ_ROTATE_Y", "OBJ_MEDIUM", "HitRecords", "compile_world", "hittable_list", "bvh_node", "sphere", "moving_sphere", "triangle", "xy_rect", "xz_rect", "yz_rect", "box",
     "translate", "rotate_y", "constant_medium", "lambertian", "metal", "dielectric", "diffuse_light", "solid_color",
     "checker_texture", "noise_texture", "image_texture", "barycentric_image_texture", "mesh", "random_double", "reset_scene_rng", "imageio", "save_scene",

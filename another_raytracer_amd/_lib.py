@@ -144,6 +144,7 @@ SIGNATURES = {
     "rt_trace_rays": (_I, [_P, _P, ctypes.c_int64, ctypes.c_int32, _P, _P]),
     "rt_query_rays": (_I, [_P, ctypes.POINTER(rt_query_params), _P, _P, ctypes.c_int64, _P, _P]),
     "rt_radiance_rays": (_I, [_P, ctypes.POINTER(rt_radiance_params), _P, _P, ctypes.c_int64, _P, ctypes.POINTER(rt_stats)]),
+    "rt_radiance_grad": (_I, [_P, ctypes.POINTER(rt_radiance_params), _P, _P, _P, ctypes.c_int64, _P, _P, _P, _P, ctypes.POINTER(rt_stats)]),
     "rt_camera_rays": (_I, [ctypes.POINTER(rt_camera), ctypes.POINTER(rt_params), ctypes.c_uint32, _I, _P, _P]),
     "rt_tile_candidates": (_I, [_P, ctypes.POINTER(rt_camera), ctypes.POINTER(rt_params), _P, ctypes.c_int64]),
     "rt_render_views": (_I, [_P, ctypes.POINTER(rt_camera), _P, ctypes.c_int32, ctypes.POINTER(rt_params), _P, _P, ctypes.POINTER(rt_stats)]),

@@ -626,6 +626,41 @@ int rt_radiance_rays(rt_scene* s, const rt_radiance_params* q, const double* ray
     });
 }
 
+int rt_radiance_grad(rt_scene* s, const rt_radiance_params* q, const double* rays, const uint64_t* rng, const double* weights, int64_t n,
+                     double* radiance, double* grad_textures, double* grad_materials, double* grad_background, rt_stats* stats) {
+    if (!s || !q) return fail(RT_E_INVALID, "rt_radiance_grad: scene and params must be non-NULL");
+    if (n < 0 || n > (int64_t(1) << 30)) return fail(RT_E_INVALID, "rt_radiance_grad: n must be in [0, 2^30]");
+    if (q->flags & ~(RT_OUT_DEVICE | RT_GLOBAL_SCENE)) return fail(RT_E_INVALID, "rt_radiance_grad takes RT_OUT_DEVICE and RT_GLOBAL_SCENE only");
+    if (q->spp < 0) return fail(RT_E_INVALID, "rt_radiance_grad: spp must be >= 1 (0 is taken as 1)");
+    if (q->max_depth < 1) return fail(RT_E_INVALID, "rt_radiance_grad: max_depth must be >= 1");
+    if (q->stream && !(q->flags & RT_OUT_DEVICE)) return fail(RT_E_INVALID, "rt_radiance_grad: stream needs RT_OUT_DEVICE (host buffers run on the scene's own stream)");
+    const int64_t spp = q->spp > 0 ? q->spp : 1;
+    if (static_cast<uint64_t>(n) * static_cast<uint64_t>(spp) > art::kMaxPassSlots)
+        return fail(RT_E_INVALID, "rt_radiance_grad: n * spp = " + std::to_string(n * spp) + " exceeds kMaxPassSlots = 2^31 paths per call: chunk the "
+                                  "rays with id_base, or the samples with sample_base (gradients of chunks add)");
+    if (!rng && (q->id_base > (uint64_t(1) << 32) || q->id_base + static_cast<uint64_t>(n) > (uint64_t(1) << 32)))
+        return fail(RT_E_INVALID, "rt_radiance_grad: id_base + n must be <= 2^32 (stream ids are 32 bits)");
+    if (n == 0) return RT_OK;
+    if (!rays || !weights) return fail(RT_E_INVALID, "rt_radiance_grad: rays and weights must be non-NULL");
+    if (!radiance && !grad_textures && !grad_materials && !grad_background) return RT_OK;
+    return guard(RT_E_DEVICE, [&] {
+        art::RadianceParams rp;
+        rp.spp = static_cast<int>(spp), rp.max_depth = q->max_depth, rp.sample_base = q->sample_base;
+        rp.seed = q->seed, rp.id_base = rng ? 0 : q->id_base;
+        rp.device = (q->flags & RT_OUT_DEVICE) != 0, rp.global_scene = (q->flags & RT_GLOBAL_SCENE) != 0;
+        rp.stream = q->stream;
+        for (int c = 0; c < 3; ++c) rp.background[c] = q->background[c];
+        art::RenderStats st;
+        s->device_renderer().radiance_grad(rp, rays, rng, weights, static_cast<size_t>(n), radiance, grad_textures, grad_materials, grad_background,
+                                           stats ? &st : nullptr);
+        if (stats) {
+            fill_stats(st, stats);
+            stats->extend_variant = stats->kernel_lds_mode = -1;
+        }
+        return RT_OK;
+    });
+}
+
 int rt_render_views(rt_scene* s, const rt_camera* cams, const uint64_t* seeds, int32_t nviews, const rt_params* p, uint8_t* out_rgb8,
                     double* out_accum, rt_stats* stats) {
     if (!s || !cams || !p) return fail(RT_E_INVALID, "rt_render_views: scene, cams and params must be non-NULL");

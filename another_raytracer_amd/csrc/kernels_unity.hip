@@ -4,6 +4,7 @@
 #include "k_paths.hip"
 #include "k_paths_g_mesh.hip"
 #include "radiance_rays.hip"
+#include "radiance_grad.hip"
 #include "tile_lists.hip"
 #include "refit.hip"
 #include "device_scene.hip"

@@ -62,6 +62,8 @@ struct RadianceJob {
 // The persistent path kernel over the job's paths with `background` on a miss (flags: RT_GLOBAL_SCENE), then the per-ray
 // sums when job.res is set.
 void launch_radiance_rays(const DeviceScene& ds, int flags, int num_cu, hipStream_t st, const RadianceJob& job, uint32_t n, const double background[3]);
+// k_radiance_sum alone: radiance[i] = +0.0 + the spp records of ray i in sample order (rt_radiance_grad's sums)
+void launch_radiance_sum(hipStream_t st, const ResRec* res, uint32_t n, uint32_t spp, double* radiance);
 // One launch of rt_render_views as its kernels see it: a group of whole views of one W x H x spp frame.  Path
 // p = ((v * npix + pixel) * spp + s) of P = views * npix * spp <= kMaxPassSlots, pixel = ly * W + lx (row-major: p is
 // also the index of the path's record, and p / spp the pixel's place in the group's sums).
@@ -86,6 +88,38 @@ struct ViewsJob {
 // The persistent path kernel over the job's paths with `background` on a miss (flags: RT_GLOBAL_SCENE), then the sums
 // of the job's npixels = views * npix pixels when job.res is set.
 void launch_radiance_views(const DeviceScene& ds, int flags, int num_cu, hipStream_t st, const ViewsJob& job, uint32_t npixels, const double background[3]);
+// radiance_grad.hip
+// One vertex of a path as k_radiance_grad records it where the path scatters, for the walk back from the path's end:
+// P = the throughput before the vertex (P_j), a = its attenuation (a_j), row = the accumulator row the attenuation came
+// from (kGradNoRow: none).  Vertex j of the lane with grid-wide index g is verts[j * lanes + g].
+struct GradVertex {
+    double P[3], a[3];
+    uint32_t row, pad[3];
+};
+static_assert(sizeof(GradVertex) == 64, "GradVertex is one 64-B line");
+constexpr uint32_t kGradNoRow = 0xFFFFFFFFu;
+constexpr uint32_t kGradRowLimbs = 10;   // a row of the accumulator: 3 colours x 3 limbs (grad_fixed.h), then the NaN flag
+constexpr uint32_t kGradMaxCopies = 64;  // copies of the accumulator table, one per block index modulo the count
+// One rt_radiance_grad call as its kernels see it: rt_radiance_rays' job (radiance and res may both be null: no radiance
+// asked for), the adjoints and the accumulators.  Rows: texture t is row t, material m row n_texs + m, the background
+// row n_texs + n_mats; rows = n_texs + n_mats + 1.
+struct GradJob {
+    RadianceJob path;
+    const double* weights;         // n x 3
+    GradVertex* verts;             // lanes x max(max_depth - 1, 1) records
+    unsigned long long* acc;       // copies x rows x kGradRowLimbs, zeroed before the launch; null (and verts): radiance only
+    uint32_t rows, copies, n_texs;
+    uint32_t lanes;                // grid blocks x block size
+};
+// The persistent grid of the call's kernel (blocks of kBlock lanes): every block the CUs hold at once, or fewer when the
+// job has fewer paths.  The workspace is sized by it.
+uint32_t radiance_grad_grid(const DeviceScene& ds, int num_cu, uint32_t P, uint32_t stack);
+// The path kernel over `grid` blocks (job.lanes = grid * kBlock) with `background` on a miss, the per-ray sums when
+// job.path.res is set, then k_grad_finish: the accumulators, summed over the copies and rounded once, into the colour
+// columns of grad_textures (n_texs x 4), grad_materials (n_mats x 5) and grad_background (3); the other columns +0.0.
+// Any of the three may be null.
+void launch_radiance_grad(const DeviceScene& ds, hipStream_t st, const GradJob& job, uint32_t grid, uint32_t n, const double background[3],
+                          uint32_t n_mats, double* grad_textures, double* grad_materials, double* grad_background);
 // rt_camera_rays: entry (ly * W + lx) * g.k + j = cam_ray of local pixel (lx, ly), sample g.sample_base + j (rng may be null)
 void launch_camera_rays(hipStream_t st, const PassGeom& g, const CameraRec& cam, double* rays, uint64_t* rng);
 // k_paths.hip

@@ -171,6 +171,9 @@ static void launch_radiance_job(const DeviceScene& ds, int flags, int num_cu, hi
 void launch_radiance_rays(const DeviceScene& ds, int flags, int num_cu, hipStream_t st, const RadianceJob& job, uint32_t n, const double background[3]) {
     launch_radiance_job(ds, flags, num_cu, st, job, n, background);
 }
+void launch_radiance_sum(hipStream_t st, const ResRec* res, uint32_t n, uint32_t spp, double* radiance) {
+    hipLaunchKernelGGL(k_radiance_sum, dim3((n + 255) / 256), dim3(256), 0, st, res, n, spp, radiance);
+}
 void launch_radiance_views(const DeviceScene& ds, int flags, int num_cu, hipStream_t st, const ViewsJob& job, uint32_t npixels, const double background[3]) {
     launch_radiance_job(ds, flags, num_cu, st, job, npixels, background);
 }

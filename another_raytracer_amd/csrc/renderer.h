@@ -69,6 +69,13 @@ public:
     // the claim counter and the per-path records come from the workspace either way.  stats (may be null: then a device
     // call on the caller's stream returns once enqueued) receives segments, primary and ms.
     void radiance_rays(const RadianceParams& p, const double* rays, const uint64_t* rng, size_t n, double* radiance, RenderStats* stats);
+    // rt_radiance_grad: radiance_rays' paths with the adjoint weights (n x 3), and the gradient of sum_i <weights[i],
+    // radiance[i]> in the row layouts of the texture and material getters plus the background's three doubles (art.h).
+    // radiance and the three gradient buffers may each be null.  Buffers and stream as radiance_rays.  The workspace holds,
+    // beside radiance_rays' parts, the accumulator table, copies x (textures + materials + 1) x 80 bytes with copies =
+    // min(grid blocks, 64), and the vertex records, grid lanes x max(max_depth - 1, 1) x 64 bytes.
+    void radiance_grad(const RadianceParams& p, const double* rays, const uint64_t* rng, const double* weights, size_t n, double* radiance,
+                       double* grad_textures, double* grad_materials, double* grad_background, RenderStats* stats);
     // rt_render_views: nviews whole frames of p's width x height x spp, view v through cams[v] with seed seeds[v] (seeds
     // null: p.seed), each equal to render()'s bit for bit.  out_rgb (nviews x H x W x 3 bytes) and out_acc (optional, the
     // f64 sums) are host buffers, or with RT_OUT_DEVICE device buffers written in place on p.stream; the camera table,

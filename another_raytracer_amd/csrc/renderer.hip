@@ -115,7 +115,7 @@ struct Call {
     bool device = false, timed = false, wait = true, sizing = false;
     hipStream_t st = nullptr;
     hipEvent_t* ev = nullptr;
-    struct Copy { void* dst; const void* src; size_t bytes; } outs[3];
+    struct Copy { void* dst; const void* src; size_t bytes; } outs[4];
     int nouts = 0;
 
     Call() = default;
@@ -736,6 +736,61 @@ void Renderer::radiance_rays(const RadianceParams& p, const double* rays, const 
     launch_radiance_rays(ds, p.global_scene ? RT_GLOBAL_SCENE : 0, I.num_cu, st, job, static_cast<uint32_t>(n), p.background);
     call.end();
     call.finish(job.segments).fill(stats, P, 1, static_cast<int>(spp));  // (a device call on the caller's stream without stats returns enqueued)
+}
+
+void Renderer::radiance_grad(const RadianceParams& p, const double* rays, const uint64_t* rng, const double* weights, size_t n, double* radiance,
+                             double* grad_textures, double* grad_materials, double* grad_background, RenderStats* stats) {
+    upload();
+    Impl& I = *impl_;
+    const DeviceScene& ds = I.s64;
+    if (n == 0) return;
+    const uint32_t spp = static_cast<uint32_t>(std::max(1, p.spp));
+    const uint64_t P = static_cast<uint64_t>(n) * spp;
+    if (n > (1u << 30) || P > kMaxPassSlots) throw std::runtime_error("too many rays or paths");
+    Call call(I.own_stream, I.ev, p.device, p.stream, stats != nullptr);
+    hipStream_t st = call.st;
+    const size_t T = I.flat.texs.size(), M = I.flat.mats.size();
+    GradJob job{};
+    RadianceJob& path = job.path;
+    path.stack = stack_rows(ds.max_stack);
+    const uint32_t grid = radiance_grad_grid(ds, I.num_cu, static_cast<uint32_t>(P), path.stack);
+    job.lanes = grid * static_cast<uint32_t>(kBlock);
+    job.rows = static_cast<uint32_t>(T + M + 1), job.n_texs = static_cast<uint32_t>(T);
+    job.copies = std::min(grid, kGradMaxCopies);
+    // workspace: rt_radiance_rays' parts, then the accumulator table's copies (copies x rows x 80 B) and the vertex
+    // records (lanes x max(max_depth - 1, 1) x 64 B)
+    const size_t acc_limbs = static_cast<size_t>(job.copies) * job.rows * kGradRowLimbs;
+    const size_t nverts = static_cast<size_t>(job.lanes) * static_cast<size_t>(std::max(p.max_depth - 1, 1));
+    double *d_gt = nullptr, *d_gm = nullptr, *d_gb = nullptr;
+    const bool grads = grad_textures || grad_materials || grad_background;  // none: the kernel records and adds nothing
+    call.carve(I.ws, [&](Carver& c) {
+        path.next = c.take<uint32_t>(kCounterStride);
+        path.segments = c.take<unsigned long long>(1);
+        path.res = c.take<ResRec>(P, spp > 1 && radiance);
+        job.acc = c.take<unsigned long long>(acc_limbs, grads);
+        job.verts = c.take<GradVertex>(nverts, grads);
+        path.rays = call.in(c, rays, 7 * n);
+        path.rng = call.in(c, rng, P);
+        job.weights = call.in(c, weights, 3 * n);
+        path.radiance = call.out(c, radiance, 3 * n);
+        d_gt = call.out(c, grad_textures, RT_TEXTURE_DOUBLES * T);
+        d_gm = call.out(c, grad_materials, RT_MATERIAL_DOUBLES * M);
+        d_gb = call.out(c, grad_background, 3);
+    });
+    if (spp == 1 || !radiance) path.res = nullptr;
+    path.P = static_cast<uint32_t>(P), path.spp = spp, path.chunk = path_chunk(path.P, I.num_cu);
+    path.sample_base = p.sample_base, path.id_base = static_cast<uint32_t>(p.id_base);
+    path.max_depth = p.max_depth;
+    path.seed_mix = splitmix64(p.seed);
+    path.fd_spp = FastDiv::make(spp);
+    HIP_OK(hipMemsetAsync(path.next, 0, sizeof(uint32_t), st));
+    HIP_OK(hipMemsetAsync(path.segments, 0, sizeof(unsigned long long), st));
+    if (!grads) job.acc = nullptr, job.verts = nullptr;
+    else HIP_OK(hipMemsetAsync(job.acc, 0, sizeof(unsigned long long) * acc_limbs, st));
+    call.begin();
+    launch_radiance_grad(ds, st, job, grid, static_cast<uint32_t>(n), p.background, static_cast<uint32_t>(M), d_gt, d_gm, d_gb);
+    call.end();
+    call.finish(path.segments).fill(stats, P, 1, static_cast<int>(spp));
 }
 
 void Renderer::render_views(const CameraRec* cams, const uint64_t* seeds, size_t nviews, const RenderParams& p, uint8_t* out_rgb, double* out_acc,

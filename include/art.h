@@ -89,7 +89,8 @@ extern "C" {
  * RT_TEXTURE_DOUBLES, RT_MAT_*, RT_TEX_* (new values for its materials and textures); rt_scene_update_rects,
  * rt_scene_update_boxes, rt_scene_update_objects, rt_scene_rects_get, rt_scene_boxes_get, rt_scene_objects_get,
  * RT_RECT_DOUBLES, RT_BOX_DOUBLES, RT_OBJECT_DOUBLES, RT_OBJ_* (new extents for its rects and boxes, new offsets, angles
- * and densities for its translate, rotate_y and constant_medium objects). */
+ * and densities for its translate, rotate_y and constant_medium objects); rt_radiance_grad (the exact gradient of
+ * rt_radiance_rays' radiance with respect to the solid texture colours, the metal albedos and the background). */
 #define RT_ABI_VERSION 5
 
 /* return codes */
@@ -515,6 +516,43 @@ typedef struct rt_radiance_params { /* zero-initialised + max_depth = host buffe
 } rt_radiance_params;
 int rt_radiance_rays(rt_scene* scene, const rt_radiance_params* q, const double* rays, const uint64_t* rng, int64_t n, double* radiance,
                      rt_stats* stats);
+/* rt_radiance_grad (additive since ABI 5): rt_radiance_rays' paths, and the gradient of
+ *   phi = sum_i <weights[i], radiance[i]>
+ * with respect to every solid texture colour, every metal albedo and the background -- one call whatever the number of
+ * colours, measured at 1.4 to 4.3 times rt_radiance_rays on the same paths.  _ray_color has no Russian roulette and no scatter direction depends on a colour, so
+ * with a fixed seed the radiance is a polynomial in these colours and the gradient below is its exact derivative.
+ * rays, rng, n, every field of q, stats, the limits, the host / device buffer rules and the stream rules are
+ *   rt_radiance_rays'.  weights (n x 3 f64) is the adjoint d loss / d radiance[i]; it applies to each of ray i's spp
+ *   paths.  radiance (may be NULL) receives the bits rt_radiance_rays writes, and stats the same segment count.
+ * Outputs, each of which may be NULL: grad_textures (T x RT_TEXTURE_DOUBLES) and grad_materials (M x
+ *   RT_MATERIAL_DOUBLES) in the row layout of rt_scene_textures_get / rt_scene_materials_get, grad_background (3); so
+ *   params -= lr * grad followed by rt_scene_update_* is a descent step.  Only the three colour columns are written with
+ *   sums, and a row is non-zero only for an RT_TEX_SOLID texture or an RT_MAT_METAL material: the scale, fuzz and ir
+ *   columns and the rows of every other type are +0.0.
+ * Definition (w = weights[i], * the component-wise f64 product, each product rounded as written): a path scatters at
+ *   vertices 0 .. k-1 with attenuations a_0 .. a_{k-1}, then ends at a diffuse_light with emission E, at a miss with E =
+ *   background, or with nothing (the depth ran out, or the material absorbed): such a path adds to no row.
+ *     P_0 = (1, 1, 1), P_{j+1} = P_j * a_j          (the renderer's throughput, in the order it multiplies it)
+ *     Q_{k-1} = E,     Q_{j-1} = a_j * Q_j
+ *     the end of the path adds  w * P_k             to the row E came from, or to grad_background;
+ *     vertex j adds             (w * P_j) * Q_j     to the row a_j came from (skipped, being zero, when E is (0, 0, 0)).
+ *   The row of a lambertian, isotropic or diffuse_light value is the solid texture it resolved to -- directly, or
+ *   through checker levels; the row of a metal's is the metal's material row; a dielectric's attenuation and a noise or
+ *   image value have no row.
+ * Accumulation is exact, so the gradient's bits depend on neither the device, the grid nor the order of the rays: each
+ *   f64 contribution c becomes the integer trunc(c * 2^96) (its magnitude truncated towards zero: |c| < 2^-96 adds
+ *   nothing), the integers are summed in 192 bits with integer atomics, and each sum is rounded to f64 once, to nearest
+ *   even.  A contribution that is not finite or has |c| >= 2^56 turns its row's three colours to NaN.
+ * Workspace (the scene's grow-only one, as rt_radiance_rays'): beside that call's parts, the accumulators, copies x (T + M
+ *   + 1) x 80 bytes with copies = min(blocks of the grid, 64), and a 64-byte record per scatter vertex, lanes of the grid
+ *   x max(max_depth - 1, 1) x 64 bytes -- about 12 MiB per unit of max_depth on a 256-CU device.  A refused allocation
+ *   is RT_E_DEVICE, and the next call allocates again.  With all three gradient outputs NULL the call records and adds
+ *   nothing and needs neither: it is rt_radiance_rays on an HBM-scene kernel.
+ * Scenes updated by rt_scene_update_*: the call reads the device's current values.
+ * RT_E_INVALID, before any device work: every case of rt_radiance_rays (radiance may be NULL here), and weights NULL
+ *   with n > 0.  n = 0, or all four outputs NULL, is RT_OK and touches nothing. */
+int rt_radiance_grad(rt_scene* scene, const rt_radiance_params* q, const double* rays, const uint64_t* rng, const double* weights, int64_t n,
+                     double* radiance, double* grad_textures, double* grad_materials, double* grad_background, rt_stats* stats);
 /* rt_camera_rays (additive since ABI 5): rt_render's own camera rays as data -- the starting point of a custom camera, and
  * what makes rt_radiance_rays checkable against rt_render.  Entry (ly * width + lx) * k + j of rays_out (7 doubles) and
  * rng_out (one PCG state; may be NULL) holds the ray of local pixel (lx, ly), sample sample_base + j, and the generator's

@@ -174,6 +174,25 @@ inline void radiance_rays(const scene& world, const double* rays, std::int64_t n
     for (int k = 0; k < 3; ++k) q.background[k] = o.background.e[k];
     check(rt_radiance_rays(world.objects.get(), &q, rays, rng, n, radiance, stats), "radiance_rays");
 }
+// radiance_rays' paths with the adjoint weights (n * 3 doubles) and the exact gradient of sum_i <weights[i], radiance[i]>
+// with respect to the solid texture colours, the metal albedos and the background (rt_radiance_grad): grad_textures
+// (T x RT_TEXTURE_DOUBLES) and grad_materials (M x RT_MATERIAL_DOUBLES) in the getters' row layout, grad_background (3);
+// radiance and each gradient buffer may be nullptr.
+inline void radiance_grad(const scene& world, const double* rays, const double* weights, std::int64_t n, double* radiance, double* grad_textures,
+                          double* grad_materials, double* grad_background, const radiance_options& o = {}, const std::uint64_t* rng = nullptr,
+                          rt_stats* stats = nullptr) {
+    rt_radiance_params q{};
+    q.flags = o.flags;
+    q.spp = o.spp;
+    q.max_depth = o.max_depth;
+    q.sample_base = o.sample_base;
+    q.seed = o.seed;
+    q.id_base = o.id_base;
+    q.stream = o.stream;
+    for (int k = 0; k < 3; ++k) q.background[k] = o.background.e[k];
+    check(rt_radiance_grad(world.objects.get(), &q, rays, rng, weights, n, radiance, grad_textures, grad_materials, grad_background, stats),
+          "radiance_grad");
+}
 // The renderer's own camera rays as data (rt_camera_rays): entry (y * width + x) * k + j of rays_out (7 doubles) and
 // rng_out (may be nullptr) is the ray render_engine starts at pixel (x, y) for sample sample_base + j with `seed`, and the
 // PCG state after the camera's draws -- so the in-order sum of radiance_rays over a pixel's entries is that pixel's sum.
