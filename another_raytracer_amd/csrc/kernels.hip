@@ -719,6 +719,10 @@ static KernelId launch_paths_g_ft(int num_cu, hipStream_t st, const DevScene& S,
     // LM 1 also for a scene without BVH nodes (the earth scene: one sphere object): its world and objects in LDS and no
     // LM 0 suspend machinery (which spilled the earth's textured kernel)
     if (lds_m <= kPathsGLdsCap) {
+        // no LM 1 instantiation of the F_LEAF2 kernels: leaves are pair-aligned only when some leaf starts past slot 8190
+        // (build_device_scene: leaf16_ok fails), and 8191 primitive references of kLm1TriBytes each are 896 KiB
+        if constexpr ((F & F_LEAF2) != 0) throw std::runtime_error("internal: pair-aligned leaves in a scene that fits the LDS");
+        else {
         // the camera-ray rings (triangle-free kernels) when they fit too; otherwise the lanes generate their own rays
         const size_t lds_r = lds_m + paths_g_ring_bytes(kBlockM);
         PassGeom gr = g;
@@ -726,6 +730,7 @@ static KernelId launch_paths_g_ft(int num_cu, hipStream_t st, const DevScene& S,
         // after a segment or two, so most lanes start a path every round and the ring only adds LDS traffic (-1.4 %)
         gr.lds_ring = (paths_g_ring(F, 1) && S.n_nodes > 0 && lds_r <= kPathsGLdsCap) ? 1u : 0u;
         return go(std::integral_constant<int, 1>{}, kBlockM, gr.lds_ring ? lds_r : lds_m, S, gr);
+        }
     }
     // too large for LM 1: as many of the first (top-level) nodes as fit beside the stacks
     const size_t head = align128(lm_head);

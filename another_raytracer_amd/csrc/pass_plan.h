@@ -32,6 +32,12 @@ constexpr PassPlan plan_passes(uint64_t slot_target, int samples_per_pass, uint3
 }
 // A pixel list's slots per sample (the list padded to whole waves) and its samples per pass in a workspace of Pmax slots.
 constexpr uint32_t list_pad(uint32_t nlist) { return (nlist + 63u) & ~63u; }
+// Words of adaptive mode's four level lists over nsq big squares (at most 4 / 12 / 48 / 80 entries of every square's 144
+// pixels), each padded to whole 64-entry batches behind the 64-word line of its count.  More than the frame's pixels
+// while a level's padding shows: 2 squares (24 x 12) need 704 words, not 288 + 256.
+constexpr uint32_t adaptive_list_words(uint32_t nsq) {
+    return 4u * 64u + list_pad(4u * nsq) + list_pad(12u * nsq) + list_pad(48u * nsq) + list_pad(80u * nsq);
+}
 constexpr uint32_t list_pass_samples(uint32_t spp, uint32_t Pmax, uint32_t nlist) {
     return std::max<uint32_t>(1, std::min<uint32_t>(spp, Pmax / std::max<uint32_t>(list_pad(nlist), 64u)));
 }

@@ -520,7 +520,7 @@ static void adaptive_device_counted(Frame& f, const RenderBufs& b, uint32_t coun
         lists[L] = at + 64;  // the count word at lists[L][-1]
         at = lists[L] + list_pad(caps[L]);
     }
-    HIP_OK(hipMemsetAsync(b.ad_lists, 0, 4 * f.local_pix + 4 * 4 * 64, f.stream));  // every count 0
+    HIP_OK(hipMemsetAsync(b.ad_lists, 0, 4ull * adaptive_list_words(b.nsq), f.stream));  // every count 0
     HIP_OK(hipMemsetAsync(b.ad_work, 0xFF, sizeof(int32_t) * 3 * f.local_pix, f.stream));  // the reference's -1 frame
     launch_adapt_corners(f.stream, lists[0], p.width, b.sqx, b.nsq);
     // one slot counter line per level (counter(w, level, 0, 0): the wavefront variants' depth lines, unused here),
@@ -590,7 +590,7 @@ void Renderer::render(const CameraRec& cam, const RenderParams& p, uint8_t* out_
         f.w.pool = c.take<char>(pool_bytes(f.variant, I.num_cu));
         tile_tab = c.take<TileRec>(f.g.npix_pad / 64u, !adaptive && tile_lists_wanted(f.ds, f.variant, f.k));
         b.ad_work = c.take<int32_t>(3 * f.local_pix, adaptive);
-        b.ad_lists = c.take<uint32_t>(f.local_pix + 4 * 64, adaptive);
+        b.ad_lists = c.take<uint32_t>(adaptive_list_words(static_cast<uint32_t>(f.local_pix / (kBig * kBig))), adaptive);
         b.ad_f0 = c.take<uint8_t>(21 * (f.local_pix / (kBig * kBig)), adaptive);  // 1 + 4 + 16 flags per big square
         b.ad_count = c.take<uint32_t>(1, adaptive);
     })) return;

@@ -236,10 +236,44 @@ uint64_t reference_bvh_nodes(uint64_t n) {
     if (n <= 2) return 1;
     return 1 + reference_bvh_nodes(n / 2) + reference_bvh_nodes(n - n / 2);
 }
+namespace {
+// bvh.cpp:3-42 replayed for its leaf order alone: one random_int(0,2) per node in pre-order; a span of 2 orders its pair
+// with the node's comparator (box minimum at time 0 on the drawn axis, bvh.h:30-39), a larger span std::sorts its
+// range with it and splits at the median.  Every node of the reference sorts a copy of its parent's vector, but only
+// inside its own range, so one shared vector gives the same permutation.  The product's own tree is built by the
+// compiler from `items`; this order is what the canonical dump lists, and a reader that rebuilds a tree from it
+// (oracle/restate.cpp) gets the reference's shape.
+void reference_leaf_order(SceneGraph& g, std::vector<int>& objects, size_t start, size_t end, std::vector<int>& out) {
+    const int axis = g.rng.i(0, 2);
+    auto cmp = [&g, axis](int a, int b) {
+        AABBd ba, bb;
+        g.bounding_box(a, 0, 0, ba);
+        g.bounding_box(b, 0, 0, bb);
+        return ba.mn[axis] < bb.mn[axis];
+    };
+    const size_t span = end - start;
+    if (span == 1) {
+        out.push_back(objects[start]);
+    } else if (span == 2) {
+        const bool in_order = cmp(objects[start], objects[start + 1]);
+        out.push_back(objects[in_order ? start : start + 1]);
+        out.push_back(objects[in_order ? start + 1 : start]);
+    } else {
+        std::sort(objects.begin() + static_cast<std::ptrdiff_t>(start), objects.begin() + static_cast<std::ptrdiff_t>(end), cmp);
+        const size_t mid = start + span / 2;
+        reference_leaf_order(g, objects, start, mid, out);
+        reference_leaf_order(g, objects, mid, end, out);
+    }
+}
+}  // namespace
 int SceneGraph::bvh(std::vector<int> items) {
     if (items.empty()) throw std::runtime_error("bvh over an empty list");
-    rng.skip(reference_bvh_nodes(items.size()));  // bvh.cpp:9: random_int(0,2) in every node constructor
+    AABBd probe;
+    for (int it : items)
+        if (!bounding_box(it, 0, 1, probe)) throw std::runtime_error("bvh item without a bounding box");
     Node n = make_node(N_BVH);
+    std::vector<int> sorted = items;
+    reference_leaf_order(*this, sorted, 0, sorted.size(), n.leaf_order);  // draws bvh.cpp:9's random_int(0,2) of every node
     n.items = std::move(items);
     n.t0 = 0;
     n.t1 = 1;
@@ -649,7 +683,7 @@ struct Dumper {
             case N_BVH: {
                 std::string r = "{\"type\":\"bvh\",\"nodes\":" + std::to_string(reference_bvh_nodes(n.items.size())) + ",\"box\":[" +
                                 V(n.bbox.mn) + "," + V(n.bbox.mx) + "],\"items\":[";
-                for (size_t i = 0; i < n.items.size(); ++i) r += (i ? ",\n" : "\n") + obj(n.items[i]);
+                for (size_t i = 0; i < n.leaf_order.size(); ++i) r += (i ? ",\n" : "\n") + obj(n.leaf_order[i]);
                 return r + "]}";
             }
             case N_TRANSLATE: return "{\"type\":\"translate\",\"offset\":" + V(n.a) + ",\"child\":" + obj(n.child) + "}";

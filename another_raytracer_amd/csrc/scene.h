@@ -92,6 +92,7 @@ struct Node {
     int child = -1;           // translate / rotate_y / medium boundary
     double neg_inv_density = 0;
     std::vector<int> items;   // list / bvh
+    std::vector<int> leaf_order;  // bvh: items in the leaf order of the reference's tree (the dump lists them so)
 };
 
 inline Node make_node(NodeType t) {
@@ -144,7 +145,7 @@ struct SceneGraph {
 // (SURVEY Q8).  asset_dir holds cow.tris / dino.tris / earthmap.rgb.  Throws std::runtime_error.
 void build_builtin_scene(SceneGraph& g, const std::string& name, const std::string& asset_dir);
 
-// Canonical JSON dump, same schema as oracle/ref_harness `dump` (BVH items in construction order).
+// Canonical JSON dump, same schema as oracle/ref_harness `dump` (BVH items in the reference tree's leaf order).
 std::string dump_scene(const SceneGraph& g);
 
 // Reference-BVH node count for n items (bvh.cpp:3-42): the number of random_int draws bvh() replays.

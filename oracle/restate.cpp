@@ -23,12 +23,17 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <cctype>
+#include <climits>
 #include <limits>
+#include <map>
 #include <memory>
+#include <mutex>
 #include <random>
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include <zlib.h>
@@ -579,9 +584,397 @@ void mesh_scene(Scene& s, Rng& rng, const std::string& asset, const std::string&
     s.world.push_back(s.medium(boundary, .0001, V3(1, 1, 1)));
 }
 
+// ------------------------------------------------------------------------------------------------ dump loader
+// A scene the oracle did not build: the canonical dump (orc_dump below, rt_scene_dump of the product: one schema) read
+// back into Scene / Obj / Mat / Tex.  The dump is canonical, so the reader is strict: keys in the dumpers' order, no
+// escapes in strings, whitespace only between tokens.  Every defect throws (the orc_* entries turn that into
+// orc_last_error); no read passes the end of the text.  Texels are not in a dump: orc_register_image supplies them.
+uint64_t fnv1a(const unsigned char* p, size_t n);
+std::string dump_obj(const Scene& s, int idx);
+
+struct ImageKey {
+    int w, h, bpp;
+    uint64_t hash;
+    bool operator<(const ImageKey& o) const { return std::tie(w, h, bpp, hash) < std::tie(o.w, o.h, o.bpp, o.hash); }
+};
+std::mutex g_images_mutex;
+std::map<ImageKey, Image> g_images;  // orc_register_image
+
+constexpr int kDumpMaxDepth = 64;  // nesting of objects and textures; the deepest builtin (translate(rotate_y(bvh(sphere)))) has 6
+
+bool is_dump(const char* scene) {  // first non-blank character '{'
+    while (*scene == ' ' || *scene == '\t' || *scene == '\r' || *scene == '\n') ++scene;
+    return *scene == '{';
+}
+
+struct DumpReader {
+    Scene& s;
+    const char* p;
+    const char* const begin;
+    const char* const end;
+    int depth = 0;
+    std::map<ImageKey, int> images;    // registry key -> index in s.images (a textured mesh shares one image)
+    std::map<uint64_t, int> perlins;   // table hash -> index in s.perlins (objects sharing one noise texture)
+
+    DumpReader(Scene& sc, const std::string& text) : s(sc), p(text.data()), begin(text.data()), end(text.data() + text.size()) {}
+
+    [[noreturn]] void fail(const std::string& what) const {
+        throw std::runtime_error("scene dump: " + what + " at byte " + std::to_string(p - begin));
+    }
+    void ws() {
+        while (p < end && (*p == ' ' || *p == '\n' || *p == '\t' || *p == '\r')) ++p;
+    }
+    bool peek(char c) {
+        ws();
+        return p < end && *p == c;
+    }
+    void expect(char c) {
+        ws();
+        if (p >= end) fail(std::string("truncated, expected '") + c + "'");
+        if (*p != c) fail(std::string("expected '") + c + "'");
+        ++p;
+    }
+    std::string str() {
+        expect('"');
+        const char* b = p;
+        while (p < end && *p != '"') {
+            if (*p == '\\' || static_cast<unsigned char>(*p) < 0x20) fail("unsupported character in a string");
+            ++p;
+        }
+        if (p >= end) fail("truncated string");
+        return std::string(b, p++);
+    }
+    void key(const char* name) {
+        ws();
+        if (p >= end) fail(std::string("truncated, missing key \"") + name + "\"");
+        if (*p != '"') fail(std::string("missing key \"") + name + "\"");
+        const char* at = p;
+        if (str() != name) { p = at; fail(std::string("missing key \"") + name + "\""); }
+        expect(':');
+    }
+    void next_key(const char* name) { expect(','); key(name); }
+    double num() {
+        ws();
+        if (p < end && *p == '"') {
+            const std::string v = str();
+            if (v == "inf") return kInf;
+            if (v == "-inf") return -kInf;
+            fail("bad number \"" + v + "\"");
+        }
+        char tok[48];
+        size_t n = 0;
+        while (p < end && n + 1 < sizeof tok && (std::isdigit(static_cast<unsigned char>(*p)) || *p == '-' || *p == '+' || *p == '.' || *p == 'e' || *p == 'E'))
+            tok[n++] = *p++;
+        tok[n] = 0;
+        if (n == 0) fail(p >= end ? "truncated, expected a number" : "expected a number");
+        char* stop = nullptr;
+        const double v = std::strtod(tok, &stop);
+        if (stop != tok + n || std::isnan(v)) fail(std::string("bad number ") + tok);
+        return v;
+    }
+    int integer(int lo, int hi, const char* what) {
+        const double v = num();
+        if (!(v >= lo && v <= hi) || v != std::floor(v)) fail(std::string(what) + " out of range");
+        return static_cast<int>(v);
+    }
+    bool boolean() {
+        ws();
+        if (end - p >= 4 && std::memcmp(p, "true", 4) == 0) { p += 4; return true; }
+        if (end - p >= 5 && std::memcmp(p, "false", 5) == 0) { p += 5; return false; }
+        fail("expected true or false");
+    }
+    // a JSON array of exactly n numbers ("wrong array length" otherwise)
+    void nums(double* out, int n) {
+        expect('[');
+        for (int i = 0; i < n; ++i) {
+            if (i) { if (peek(']')) fail("wrong array length"); expect(','); }
+            if (peek(']')) fail("wrong array length");
+            out[i] = num();
+        }
+        if (peek(',')) fail("wrong array length");
+        expect(']');
+    }
+    V3 vec() {
+        double v[3];
+        nums(v, 3);
+        return V3(v[0], v[1], v[2]);
+    }
+    AABB aabb() {
+        AABB b;
+        expect('[');
+        b.mn = vec();
+        if (peek(']')) fail("wrong array length");
+        expect(',');
+        b.mx = vec();
+        if (peek(',')) fail("wrong array length");
+        expect(']');
+        return b;
+    }
+    std::string open() {  // {"type":"..."
+        if (++depth > kDumpMaxDepth) fail("nesting deeper than " + std::to_string(kDumpMaxDepth));
+        expect('{');
+        key("type");
+        return str();
+    }
+    void close() {
+        expect('}');
+        --depth;
+    }
+
+    int image() {  // after "type":"image"
+        ImageKey k;
+        next_key("w"); k.w = integer(1, 65536, "image width");
+        next_key("h"); k.h = integer(1, 65536, "image height");
+        next_key("bpp"); k.bpp = integer(3, 4, "image bpp");
+        next_key("fnv1a");
+        const std::string hex = str();
+        char* stop = nullptr;
+        k.hash = std::strtoull(hex.c_str(), &stop, 16);
+        if (hex.size() != 16 || *stop) fail("bad image hash \"" + hex + "\"");
+        auto it = images.find(k);
+        if (it != images.end()) return it->second;
+        std::lock_guard<std::mutex> lock(g_images_mutex);
+        auto reg = g_images.find(k);
+        if (reg == g_images.end())
+            fail("image " + std::to_string(k.w) + "x" + std::to_string(k.h) + "x" + std::to_string(k.bpp) + " fnv1a " + hex +
+                 " is not registered (orc_register_image)");
+        s.images.push_back(reg->second);
+        return images[k] = static_cast<int>(s.images.size()) - 1;
+    }
+    int tex() {
+        const std::string type = open();
+        Tex t{T_SOLID};
+        if (type == "solid") {
+            next_key("c"); t.c = vec();
+        } else if (type == "checker") {
+            t.k = T_CHECKER;
+            next_key("even"); t.even = tex();
+            next_key("odd"); t.odd = tex();
+        } else if (type == "noise") {
+            t.k = T_NOISE;
+            next_key("scale"); t.scale = num();
+            auto pn = std::make_unique<Perlin>();
+            next_key("ranvec");
+            expect('[');
+            for (int i = 0; i < 256; ++i) {
+                if (i) { if (peek(']')) fail("wrong array length"); expect(','); }
+                if (peek(']')) fail("wrong array length");
+                pn->ranvec[i] = vec();
+            }
+            if (peek(',')) fail("wrong array length");
+            expect(']');
+            const char* names[3] = {"perm_x", "perm_y", "perm_z"};
+            int* perm[3] = {pn->px, pn->py, pn->pz};
+            for (int a = 0; a < 3; ++a) {
+                next_key(names[a]);
+                double v[256];
+                nums(v, 256);
+                for (int i = 0; i < 256; ++i) {
+                    if (!(v[i] >= 0 && v[i] <= 255) || v[i] != std::floor(v[i])) fail("perlin permutation entry out of range");
+                    perm[a][i] = static_cast<int>(v[i]);
+                }
+            }
+            uint64_t h = fnv1a(reinterpret_cast<const unsigned char*>(pn->ranvec), sizeof pn->ranvec);
+            h ^= fnv1a(reinterpret_cast<const unsigned char*>(pn->px), 3 * sizeof pn->px) * 31u;
+            auto it = perlins.find(h);
+            if (it != perlins.end() && std::memcmp(s.perlins[it->second].ranvec, pn->ranvec, sizeof pn->ranvec) == 0 &&
+                std::memcmp(s.perlins[it->second].px, pn->px, 3 * sizeof pn->px) == 0) {
+                t.perlin = it->second;
+            } else {
+                s.perlins.push_back(*pn);
+                t.perlin = perlins[h] = static_cast<int>(s.perlins.size()) - 1;
+            }
+        } else if (type == "image") {
+            t.k = T_IMAGE;
+            t.image = image();
+        } else if (type == "bary_image") {
+            t.k = T_BARY_IMAGE;
+            double v[2];
+            next_key("a"); nums(v, 2); t.ua = v[0]; t.va = v[1];
+            next_key("b"); nums(v, 2); t.ub = v[0]; t.vb = v[1];
+            next_key("c"); nums(v, 2); t.uc = v[0]; t.vc = v[1];
+            next_key("tex");
+            if (open() != "image") fail("a bary_image holds an image");
+            t.image = image();
+            close();
+        } else {
+            fail("unknown texture type \"" + type + "\"");
+        }
+        close();
+        return s.tex(t);
+    }
+    int mat() {
+        const std::string type = open();
+        Mat m{M_LAMB};
+        if (type == "lambertian" || type == "diffuse_light" || type == "isotropic") {
+            m.k = type == "lambertian" ? M_LAMB : type == "diffuse_light" ? M_LIGHT : M_ISO;
+            next_key("tex"); m.tex = tex();
+        } else if (type == "metal") {
+            m.k = M_METAL;
+            next_key("albedo"); m.albedo = vec();
+            next_key("fuzz"); m.fuzz = num();
+        } else if (type == "dielectric") {
+            m.k = M_DIEL;
+            next_key("ir"); m.ir = num();
+        } else {
+            fail("unknown material type \"" + type + "\"");
+        }
+        close();
+        return s.mat(m);
+    }
+    std::vector<int> objs() {
+        std::vector<int> out;
+        expect('[');
+        if (!peek(']')) {
+            out.push_back(obj());
+            while (peek(',')) { ++p; out.push_back(obj()); }
+        }
+        expect(']');
+        return out;
+    }
+    // bvh.cpp:3-42 after its sorts, from the leaf order alone: 1-spans alias left == right, 2-spans keep the listed
+    // order, larger spans split at start + span / 2; node boxes over (time0, time1) = (0, 1) like every builder call.
+    int bvh(const std::vector<int>& leaves, size_t start, size_t end_, int& nodes) {
+        Obj node{O_BVH};
+        const size_t span = end_ - start;
+        ++nodes;
+        if (span == 1) {
+            node.left = node.right = leaves[start];
+        } else if (span == 2) {
+            node.left = leaves[start];
+            node.right = leaves[start + 1];
+        } else {
+            const size_t mid = start + span / 2;
+            node.left = bvh(leaves, start, mid, nodes);
+            node.right = bvh(leaves, mid, end_, nodes);
+        }
+        AABB bl, br;
+        if (!bounding_box(s, node.left, 0, 1, bl) || !bounding_box(s, node.right, 0, 1, br)) fail("bvh item without a bounding box");
+        node.box = surrounding(bl, br);
+        return s.add(node);
+    }
+    int obj() {
+        const std::string type = open();
+        int idx = -1;
+        if (type == "sphere") {
+            Obj o{O_SPHERE};
+            next_key("center"); o.c0 = vec();
+            next_key("radius"); o.r = num();
+            next_key("mat"); o.mat = mat();
+            idx = s.add(o);
+        } else if (type == "moving_sphere") {
+            Obj o{O_MSPHERE};
+            next_key("center0"); o.c0 = vec();
+            next_key("center1"); o.c1 = vec();
+            next_key("time0"); o.t0 = num();
+            next_key("time1"); o.t1 = num();
+            next_key("radius"); o.r = num();
+            next_key("mat"); o.mat = mat();
+            idx = s.add(o);
+        } else if (type == "triangle") {
+            Obj o{O_TRI};
+            next_key("p");
+            expect('[');
+            o.c0 = vec();
+            if (peek(']')) fail("wrong array length");
+            expect(',');
+            o.c1 = vec();
+            if (peek(']')) fail("wrong array length");
+            expect(',');
+            o.p3 = vec();
+            if (peek(',')) fail("wrong array length");
+            expect(']');
+            next_key("mat"); o.mat = mat();
+            idx = s.add(o);
+        } else if (type == "xy_rect" || type == "xz_rect" || type == "yz_rect") {
+            Obj o{type[1] == 'y' ? O_XY : type[0] == 'x' ? O_XZ : O_YZ};
+            next_key("a0"); o.a0 = num();
+            next_key("a1"); o.a1 = num();
+            next_key("b0"); o.b0 = num();
+            next_key("b1"); o.b1 = num();
+            next_key("k"); o.kk = num();
+            next_key("mat"); o.mat = mat();
+            idx = s.add(o);
+        } else if (type == "box") {  // box.cpp:3-19 from min, max and the sides' material; the listed sides must be those
+            next_key("min"); const V3 p0 = vec();
+            next_key("max"); const V3 p1 = vec();
+            next_key("sides");
+            const std::vector<int> sides = objs();
+            if (sides.size() != 6) fail("wrong array length: a box has 6 sides");
+            for (int sd : sides)
+                if (s.objs[sd].k != O_XY && s.objs[sd].k != O_XZ && s.objs[sd].k != O_YZ) fail("a box side is a rect");
+            idx = s.box(p0, p1, s.objs[sides[0]].mat);
+            for (size_t i = 0; i < 6; ++i)
+                if (dump_obj(s, sides[i]) != dump_obj(s, s.objs[idx].items[i])) fail("box sides disagree with min, max");
+        } else if (type == "list") {
+            Obj o{O_LIST};
+            next_key("items"); o.items = objs();
+            idx = s.add(o);
+        } else if (type == "bvh") {
+            next_key("nodes"); const int listed_nodes = integer(0, INT32_MAX, "bvh node count");
+            next_key("box"); const AABB box = aabb();
+            next_key("items");
+            const std::vector<int> leaves = objs();
+            if (leaves.empty()) fail("bvh over an empty list");
+            int nodes = 0;
+            idx = bvh(leaves, 0, leaves.size(), nodes);
+            const AABB& got = s.objs[idx].box;
+            if (nodes != listed_nodes) fail("bvh node count disagrees with its items");
+            for (int a = 0; a < 3; ++a)
+                if (got.mn[a] != box.mn[a] || got.mx[a] != box.mx[a]) fail("bvh box disagrees with its items");
+        } else if (type == "translate") {
+            Obj o{O_TRANSLATE};
+            next_key("offset"); o.c0 = vec();
+            next_key("child"); o.left = obj();
+            idx = s.add(o);
+        } else if (type == "rotate_y") {
+            Obj o{O_ROTY};
+            next_key("sin"); o.sin_t = num();
+            next_key("cos"); o.cos_t = num();
+            next_key("hasbox"); o.hasbox = boolean();
+            next_key("bbox"); o.box = aabb();
+            next_key("child"); o.left = obj();
+            idx = s.add(o);
+        } else if (type == "constant_medium") {
+            Obj o{O_MEDIUM};
+            next_key("neg_inv_density"); o.neg_inv_density = num();
+            next_key("phase"); o.mat = mat();
+            next_key("boundary"); o.left = obj();
+            idx = s.add(o);
+        } else {
+            fail("unknown object type \"" + type + "\"");
+        }
+        close();
+        return idx;
+    }
+    void scene() {
+        expect('{');
+        key("lookfrom"); s.lookfrom = vec();
+        next_key("lookat"); s.lookat = vec();
+        next_key("vfov"); s.vfov = num();
+        next_key("aperture"); s.aperture = num();
+        next_key("background"); s.background = vec();
+        next_key("objects"); s.world = objs();
+        expect('}');
+        ws();
+        if (p != end) fail("trailing garbage");
+    }
+};
+
+void load_dump(Scene& s, const std::string& text) { DumpReader(s, text).scene(); }
+
+// Only pcg mode is defined for a dump: the mt stream position after a caller's build is unknown.
+bool refuse_mt_dump(const char* scene, int mode) {
+    if (mode != ORC_MT || !scene || !is_dump(scene)) return false;
+    g_err = "a scene dump renders in pcg mode only (the mt stream position after the caller's build is unknown)";
+    return true;
+}
+
 void build_scene(Scene& s, const std::string& name, Rng& rng) {  // scene_manager.cpp:260-355 (+ SURVEY Q7/Q8)
     const V3 sky(0.70, 0.80, 1.00);
-    if (name == "c1") {
+    if (is_dump(name.c_str())) {
+        load_dump(s, name);
+    } else if (name == "c1") {
         s.world.push_back(s.sphere(V3(0, -100.5, -1), 100, s.lambertian(V3(0.8, 0.8, 0.0))));
         s.world.push_back(s.sphere(V3(0, 0, -1), 0.5, s.lambertian(V3(0.7, 0.3, 0.3))));
         s.world.push_back(s.sphere(V3(-1, 0, -1), 0.5, s.lambertian(V3(0.1, 0.2, 0.5))));
@@ -1113,6 +1506,23 @@ extern "C" {
 void orc_set_asset_dir(const char* dir) { g_asset_dir = dir ? dir : "assets"; }
 const char* orc_last_error(void) { return g_err.c_str(); }
 
+int orc_register_image(int w, int h, int bpp, const unsigned char* data) try {
+    if (w < 1 || h < 1 || w > 65536 || h > 65536 || bpp < 3 || bpp > 4 || !data) {
+        g_err = "invalid image";
+        return -2;
+    }
+    Image im;
+    im.w = w; im.h = h; im.bpp = bpp;
+    im.data.assign(data, data + static_cast<size_t>(w) * h * bpp);
+    const ImageKey k{w, h, bpp, fnv1a(im.data.data(), im.data.size())};
+    std::lock_guard<std::mutex> lock(g_images_mutex);
+    g_images[k] = std::move(im);
+    return 0;
+} catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+}
+
 int orc_kat(int n, double* out) {
     Rng rng;
     for (int i = 0; i < n; ++i) out[i] = rng.d();
@@ -1120,6 +1530,7 @@ int orc_kat(int n, double* out) {
 }
 
 int orc_probe(const char* scene, int k, double* out) try {
+    if (refuse_mt_dump(scene, ORC_MT)) return -2;  // the probe is the mt stream after the build
     Scene s;
     Rng rng;
     build_scene(s, scene, rng);
@@ -1156,6 +1567,7 @@ int orc_render(const char* scene, int W, int H, int spp, int max_depth, int mode
         g_err = "invalid render arguments";
         return -2;
     }
+    if (refuse_mt_dump(scene, mode)) return -2;
     Scene s;
     Rng scene_rng;  // scene build always replays the reference's mt19937 (geometry identical in both modes)
     build_scene(s, scene, scene_rng);
@@ -1216,6 +1628,7 @@ int orc_render_images(const char* scene, int W, int H, int spp, int max_depth, i
         g_err = "invalid render arguments";
         return -2;
     }
+    if (refuse_mt_dump(scene, mode)) return -2;
     Scene s;
     Rng scene_rng;
     build_scene(s, scene, scene_rng);
@@ -1373,6 +1786,7 @@ int orc_render_adaptive(const char* scene, int W, int H, int spp, int max_depth,
                         uint8_t* rgb_out, long long* segments_out, double* ms_out) try {
     if (W < 12 || H < 12 || spp < 1 || max_depth < 0) { g_err = "invalid render arguments"; return -2; }
     if (W % 12 != 0 || H % 12 != 0) { g_err = "for adaptive strategy image size should perfectly fit big square size for now!!"; return -3; }
+    if (refuse_mt_dump(scene, mode)) return -2;
     Scene s;
     Rng scene_rng;
     build_scene(s, scene, scene_rng);

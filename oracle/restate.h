@@ -19,6 +19,18 @@ enum { ORC_MT = 0, ORC_PCG = 1 };
 // Directory holding assets produced from the reference inputs (cow/dino triangle lists, decoded textures).
 void orc_set_asset_dir(const char* dir);
 
+// Scene arguments.  Every `scene` below is a builtin name ("1".."9", "c1", "cow", "dino", the alias names) or, when its
+// first non-blank character is '{', a canonical scene dump (orc_dump's output; rt_scene_dump of the product emits the
+// same schema), so a scene the oracle did not build renders through the same entries.  A dump's bvh is rebuilt from
+// its leaf order (spans of 1 and 2 as listed, larger spans split at start + span / 2), its boxes from min / max; a dump
+// whose `nodes`, `box` or `sides` disagree, or that is malformed in any way, is an error.  Image texels are not in a
+// dump: register them first.  Only ORC_PCG is defined for a dump (the mt stream position after a caller's build is
+// unknown): ORC_MT entries and orc_probe return an error.
+
+// Keeps a copy of an image's texels (h rows of w pixels of bpp bytes) keyed by (w, h, bpp, FNV-1a of the bytes): the
+// `image` / `bary_image` textures of a dump resolve against these.  Returns 0, <0 on error.
+int orc_register_image(int w, int h, int bpp, const unsigned char* data);
+
 // First n values of random_double() from a fresh generator.
 int orc_kat(int n, double* out);
 

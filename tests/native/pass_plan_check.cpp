@@ -72,6 +72,20 @@ static int check_plan() {
         std::printf("FAIL list_pad\n");
         return 1;
     }
+    // adaptive mode's four level lists lie one after another, each behind its count line and padded to whole batches:
+    // the words reserved hold that layout for every frame size (2 squares: 704 words, more than 288 pixels + 256)
+    for (uint32_t nsq = 1; nsq <= 4096; nsq += (nsq < 64 ? 1 : 61)) {
+        uint32_t end = 0;
+        for (uint32_t cap : {4u, 12u, 48u, 80u}) end += 64 + art::list_pad(cap * nsq);
+        if (art::adaptive_list_words(nsq) != end || end < 144 * nsq + 256) {
+            std::printf("FAIL adaptive_list_words nsq=%u -> %u (layout ends at %u)\n", nsq, art::adaptive_list_words(nsq), end);
+            return 1;
+        }
+    }
+    if (art::adaptive_list_words(2) != 704 || art::adaptive_list_words(32) != 32 * 144 + 256) {
+        std::printf("FAIL adaptive_list_words small frames\n");
+        return 1;
+    }
     // noise-target rounds (entry-major: no padding)
     struct RoundCase { uint32_t k_next, Pmax, n_active, want; } rounds[] = {
         {32, 4096, 4096, 1},   // n_active = Pmax

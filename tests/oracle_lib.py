@@ -2,6 +2,7 @@
 __graft_entry__.smoke() and bench.py's cpu_baseline leg, always as the checker / CPU baseline, never as the product."""
 import ctypes
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -15,11 +16,22 @@ MODES = {"mt": 0, "pcg": 1}
 _lib = None
 
 
+def ensure_oracle():
+    """Builds oracle/_ref/liboracle.so unless it is there and current.  make goes by timestamps, and a library left by a
+    build of an older tree can look newer than the sources a checkout has just written; a library that lacks the newest
+    entry this module binds is such a one and is rebuilt whatever its date (the Makefile replaces it atomically)."""
+    current = False
+    if os.path.exists(ORACLE_SO):
+        with open(ORACLE_SO, "rb") as f:
+            current = b"orc_register_image\0" in f.read()
+    if not current:
+        subprocess.run(["make", "-B", "-C", os.path.join(ROOT, "oracle"), "restate"], check=True)
+
+
 def oracle():
     global _lib
     if _lib is None:
-        if not os.path.exists(ORACLE_SO):
-            subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "restate"], check=True)
+        ensure_oracle()
         lib = ctypes.CDLL(ORACLE_SO)
         lib.orc_last_error.restype = ctypes.c_char_p
         lib.orc_dump.restype = ctypes.c_size_t
@@ -35,6 +47,9 @@ def oracle():
         lib.orc_render_images.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_double)]
+        lib.orc_trace_rays.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p]
+        lib.orc_dump.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
+        lib.orc_register_image.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
         lib.orc_set_asset_dir(ASSETS.encode())
         _lib = lib
     return _lib
@@ -109,9 +124,39 @@ def oracle_render_images(scene, W, H, spp, mode="pcg", seed=0, threads=0, max_de
 def oracle_dump(scene):
     lib = oracle()
     n = lib.orc_dump(str(scene).encode(), None, 0)
+    if n == 0:
+        raise RuntimeError(lib.orc_last_error().decode())
     buf = ctypes.create_string_buffer(n)
     lib.orc_dump(str(scene).encode(), buf, n)
     return buf.value.decode()
+
+
+def oracle_register_image(pixels):
+    """Gives the oracle the texels of an (H, W, C) uint8 image: a dump names an image only by size and FNV-1a hash."""
+    pixels = np.ascontiguousarray(pixels, dtype=np.uint8)
+    h, w, c = pixels.shape
+    if oracle().orc_register_image(w, h, c, pixels.ctypes.data) != 0:
+        raise RuntimeError(oracle().orc_last_error().decode())
+
+
+_HEADER = re.compile(r'\A\{"lookfrom":.*?,"objects":\[', re.S)
+
+
+def _vec(v):
+    return "[" + ",".join(repr(float(x)) for x in v) + "]"
+
+
+def caller_scene_dump(world, lookfrom, lookat, vfov, aperture, background):
+    """The canonical dump of a caller-built world compiled for device 0 (hittable_list(native=compile_world(w, 0)), or a
+    scene_manager scene), with the five header fields replaced by the caller's view: the text every oracle_* function
+    takes in place of a builtin scene's name.  Python's repr of a float round-trips."""
+    from another_raytracer_amd.scene import scene_dump
+    text = scene_dump(world)
+    header = (f'{{"lookfrom":{_vec(lookfrom)},"lookat":{_vec(lookat)},"vfov":{float(vfov)!r},"aperture":{float(aperture)!r},'
+              f'"background":{_vec(background)},"objects":[')
+    out, n = _HEADER.subn(lambda m: header, text, count=1)
+    assert n == 1, "not a canonical scene dump"
+    return out
 
 
 def oracle_kat(n):
