@@ -22,11 +22,13 @@ camera rays as data: camera_rays(cam, W, H, spp) -- see rays.py.  Many cameras o
 frame equal to engine.run's: render_views(world, cams, W, H, spp) -- see views.py.  New vertices for a compiled scene's
 triangles with a BVH refit on the device (animated or optimised meshes): update_triangles(world, p); new centres and radii
 for its spheres: update_spheres(world, s) -- see deform.py.  New values for its materials and textures (colours, fuzz,
-ir, noise scale): update_materials(world, m), update_textures(world, t) -- see appearance.py.  New extents for its rects
+ir, noise scale): update_materials(world, m), update_textures(world, t), and new bytes for its image textures:
+update_texels(world, image, texels) -- see appearance.py.  New extents for its rects
 and boxes, and new offsets, angles and densities for its translate, rotate_y and constant_medium objects (rigid animation
 without a refit): update_rects, update_boxes, update_objects -- see rigid.py.  The exact gradient of radiance_rays'
-radiance with respect to the solid texture colours, the metal albedos and the background: radiance_grad(world, rays,
-weights), render_grad, and the torch operation differentiable_radiance -- see grad.py.
+radiance with respect to the solid texture colours, the metal albedos and the background -- and, with texels=True, every
+texel of the scene's image textures: radiance_grad(world, rays, weights), render_grad, and the torch operation
+differentiable_radiance -- see grad.py.
 All compute runs in libart.so (HIP, gfx950) behind include/art.h.
 """
 from ._lib import RTError, get_option, lib, set_option  # noqa: F401  (fails loudly when libart.so is missing)
@@ -39,7 +41,9 @@ from .scene import (  # noqa: F401
 from .rays import HitRecords, camera_rays, query_rays, radiance_rays  # noqa: F401
 from .views import render_views  # noqa: F401
 from .deform import scene_bvh, scene_lds_image, scene_spheres, scene_triangles, update_spheres, update_triangles  # noqa: F401
-from .appearance import scene_materials, scene_textures, update_materials, update_textures  # noqa: F401
+from .appearance import (  # noqa: F401
+    scene_images, scene_materials, scene_texels, scene_textures, update_materials, update_texels, update_textures,
+)
 from .rigid import (  # noqa: F401
     OBJ_BVH, OBJ_MEDIUM, OBJ_PRIM, OBJ_ROTATE_Y, OBJ_TRANSLATE, medium_density, rotation, scene_boxes, scene_objects, scene_rects, update_boxes,
     update_objects, update_rects,
@@ -49,7 +53,7 @@ from . import imageio  # noqa: F401
 
 __all__ = [
     "RTError", "set_option", "get_option", "camera", "denoise", "engine", "engine_mode", "tracer_constants", "scene", "scene_alias", "scene_manager",
-    "query_rays", "radiance_rays", "radiance_grad", "render_grad", "differentiable_radiance", "camera_rays", "render_views", "scene_triangles", "update_triangles", "scene_bvh", "scene_spheres", "update_spheres", "scene_lds_image", "scene_materials", "scene_textures", "update_materials", "update_textures", "scene_rects", "scene_boxes", "scene_objects", "update_rects", "update_boxes", "update_objects", "rotation", "medium_density",
+    "query_rays", "radiance_rays", "radiance_grad", "render_grad", "differentiable_radiance", "camera_rays", "render_views", "scene_triangles", "update_triangles", "scene_bvh", "scene_spheres", "update_spheres", "scene_lds_image", "scene_materials", "scene_textures", "update_materials", "update_textures", "scene_images", "scene_texels", "update_texels", "scene_rects", "scene_boxes", "scene_objects", "update_rects", "update_boxes", "update_objects", "rotation", "medium_density",
     "OBJ_PRIM", "OBJ_BVH", "OBJ_TRANSLATE", "OBJ_ROTATE_Y", "OBJ_MEDIUM", "HitRecords", "compile_world", "hittable_list", "bvh_node", "sphere", "moving_sphere", "triangle", "xy_rect", "xz_rect", "yz_rect", "box",
     "translate", "rotate_y", "constant_medium", "lambertian", "metal", "dielectric", "diffuse_light", "solid_color",
     "checker_texture", "noise_texture", "image_texture", "barycentric_image_texture", "mesh", "random_double", "reset_scene_rng", "imageio", "save_scene",

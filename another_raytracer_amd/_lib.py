@@ -132,6 +132,10 @@ SIGNATURES = {
     "rt_scene_textures_get": (ctypes.c_int64, [_P, _P, _P, ctypes.c_int64]),
     "rt_scene_update_materials": (_I, [_P, ctypes.POINTER(rt_update_params), _P, ctypes.c_int64, ctypes.c_int64, _DP]),
     "rt_scene_update_textures": (_I, [_P, ctypes.POINTER(rt_update_params), _P, ctypes.c_int64, ctypes.c_int64, _DP]),
+    "rt_scene_images_get": (ctypes.c_int64, [_P, _P, _P, ctypes.c_int64]),
+    "rt_scene_texture_images_get": (ctypes.c_int64, [_P, _P, ctypes.c_int64]),
+    "rt_scene_texels_get": (ctypes.c_int64, [_P, ctypes.c_int32, _P, ctypes.c_int64]),
+    "rt_scene_update_texels": (_I, [_P, ctypes.POINTER(rt_update_params), ctypes.c_int32, _P, ctypes.c_int64, ctypes.c_int64, _DP]),
     "rt_scene_rects_get": (ctypes.c_int64, [_P, _P, _P, ctypes.c_int64]),
     "rt_scene_boxes_get": (ctypes.c_int64, [_P, _P, _P, ctypes.c_int64]),
     "rt_scene_objects_get": (ctypes.c_int64, [_P, _P, _P, ctypes.c_int64]),
@@ -145,6 +149,8 @@ SIGNATURES = {
     "rt_query_rays": (_I, [_P, ctypes.POINTER(rt_query_params), _P, _P, ctypes.c_int64, _P, _P]),
     "rt_radiance_rays": (_I, [_P, ctypes.POINTER(rt_radiance_params), _P, _P, ctypes.c_int64, _P, ctypes.POINTER(rt_stats)]),
     "rt_radiance_grad": (_I, [_P, ctypes.POINTER(rt_radiance_params), _P, _P, _P, ctypes.c_int64, _P, _P, _P, _P, ctypes.POINTER(rt_stats)]),
+    "rt_radiance_grad_texels": (_I, [_P, ctypes.POINTER(rt_radiance_params), _P, _P, _P, ctypes.c_int64, _P, _P, _P, _P, _P,
+                                     ctypes.POINTER(rt_stats)]),
     "rt_camera_rays": (_I, [ctypes.POINTER(rt_camera), ctypes.POINTER(rt_params), ctypes.c_uint32, _I, _P, _P]),
     "rt_tile_candidates": (_I, [_P, ctypes.POINTER(rt_camera), ctypes.POINTER(rt_params), _P, ctypes.c_int64]),
     "rt_render_views": (_I, [_P, ctypes.POINTER(rt_camera), _P, ctypes.c_int32, ctypes.POINTER(rt_params), _P, _P, ctypes.POINTER(rt_stats)]),

@@ -21,19 +21,20 @@ def get(world, name, *shapes):
     return outs
 
 
-def update(world, v, arg, shapes, rule, name, first, stream, timing):
+def update(world, v, arg, shapes, rule, name, first, stream, timing, dtypes=("float64",), lead=()):
     """rt_scene_<name>: v (the caller's argument `arg`) holds records [first, first + n); its shape is (n, *one of shapes),
-    which `rule` says in words."""
+    which `rule` says in words.  dtypes: the element type (update_texels: uint8); lead: the arguments the C function takes
+    between its params and its buffer (update_texels: the image)."""
     handle = _native_scene(world)
     if not hasattr(v, "shape"):
         raise TypeError(f"{arg} must be a numpy array or a torch tensor")
     shape = tuple(int(x) for x in v.shape)
     if shape[1:] not in shapes:
         raise ValueError(f"{arg} must have {rule}")
-    ptr, dev = address(v, arg, ("float64",), shape=shape, device_index=handle.device)
+    ptr, dev = address(v, arg, dtypes, shape=shape, device_index=handle.device)
     u = rt_update_params()
     u.flags = RT_OUT_DEVICE if dev else 0
     u.stream = stream_handle(stream, v.device if dev else None)
     ms = ctypes.c_double()
-    check(getattr(lib, f"rt_scene_{name}")(handle, ctypes.byref(u), ctypes.c_void_p(ptr), int(first), shape[0], ctypes.byref(ms) if timing else None), name)
+    check(getattr(lib, f"rt_scene_{name}")(handle, ctypes.byref(u), *lead, ctypes.c_void_p(ptr), int(first), shape[0], ctypes.byref(ms) if timing else None), name)
     return ms.value if timing else None

@@ -15,10 +15,22 @@ makes is a row too), and the material index is query_rays' `mat`.  A record take
 fuzz (clamped to 1), a dielectric ir, a solid texture its colour, a noise texture its scale; everything else in a row is
 ignored and stays, so get -> update changes nothing.  Every later call gives the bits a scene compiled fresh with the
 same values gives.
+
+Image textures are bytes, not rows of doubles, and have calls of their own (rt_scene_images_get, rt_scene_texels_get,
+rt_scene_update_texels):
+
+    desc, first_texel, texture_image = art.scene_images(world)   # per image {w, h, bpp} and its first global texel
+    earth = art.scene_texels(world, 0)                            # (h, w, bpp) uint8, top row first
+    earth[:, :, 0] //= 2
+    art.update_texels(world, 0, earth)                            # or rows: update_texels(world, 0, earth[10:20], first_row=10)
 """
+import ctypes
+
 import numpy as np
 
 from . import _update
+from ._lib import check, lib
+from .rays import _native_scene
 
 MATERIAL_DOUBLES, TEXTURE_DOUBLES = 5, 4   # art.h RT_MATERIAL_DOUBLES, RT_TEXTURE_DOUBLES
 
@@ -55,3 +67,44 @@ def update_textures(world, t, first=0, stream=None, timing=False):
     image and barycentric image textures take nothing.  Every material that uses the texture -- directly or through a
     checker -- shows the new value.  t, stream and timing as update_materials."""
     return _update.update(world, t, "t", ((TEXTURE_DOUBLES,),), "shape (n, 4): colour r, g, b; scale per texture", "update_textures", first, stream, timing)
+
+
+def scene_images(world):
+    """rt_scene_images_get and rt_scene_texture_images_get: (desc, first_texel, texture_image) -- desc (K, 3) int32: w, h,
+    bpp of image k, in the order the scene's images were made; first_texel (K,) int64: the global index of the image's
+    texel (0, 0), texel (column i, row j from the top) being first_texel[k] + j * w + i -- the rows of radiance_grad's
+    texel gradient; texture_image (T,) int32: the image of texture t (an image or a barycentric image texture), else -1.
+    Needs no device."""
+    desc, first = _update.get(world, "scene_images", ((3,), np.int32), ((), np.int64))
+    tex, = _update.get(world, "scene_texture_images", ((), np.int32))
+    return desc, first, tex
+
+
+def _image_desc(handle, image):
+    """(w, h, bpp) of image `image` of the native scene; IndexError for an image the scene does not have."""
+    n = check(lib.rt_scene_images_get(handle, None, None, 0), "scene_images")
+    if not 0 <= int(image) < n:
+        raise IndexError(f"image {image} is not one of the scene's {n} images")
+    desc = np.empty((n, 3), np.int32)
+    check(lib.rt_scene_images_get(handle, ctypes.c_void_p(desc.ctypes.data), None, n), "scene_images")
+    return tuple(int(x) for x in desc[int(image)])
+
+
+def scene_texels(world, image):
+    """rt_scene_texels_get: the bytes of image `image` as the scene holds them now, an (h, w, bpp) uint8 array, top row
+    first.  Needs no device unless the scene has been updated."""
+    handle = _native_scene(world)
+    w, h, bpp = _image_desc(handle, image)
+    out = np.empty((h, w, bpp), np.uint8)
+    check(lib.rt_scene_texels_get(handle, int(image), ctypes.c_void_p(out.ctypes.data), out.nbytes), "scene_texels")
+    return out
+
+
+def update_texels(world, image, texels, first_row=0, stream=None, timing=False):
+    """rt_scene_update_texels: texels holds rows [first_row, first_row + n) of image `image`, shape (n, w, bpp) uint8 in
+    scene_texels' layout.  Every later call gives the bits a scene compiled with these bytes gives.  texels, stream and
+    timing as update_materials: a numpy array copies and blocks, a contiguous uint8 torch tensor on the scene's device is
+    read in place on `stream` (default: torch's current stream); timing=True returns the device time in milliseconds."""
+    w, _, bpp = _image_desc(_native_scene(world), image)
+    return _update.update(world, texels, "texels", ((w, bpp),), f"shape (n, {w}, {bpp}): rows of image {int(image)}", "update_texels", first_row, stream,
+                          timing, dtypes=("uint8",), lead=(int(image),))

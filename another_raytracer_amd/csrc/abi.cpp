@@ -35,7 +35,7 @@ struct rt_scene {
     art::Renderer& device_renderer() { return renderer ? *renderer : *(renderer = std::make_unique<art::Renderer>(flat, device)); }
     // the rt_scene_update_* calls leave `flat` stale: the renderer counts the updates, and whoever reads from `flat` what
     // an update writes (the getters through get_begin, rt_scene_save) takes it from the device first
-    uint64_t synced = 0;
+    uint64_t synced = 0, synced_texels = 0;
     bool updated() const { return renderer && renderer->generation() > 0; }
     void sync_flat() {
         if (!renderer || renderer->generation() == synced) return;
@@ -48,7 +48,8 @@ struct rt_scene {
         flat.rects = now.rects;
         flat.boxes = now.boxes;
         flat.objs = now.objs;
-        synced = renderer->generation();
+        if (synced_texels != renderer->texel_generation()) flat.texels = now.texels;  // (the pool is large: only after a texel update)
+        synced = renderer->generation(), synced_texels = renderer->texel_generation();
     }
 };
 struct rt_graph {
@@ -226,7 +227,7 @@ size_t rt_scene_dump(const rt_scene* s, char* buf, size_t cap) {
         return 0;
     }
     if (s->updated()) {
-        fail(RT_E_SCENE, "the scene was updated (rt_scene_update_triangles, _spheres, _materials, _textures, _rects, _boxes, _objects): its object graph no longer describes it");
+        fail(RT_E_SCENE, "the scene was updated (rt_scene_update_triangles, _spheres, _materials, _textures, _texels, _rects, _boxes, _objects): its object graph no longer describes it");
         return 0;
     }
     try {
@@ -394,6 +395,80 @@ int rt_scene_update_materials(rt_scene* s, const rt_update_params* u, const doub
 
 int rt_scene_update_textures(rt_scene* s, const rt_update_params* u, const double* t, int64_t first, int64_t n, double* ms) {
     return scene_update(art::UpdateKind::Textures, s, u, t, first, n, ms);
+}
+
+// ---- image texels: the images are the graph's in rt_tex_image order (compile_scene: one ImageRec per graph image)
+static int64_t texel_count(const art::FlatScene& f) {
+    int64_t n = 0;
+    for (const art::ImageRec& im : f.images) n += static_cast<int64_t>(im.w) * static_cast<int64_t>(im.h);
+    return n;
+}
+
+int64_t rt_scene_images_get(rt_scene* s, int32_t* desc_out, int64_t* first_texel_out, int64_t cap) {
+    if (!s) return fail(RT_E_INVALID, "rt_scene_images_get: scene is NULL");
+    const int64_t count = static_cast<int64_t>(s->flat.images.size());
+    if (!desc_out && !first_texel_out) return count;
+    if (cap < count)
+        return fail(RT_E_INVALID, "rt_scene_images_get: the out buffers hold " + std::to_string(cap) + " images, the scene has " + std::to_string(count));
+    int64_t first = 0;
+    for (int64_t k = 0; k < count; ++k) {
+        const art::ImageRec& im = s->flat.images[static_cast<size_t>(k)];
+        if (desc_out) desc_out[3 * k] = im.w, desc_out[3 * k + 1] = im.h, desc_out[3 * k + 2] = im.bpp;
+        if (first_texel_out) first_texel_out[k] = first;
+        first += static_cast<int64_t>(im.w) * static_cast<int64_t>(im.h);
+    }
+    return count;
+}
+
+int64_t rt_scene_texture_images_get(rt_scene* s, int32_t* image_out, int64_t cap) {
+    if (!s) return fail(RT_E_INVALID, "rt_scene_texture_images_get: scene is NULL");
+    const int64_t count = static_cast<int64_t>(s->flat.texs.size());
+    if (!image_out) return count;
+    if (cap < count)
+        return fail(RT_E_INVALID, "rt_scene_texture_images_get: image_out holds " + std::to_string(cap) + " textures, the scene has " + std::to_string(count));
+    for (int64_t k = 0; k < count; ++k) {
+        const art::TexRec& t = s->flat.texs[static_cast<size_t>(k)];
+        image_out[k] = (t.type == art::TEX_IMAGE || t.type == art::TEX_BARY_IMAGE) ? t.image : -1;
+    }
+    return count;
+}
+
+int64_t rt_scene_texels_get(rt_scene* s, int32_t image, uint8_t* out, int64_t cap_bytes) {
+    if (!s) return fail(RT_E_INVALID, "rt_scene_texels_get: scene is NULL");
+    if (image < 0 || static_cast<size_t>(image) >= s->flat.images.size())
+        return fail(RT_E_INVALID, "rt_scene_texels_get: image " + std::to_string(image) + " is not one of the scene's " + std::to_string(s->flat.images.size()) + " images");
+    const art::ImageRec& im = s->flat.images[static_cast<size_t>(image)];
+    const int64_t bytes = static_cast<int64_t>(im.w) * im.h * im.bpp;
+    if (!out) return bytes;
+    if (cap_bytes < bytes)
+        return fail(RT_E_INVALID, "rt_scene_texels_get: out holds " + std::to_string(cap_bytes) + " bytes, the image has " + std::to_string(bytes));
+    const int rc = guard(RT_E_DEVICE, [&] {
+        s->sync_flat();
+        return RT_OK;
+    });
+    if (rc != RT_OK) return rc;
+    std::memcpy(out, s->flat.texels.data() + im.offset, static_cast<size_t>(bytes));
+    return bytes;
+}
+
+int rt_scene_update_texels(rt_scene* s, const rt_update_params* u, int32_t image, const uint8_t* texels, int64_t first_row, int64_t n_rows, double* ms) {
+    const std::string f = "rt_scene_update_texels";
+    if (!s || !u) return fail(RT_E_INVALID, f + ": scene and params must be non-NULL");
+    if (image < 0 || static_cast<size_t>(image) >= s->flat.images.size())
+        return fail(RT_E_INVALID, f + ": image " + std::to_string(image) + " is not one of the scene's " + std::to_string(s->flat.images.size()) + " images");
+    const int64_t h = s->flat.images[static_cast<size_t>(image)].h;
+    if (first_row < 0 || n_rows < 0 || first_row > h || n_rows > h - first_row)
+        return fail(RT_E_INVALID, f + ": [first_row, first_row + n_rows) must lie within the image's " + std::to_string(h) + " rows");
+    if (u->flags & ~RT_OUT_DEVICE) return fail(RT_E_INVALID, f + " takes RT_OUT_DEVICE only");
+    if (u->stream && !(u->flags & RT_OUT_DEVICE)) return fail(RT_E_INVALID, f + ": stream needs RT_OUT_DEVICE (host buffers run on the scene's own stream)");
+    if (n_rows > 0 && !texels) return fail(RT_E_INVALID, f + ": the texel buffer is NULL");
+    if (ms) *ms = 0;
+    if (n_rows == 0) return RT_OK;
+    return guard(RT_E_DEVICE, [&] {
+        s->device_renderer().update_texels(static_cast<size_t>(image), texels, static_cast<size_t>(first_row), static_cast<size_t>(n_rows),
+                                           (u->flags & RT_OUT_DEVICE) != 0, u->stream, ms);
+        return RT_OK;
+    });
 }
 
 static_assert(art::kUpdateRows[4].width == RT_RECT_DOUBLES && art::kUpdateRows[5].width == RT_BOX_DOUBLES && art::kUpdateRows[6].width == RT_OBJECT_DOUBLES,
@@ -626,23 +701,30 @@ int rt_radiance_rays(rt_scene* s, const rt_radiance_params* q, const double* ray
     });
 }
 
-int rt_radiance_grad(rt_scene* s, const rt_radiance_params* q, const double* rays, const uint64_t* rng, const double* weights, int64_t n,
-                     double* radiance, double* grad_textures, double* grad_materials, double* grad_background, rt_stats* stats) {
-    if (!s || !q) return fail(RT_E_INVALID, "rt_radiance_grad: scene and params must be non-NULL");
-    if (n < 0 || n > (int64_t(1) << 30)) return fail(RT_E_INVALID, "rt_radiance_grad: n must be in [0, 2^30]");
-    if (q->flags & ~(RT_OUT_DEVICE | RT_GLOBAL_SCENE)) return fail(RT_E_INVALID, "rt_radiance_grad takes RT_OUT_DEVICE and RT_GLOBAL_SCENE only");
-    if (q->spp < 0) return fail(RT_E_INVALID, "rt_radiance_grad: spp must be >= 1 (0 is taken as 1)");
-    if (q->max_depth < 1) return fail(RT_E_INVALID, "rt_radiance_grad: max_depth must be >= 1");
-    if (q->stream && !(q->flags & RT_OUT_DEVICE)) return fail(RT_E_INVALID, "rt_radiance_grad: stream needs RT_OUT_DEVICE (host buffers run on the scene's own stream)");
+// rt_radiance_grad and rt_radiance_grad_texels (`f`: the name in messages; grad_texels null: the former)
+static int radiance_grad(const std::string& f, rt_scene* s, const rt_radiance_params* q, const double* rays, const uint64_t* rng, const double* weights,
+                         int64_t n, double* radiance, double* grad_textures, double* grad_materials, double* grad_background, double* grad_texels,
+                         rt_stats* stats) {
+    if (!s || !q) return fail(RT_E_INVALID, f + ": scene and params must be non-NULL");
+    if (n < 0 || n > (int64_t(1) << 30)) return fail(RT_E_INVALID, f + ": n must be in [0, 2^30]");
+    if (q->flags & ~(RT_OUT_DEVICE | RT_GLOBAL_SCENE)) return fail(RT_E_INVALID, f + " takes RT_OUT_DEVICE and RT_GLOBAL_SCENE only");
+    if (q->spp < 0) return fail(RT_E_INVALID, f + ": spp must be >= 1 (0 is taken as 1)");
+    if (q->max_depth < 1) return fail(RT_E_INVALID, f + ": max_depth must be >= 1");
+    if (q->stream && !(q->flags & RT_OUT_DEVICE)) return fail(RT_E_INVALID, f + ": stream needs RT_OUT_DEVICE (host buffers run on the scene's own stream)");
     const int64_t spp = q->spp > 0 ? q->spp : 1;
     if (static_cast<uint64_t>(n) * static_cast<uint64_t>(spp) > art::kMaxPassSlots)
-        return fail(RT_E_INVALID, "rt_radiance_grad: n * spp = " + std::to_string(n * spp) + " exceeds kMaxPassSlots = 2^31 paths per call: chunk the "
+        return fail(RT_E_INVALID, f + ": n * spp = " + std::to_string(n * spp) + " exceeds kMaxPassSlots = 2^31 paths per call: chunk the "
                                   "rays with id_base, or the samples with sample_base (gradients of chunks add)");
     if (!rng && (q->id_base > (uint64_t(1) << 32) || q->id_base + static_cast<uint64_t>(n) > (uint64_t(1) << 32)))
-        return fail(RT_E_INVALID, "rt_radiance_grad: id_base + n must be <= 2^32 (stream ids are 32 bits)");
+        return fail(RT_E_INVALID, f + ": id_base + n must be <= 2^32 (stream ids are 32 bits)");
     if (n == 0) return RT_OK;
-    if (!rays || !weights) return fail(RT_E_INVALID, "rt_radiance_grad: rays and weights must be non-NULL");
-    if (!radiance && !grad_textures && !grad_materials && !grad_background) return RT_OK;
+    if (!rays || !weights) return fail(RT_E_INVALID, f + ": rays and weights must be non-NULL");
+    if (!radiance && !grad_textures && !grad_materials && !grad_background && !grad_texels) return RT_OK;
+    if (grad_texels) {  // a vertex record's row is 32 bits: T + M + 1 + N rows, and kGradNoRow
+        const uint64_t rows = s->flat.texs.size() + s->flat.mats.size() + 1 + static_cast<uint64_t>(texel_count(s->flat));
+        if (rows > 0xFFFFFFFFull)
+            return fail(RT_E_INVALID, f + ": textures + materials + 1 + texels = " + std::to_string(rows) + " rows do not fit the 32-bit row of a vertex record");
+    }
     return guard(RT_E_DEVICE, [&] {
         art::RadianceParams rp;
         rp.spp = static_cast<int>(spp), rp.max_depth = q->max_depth, rp.sample_base = q->sample_base;
@@ -652,13 +734,25 @@ int rt_radiance_grad(rt_scene* s, const rt_radiance_params* q, const double* ray
         for (int c = 0; c < 3; ++c) rp.background[c] = q->background[c];
         art::RenderStats st;
         s->device_renderer().radiance_grad(rp, rays, rng, weights, static_cast<size_t>(n), radiance, grad_textures, grad_materials, grad_background,
-                                           stats ? &st : nullptr);
+                                           grad_texels, stats ? &st : nullptr);
         if (stats) {
             fill_stats(st, stats);
             stats->extend_variant = stats->kernel_lds_mode = -1;
         }
         return RT_OK;
     });
+}
+
+int rt_radiance_grad(rt_scene* s, const rt_radiance_params* q, const double* rays, const uint64_t* rng, const double* weights, int64_t n,
+                     double* radiance, double* grad_textures, double* grad_materials, double* grad_background, rt_stats* stats) {
+    return radiance_grad("rt_radiance_grad", s, q, rays, rng, weights, n, radiance, grad_textures, grad_materials, grad_background, nullptr, stats);
+}
+
+int rt_radiance_grad_texels(rt_scene* s, const rt_radiance_params* q, const double* rays, const uint64_t* rng, const double* weights, int64_t n,
+                            double* radiance, double* grad_textures, double* grad_materials, double* grad_background, double* grad_texels,
+                            rt_stats* stats) {
+    return radiance_grad("rt_radiance_grad_texels", s, q, rays, rng, weights, n, radiance, grad_textures, grad_materials, grad_background, grad_texels,
+                         stats);
 }
 
 int rt_render_views(rt_scene* s, const rt_camera* cams, const uint64_t* seeds, int32_t nviews, const rt_params* p, uint8_t* out_rgb8,

@@ -5,6 +5,7 @@
 #include "k_paths_g_mesh.hip"
 #include "radiance_rays.hip"
 #include "radiance_grad.hip"
+#include "texel_grad.hip"
 #include "tile_lists.hip"
 #include "refit.hip"
 #include "device_scene.hip"

@@ -120,6 +120,28 @@ uint32_t radiance_grad_grid(const DeviceScene& ds, int num_cu, uint32_t P, uint3
 // Any of the three may be null.
 void launch_radiance_grad(const DeviceScene& ds, hipStream_t st, const GradJob& job, uint32_t grid, uint32_t n, const double background[3],
                           uint32_t n_mats, double* grad_textures, double* grad_materials, double* grad_background);
+// k_grad_finish alone (nothing when the three outputs are null): what follows launch_texel_grad's path kernel too
+void launch_grad_finish(hipStream_t st, const GradJob& job, uint32_t n_mats, double* grad_textures, double* grad_materials, double* grad_background);
+// texel_grad.hip
+// One rt_radiance_grad_texels call with a texel output as k_texel_grad sees it: rt_radiance_grad's job, and the texel
+// rows.  Global texel t (art.h: first_k + j * w_k + i) is row g.rows + t of a GradVertex and row t of the texel table,
+// which has its own copy count (Renderer::radiance_grad keeps the table within a byte budget); a block adds to copy
+// blockIdx.x % texel_copies.  image_row[k] = g.rows + first_k, or kGradNoRow for an image with bpp < 3.
+struct TexelJob {
+    GradJob g;
+    unsigned long long* texel_acc;  // texel_copies x n_texels x kGradRowLimbs, zeroed before the launch
+    const uint32_t* image_row;      // one entry per image of the scene
+    uint32_t n_texels, texel_copies;
+};
+constexpr size_t kTexelTableBudget = size_t(256) << 20;  // bytes of texel rows over all copies, unless one copy is more
+// Whether the scene's kernel has a texel form (a scene of solid and checker textures only has no image: its call is
+// launch_radiance_grad's), and that kernel's persistent grid, as radiance_grad_grid
+bool texel_grad_kernel(const DeviceScene& ds);
+uint32_t texel_grad_grid(const DeviceScene& ds, int num_cu, uint32_t P, uint32_t stack);
+// k_texel_grad over `grid` blocks, the per-ray sums, k_grad_finish, then k_texel_finish: the texel table summed over
+// its copies and rounded once into grad_texels (n_texels x 3; null: not launched)
+void launch_texel_grad(const DeviceScene& ds, hipStream_t st, const TexelJob& job, uint32_t grid, uint32_t n, const double background[3],
+                       uint32_t n_mats, double* grad_textures, double* grad_materials, double* grad_background, double* grad_texels);
 // rt_camera_rays: entry (ly * W + lx) * g.k + j = cam_ray of local pixel (lx, ly), sample g.sample_base + j (rng may be null)
 void launch_camera_rays(hipStream_t st, const PassGeom& g, const CameraRec& cam, double* rays, uint64_t* rng);
 // k_paths.hip

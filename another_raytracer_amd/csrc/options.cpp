@@ -38,6 +38,7 @@ const OptDef kDefs[static_cast<int>(Opt::kCount)] = {
     {"views.max_paths", 0, 0, 2147483648.0, true},
     {"render.tile_lists", 1, 0, 2, true},
     {"render.accum_overlap", 1, 0, 2, true},
+    {"grad.texel_copies", 0, 0, 64, true},
     {"multi.timeout_ms", std::numeric_limits<double>::quiet_NaN(), 0, kInf, false},
     {"multi.rccl_blocking", 0, 0, 1, true},
     {"test.fault_workspace_bytes", 0, 0, 1.8e19, true},

@@ -37,6 +37,8 @@ enum class Opt : int {
     AccumOverlap,    // render.accum_overlap: a whole-image k_paths pass runs as two launches and the first one's radiance
                      // records are summed on a second stream while the second traces (pass_plan.h split_pass): 0 off,
                      // 1 (default) when the records are large enough to pay for the extra launch, 2 whenever k >= 2
+    GradTexelCopies, // grad.texel_copies: copies of rt_radiance_grad_texels' texel accumulator table: 0 (default) as many as its
+                     // byte budget holds, 1..64 that many (never more than the grid has blocks); the results do not depend on it
     // multi-GPU
     MultiTimeoutMs,  // multi.timeout_ms: deadline of RCCL init / gather waits (unset: ART_MULTI_TIMEOUT_MS, else 120000;
                      // inf, or anything beyond ~292 years, means no deadline)

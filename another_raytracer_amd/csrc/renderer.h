@@ -74,8 +74,13 @@ public:
     // radiance and the three gradient buffers may each be null.  Buffers and stream as radiance_rays.  The workspace holds,
     // beside radiance_rays' parts, the accumulator table, copies x (textures + materials + 1) x 80 bytes with copies =
     // min(grid blocks, 64), and the vertex records, grid lanes x max(max_depth - 1, 1) x 64 bytes.
+    // grad_texels (rt_radiance_grad_texels; null: rt_radiance_grad, the same kernels and bits): one row of three doubles
+    // per texel of the scene's images in image order.  With it the scene's kernel is k_texel_grad, and the workspace also
+    // holds the texel table, copies x texels x 80 bytes, zeroed per call, with as many copies as 256 MiB hold (at least
+    // one, at most the other table's count; option grad.texel_copies sets the count).  A scene without an image texture
+    // runs k_radiance_grad and gets zeros.
     void radiance_grad(const RadianceParams& p, const double* rays, const uint64_t* rng, const double* weights, size_t n, double* radiance,
-                       double* grad_textures, double* grad_materials, double* grad_background, RenderStats* stats);
+                       double* grad_textures, double* grad_materials, double* grad_background, double* grad_texels, RenderStats* stats);
     // rt_render_views: nviews whole frames of p's width x height x spp, view v through cams[v] with seed seeds[v] (seeds
     // null: p.seed), each equal to render()'s bit for bit.  out_rgb (nviews x H x W x 3 bytes) and out_acc (optional, the
     // f64 sums) are host buffers, or with RT_OUT_DEVICE device buffers written in place on p.stream; the camera table,
@@ -124,6 +129,12 @@ public:
     //     cos, a medium's neg_inv_density; a prim and a BVH nothing (k_update_objects).  Nothing is prepared or refitted:
     //     no box depends on them.
     void update(UpdateKind kind, const double* v, size_t first, size_t n, bool device, void* stream, double* ms);
+    // rt_scene_update_texels: new bytes for rows [first_row, first_row + n_rows) of image `image` of flat().images (w x bpp
+    // bytes per row), through update's runner -- buffers, stream, ms, generation() as there -- as one copy into the texel
+    // pool, the only device copy of an image's bytes.  texel_generation() counts these calls: current_flat() fetches the
+    // pool only after one.
+    void update_texels(size_t image, const uint8_t* bytes, size_t first_row, size_t n_rows, bool device, void* stream, double* ms);
+    uint64_t texel_generation() const;
     // rt_scene_lds_image_get: kLdsImageBytes + sizeof(TileReps), or 0 when the scene has no LDS image; out (may be null:
     // the size only) receives the device's bytes, or with `rebuilt` what build_lds_image makes of current_flat().
     size_t lds_image_get(bool rebuilt, uint8_t* out);

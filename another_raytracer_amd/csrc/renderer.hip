@@ -39,6 +39,8 @@ struct Renderer::Impl {
     hipEvent_t ev[2] = {nullptr, nullptr};
     std::vector<ViewRec> view_table;  // rt_render_views: the camera table of the last call, as uploaded
     uint64_t gen = 0, fetched_gen = 0;  // rt_scene_update_* calls so far / the one `flat` was last fetched after
+    uint64_t texel_gen = 0, fetched_texel_gen = 0;  // rt_scene_update_texels calls likewise (the texel pool is fetched only after one)
+    const uint32_t* image_row = nullptr;  // rt_radiance_grad_texels: TexelJob::image_row on the device, made by the first such call
     // The second stream of a split pass (pass_plan.h split_pass) and its events: fork[0] the head's k_paths launch has
     // ended, fork[1] the head's sums are in.  Created by the first split.  The stream has the lowest priority, so that
     // of two dispatches that become ready together -- the tail's k_paths and the head's k_accum -- the path kernel's
@@ -115,7 +117,7 @@ struct Call {
     bool device = false, timed = false, wait = true, sizing = false;
     hipStream_t st = nullptr;
     hipEvent_t* ev = nullptr;
-    struct Copy { void* dst; const void* src; size_t bytes; } outs[4];
+    struct Copy { void* dst; const void* src; size_t bytes; } outs[6];
     int nouts = 0;
 
     Call() = default;
@@ -739,21 +741,39 @@ void Renderer::radiance_rays(const RadianceParams& p, const double* rays, const 
 }
 
 void Renderer::radiance_grad(const RadianceParams& p, const double* rays, const uint64_t* rng, const double* weights, size_t n, double* radiance,
-                             double* grad_textures, double* grad_materials, double* grad_background, RenderStats* stats) {
+                             double* grad_textures, double* grad_materials, double* grad_background, double* grad_texels, RenderStats* stats) {
     upload();
     Impl& I = *impl_;
-    const DeviceScene& ds = I.s64;
+    DeviceScene& ds = I.s64;
     if (n == 0) return;
     const uint32_t spp = static_cast<uint32_t>(std::max(1, p.spp));
     const uint64_t P = static_cast<uint64_t>(n) * spp;
     if (n > (1u << 30) || P > kMaxPassSlots) throw std::runtime_error("too many rays or paths");
+    const size_t T = I.flat.texs.size(), M = I.flat.mats.size();
+    // the texel rows: global texel t is row T + M + 1 + t of a vertex record (32 bits; abi.cpp refuses a scene beyond)
+    size_t N = 0;
+    for (const ImageRec& im : I.flat.images) N += static_cast<size_t>(im.w) * static_cast<size_t>(im.h);
+    if (grad_texels && T + M + 1 + N > 0xFFFFFFFFull) throw std::runtime_error("too many texels for a 32-bit row");
+    // with a texel output the scene's kernel is k_texel_grad -- unless the scene has no image texture (then no texel has
+    // a row: k_radiance_grad, and zeros)
+    const bool texels = grad_texels && N > 0 && texel_grad_kernel(ds);
+    if (texels && !I.image_row) {
+        std::vector<uint32_t> rows;
+        uint64_t first = T + M + 1;
+        for (const ImageRec& im : I.flat.images) {
+            rows.push_back(im.bpp >= 3 ? static_cast<uint32_t>(first) : kGradNoRow);
+            first += static_cast<uint64_t>(im.w) * static_cast<uint64_t>(im.h);
+        }
+        I.image_row = ds.upload(rows);
+    }
     Call call(I.own_stream, I.ev, p.device, p.stream, stats != nullptr);
     hipStream_t st = call.st;
-    const size_t T = I.flat.texs.size(), M = I.flat.mats.size();
-    GradJob job{};
+    TexelJob tjob{};
+    GradJob& job = tjob.g;
     RadianceJob& path = job.path;
     path.stack = stack_rows(ds.max_stack);
-    const uint32_t grid = radiance_grad_grid(ds, I.num_cu, static_cast<uint32_t>(P), path.stack);
+    const uint32_t grid = texels ? texel_grad_grid(ds, I.num_cu, static_cast<uint32_t>(P), path.stack)
+                                 : radiance_grad_grid(ds, I.num_cu, static_cast<uint32_t>(P), path.stack);
     job.lanes = grid * static_cast<uint32_t>(kBlock);
     job.rows = static_cast<uint32_t>(T + M + 1), job.n_texs = static_cast<uint32_t>(T);
     job.copies = std::min(grid, kGradMaxCopies);
@@ -761,14 +781,27 @@ void Renderer::radiance_grad(const RadianceParams& p, const double* rays, const 
     // records (lanes x max(max_depth - 1, 1) x 64 B)
     const size_t acc_limbs = static_cast<size_t>(job.copies) * job.rows * kGradRowLimbs;
     const size_t nverts = static_cast<size_t>(job.lanes) * static_cast<size_t>(std::max(p.max_depth - 1, 1));
-    double *d_gt = nullptr, *d_gm = nullptr, *d_gb = nullptr;
-    const bool grads = grad_textures || grad_materials || grad_background;  // none: the kernel records and adds nothing
+    // and with a texel output the texel table's copies (texel_copies x N x 80 B): as many as kTexelTableBudget holds, at
+    // least one, at most the other table's count; option grad.texel_copies > 0 sets the count instead (A/B, tests)
+    tjob.n_texels = static_cast<uint32_t>(N);
+    tjob.image_row = I.image_row;
+    if (texels) {
+        const size_t one = N * kGradRowLimbs * sizeof(unsigned long long);
+        const uint32_t forced = static_cast<uint32_t>(opt(Opt::GradTexelCopies));
+        const uint32_t want = forced ? forced : static_cast<uint32_t>(std::max<size_t>(1, kTexelTableBudget / one));
+        tjob.texel_copies = std::min(want, job.copies);
+    }
+    const size_t texel_limbs = texels ? static_cast<size_t>(tjob.texel_copies) * N * kGradRowLimbs : 0;
+    double *d_gt = nullptr, *d_gm = nullptr, *d_gb = nullptr, *d_gx = nullptr;
+    // none: the kernel records and adds nothing
+    const bool grads = grad_textures || grad_materials || grad_background || texels;
     call.carve(I.ws, [&](Carver& c) {
         path.next = c.take<uint32_t>(kCounterStride);
         path.segments = c.take<unsigned long long>(1);
         path.res = c.take<ResRec>(P, spp > 1 && radiance);
         job.acc = c.take<unsigned long long>(acc_limbs, grads);
         job.verts = c.take<GradVertex>(nverts, grads);
+        tjob.texel_acc = c.take<unsigned long long>(texel_limbs, texels);
         path.rays = call.in(c, rays, 7 * n);
         path.rng = call.in(c, rng, P);
         job.weights = call.in(c, weights, 3 * n);
@@ -776,6 +809,7 @@ void Renderer::radiance_grad(const RadianceParams& p, const double* rays, const 
         d_gt = call.out(c, grad_textures, RT_TEXTURE_DOUBLES * T);
         d_gm = call.out(c, grad_materials, RT_MATERIAL_DOUBLES * M);
         d_gb = call.out(c, grad_background, 3);
+        d_gx = call.out(c, N ? grad_texels : nullptr, 3 * N);
     });
     if (spp == 1 || !radiance) path.res = nullptr;
     path.P = static_cast<uint32_t>(P), path.spp = spp, path.chunk = path_chunk(path.P, I.num_cu);
@@ -787,8 +821,14 @@ void Renderer::radiance_grad(const RadianceParams& p, const double* rays, const 
     HIP_OK(hipMemsetAsync(path.segments, 0, sizeof(unsigned long long), st));
     if (!grads) job.acc = nullptr, job.verts = nullptr;
     else HIP_OK(hipMemsetAsync(job.acc, 0, sizeof(unsigned long long) * acc_limbs, st));
-    call.begin();
-    launch_radiance_grad(ds, st, job, grid, static_cast<uint32_t>(n), p.background, static_cast<uint32_t>(M), d_gt, d_gm, d_gb);
+    call.begin();  // (the texel table's zeroing is inside the timed region: it is what a texel output costs)
+    if (texels) {
+        HIP_OK(hipMemsetAsync(tjob.texel_acc, 0, sizeof(unsigned long long) * texel_limbs, st));
+        launch_texel_grad(ds, st, tjob, grid, static_cast<uint32_t>(n), p.background, static_cast<uint32_t>(M), d_gt, d_gm, d_gb, d_gx);
+    } else {
+        launch_radiance_grad(ds, st, job, grid, static_cast<uint32_t>(n), p.background, static_cast<uint32_t>(M), d_gt, d_gm, d_gb);
+        if (d_gx && N) HIP_OK(hipMemsetAsync(d_gx, 0, sizeof(double) * 3 * N, st));
+    }
     call.end();
     call.finish(path.segments).fill(stats, P, 1, static_cast<int>(spp));
 }
@@ -1087,6 +1127,22 @@ static void enqueue_update(UpdateKind kind, hipStream_t st, const DeviceScene& d
     if (kind == UpdateKind::Spheres) launch_image_nodes(st, image, w.nodes, w.n_nodes);
 }
 
+// The update runner, what every rt_scene_update_* call shares: the call protocol over `count` values v of the caller's
+// (a host v goes through the workspace), enqueue(stream, the values on the device) between the timing events, one more
+// generation, and the wait rule.
+template <class T, class Enqueue>
+static void run_update(Renderer::Impl& I, const T* v, size_t count, bool device, void* stream, double* ms, Enqueue&& enqueue) {
+    Call call(I.own_stream, I.ev, device, stream, ms != nullptr);
+    const T* in = nullptr;
+    call.carve(I.ws, [&](Carver& c) { in = call.in(c, v, count); }, 1);  // host values: through the workspace
+    call.begin();
+    enqueue(call.st, in);
+    call.end();
+    ++I.gen;
+    const Call::Done done = call.finish();  // (a device call on the caller's stream without ms returns enqueued)
+    if (ms) *ms = done.ms;
+}
+
 void Renderer::update(UpdateKind kind, const double* v, size_t first, size_t n, bool device, void* stream, double* ms) {
     const UpdateRow& row = update_row(kind);
     upload();
@@ -1096,15 +1152,27 @@ void Renderer::update(UpdateKind kind, const double* v, size_t first, size_t n, 
     if (first + n > update_count(I.flat, kind)) throw std::runtime_error(std::string("update_") + row.nouns + ": range beyond the scene's " + row.nouns);
     if (row.cls == UpdateClass::Refit) prepare_refit(I.flat, ds);
     if (row.cls == UpdateClass::Appearance) prepare_appearance(I.flat, ds);
-    Call call(I.own_stream, I.ev, device, stream, ms != nullptr);
-    const double* in = nullptr;
-    call.carve(I.ws, [&](Carver& c) { in = call.in(c, v, row.width * n); }, 1);  // host values: through the workspace
-    call.begin();
-    enqueue_update(kind, call.st, ds, in, static_cast<uint32_t>(first), static_cast<uint32_t>(n));
-    call.end();
-    ++I.gen;
-    const Call::Done done = call.finish();  // (a device call on the caller's stream without ms returns enqueued)
-    if (ms) *ms = done.ms;
+    run_update(I, v, row.width * n, device, stream, ms, [&](hipStream_t st, const double* in) {
+        enqueue_update(kind, st, ds, in, static_cast<uint32_t>(first), static_cast<uint32_t>(n));
+    });
+}
+
+// The texel pool is the only device copy of an image's bytes (device_scene.hip uploads it once; the LDS scene image holds
+// materials' shading entries, no texel), so the update is one copy on the call's stream: rows [first_row, first_row +
+// n_rows) of the image are contiguous in the pool.
+void Renderer::update_texels(size_t image, const uint8_t* bytes, size_t first_row, size_t n_rows, bool device, void* stream, double* ms) {
+    upload();
+    Impl& I = *impl_;
+    if (n_rows == 0) return;
+    if (image >= I.flat.images.size()) throw std::runtime_error("update_texels: image beyond the scene's images");
+    const ImageRec& im = I.flat.images[image];
+    if (first_row + n_rows > static_cast<size_t>(im.h)) throw std::runtime_error("update_texels: rows beyond the image");
+    const size_t pitch = static_cast<size_t>(im.w) * static_cast<size_t>(im.bpp);
+    uint8_t* dst = const_cast<uint8_t*>(I.s64.view.texels) + im.offset + first_row * pitch;
+    run_update(I, bytes, n_rows * pitch, device, stream, ms, [&](hipStream_t st, const uint8_t* in) {
+        HIP_OK(hipMemcpyAsync(dst, in, n_rows * pitch, hipMemcpyDeviceToDevice, st));
+    });
+    ++I.texel_gen;
 }
 
 size_t Renderer::lds_image_get(bool rebuilt, uint8_t* out) {
@@ -1129,6 +1197,7 @@ size_t Renderer::lds_image_get(bool rebuilt, uint8_t* out) {
 }
 
 uint64_t Renderer::generation() const { return impl_->gen; }
+uint64_t Renderer::texel_generation() const { return impl_->texel_gen; }
 
 const FlatScene& Renderer::current_flat() {
     Impl& I = *impl_;
@@ -1181,6 +1250,10 @@ const FlatScene& Renderer::current_flat() {
     if (!nodes.empty()) HIP_OK(hipMemcpy(nodes.data(), ds.view.nodes, sizeof(BvhNode) * nodes.size(), hipMemcpyDeviceToHost));
     // the 24 box floats only: the device's leaf codes address the pair-aligned slots, the host's the compiled ones
     for (size_t k = 0; k < nodes.size(); ++k) std::memcpy(&I.flat.nodes[k], &nodes[k], 24 * sizeof(float));
+    // the texel pool, when an rt_scene_update_texels call wrote it since the last fetch
+    if (I.fetched_texel_gen != I.texel_gen && !I.flat.texels.empty())
+        HIP_OK(hipMemcpy(I.flat.texels.data(), ds.view.texels, I.flat.texels.size(), hipMemcpyDeviceToHost));
+    I.fetched_texel_gen = I.texel_gen;
     I.fetched_gen = I.gen;
     return I.flat;
 }

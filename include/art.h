@@ -206,6 +206,8 @@ int rt_device_count(void);
  *   radiance records are summed on a second stream while the second, the pass's last 128 samples, traces: 0 = off, 1 =
  *   when those records are at least 8 GiB and samples_per_pass is 0, 2 = whenever a pass holds two samples or more; the
  *   frames are identical either way; rt_stats.passes and extend_launches count both launches of a split pass);
+ *   grad.texel_copies (0; the copies of rt_radiance_grad_texels' texel accumulator table: 0 = as many as its 256 MiB
+ *   budget holds, 1..64 = that many, never more than the call's grid has blocks; the gradients are identical either way);
  *   multi.timeout_ms (the RCCL deadline; inf = none), multi.rccl_blocking (0; 1 = blocking communicators, diagnosis:
  *   gives up the deadline and the error-path protection);
  *   test.fault_workspace_bytes (0 = off; N refuses workspace growth beyond N bytes), test.fault_gather_abort (0; 1 = the
@@ -360,6 +362,34 @@ int64_t rt_scene_textures_get(rt_scene* scene, double* params_out, int32_t* desc
  *   any of a row's doubles, used or ignored.  A device buffer is not inspected.  n = 0 is RT_OK and touches nothing. */
 int rt_scene_update_materials(rt_scene* scene, const rt_update_params* u, const double* m, int64_t first, int64_t n, double* ms);
 int rt_scene_update_textures(rt_scene* scene, const rt_update_params* u, const double* t, int64_t first, int64_t n, double* ms);
+/* ---- image texels (additive since ABI 5): the bytes of a scene's image textures, read, updated and (rt_radiance_grad_texels)
+ * differentiated.  A compiled scene's images are the graph's, in rt_tex_image creation order, nothing merged; a mesh's
+ * map_Kd images and a builtin scene's follow the same rule in the order the scene makes them.  Image k has w_k * h_k
+ * texels; texel (i, j) of image k -- column i, row j counted from the top row, as the lookup computes them from u, v
+ * (texture.h:90-117: i = int(clamp(u) * w), j = int((1 - clamp(v)) * h), each capped at w - 1 / h - 1) -- is global texel
+ *   first_k + j * w_k + i,   first_k = sum of w_m * h_m over m < k,   N = the total.
+ * rt_scene_images_get: returns the image count; desc_out rows {w, h, bpp}, first_texel_out first_k.  Either may be NULL;
+ *   one that is given holds cap >= count rows (RT_E_INVALID otherwise).  Needs no device.
+ * rt_scene_texture_images_get: one entry per texture (the rows of rt_scene_textures_get, whose desc rows cannot grow):
+ *   the image index of an RT_TEX_IMAGE / RT_TEX_BARY_IMAGE texture, -1 otherwise.  Returns the texture count; image_out
+ *   may be NULL, else holds cap >= count entries.  Needs no device.
+ * rt_scene_texels_get: the image's bytes, h * w * bpp, top row first, as rt_tex_image took them and as the scene holds
+ *   them now (fetched from the device first when the scene has been updated, like the other getters).  Returns the byte
+ *   count; out may be NULL, else holds cap_bytes >= that.
+ * rt_scene_update_texels: new bytes for rows [first_row, first_row + n_rows) of one image, n_rows * w * bpp of them in
+ *   the same layout, from a host buffer or (RT_OUT_DEVICE) a device buffer.  The contract is rt_scene_update_textures':
+ *   scene A updated to bytes V1 gives, in every later call, the bits a scene compiled from the same graph calls with
+ *   V1 gives; kernel choice does not move (none depends on a byte); rt_scene_save and the getters see the new bytes;
+ *   rt_scene_dump refuses an updated scene; rt_update_params, streams and waiting, ordering, the blocking upload at the
+ *   first call and ms are as there; rt_multi is not covered.  The texel pool is the only device copy of the bytes, so
+ *   the update is one copy on the call's stream.
+ * RT_E_INVALID, before any device work: scene or u NULL; image not in [0, images); a row range outside [0, h]; a flag
+ *   other than RT_OUT_DEVICE; a stream without it; texels NULL with n_rows > 0.  n_rows = 0 is RT_OK and touches nothing. */
+int64_t rt_scene_images_get(rt_scene* scene, int32_t* desc_out, int64_t* first_texel_out, int64_t cap);
+int64_t rt_scene_texture_images_get(rt_scene* scene, int32_t* image_out, int64_t cap);
+int64_t rt_scene_texels_get(rt_scene* scene, int32_t image, uint8_t* out, int64_t cap_bytes);
+int rt_scene_update_texels(rt_scene* scene, const rt_update_params* u, int32_t image, const uint8_t* texels, int64_t first_row, int64_t n_rows,
+                           double* ms);
 
 /* ---- rigid scenes: rects, boxes and the objects that place them (translate, rotate_y, constant_medium) ----
  * The Cornell box, the Cornell smoke box, the simple-light scene and the Next-Week final scene are made of these.
@@ -553,6 +583,30 @@ int rt_radiance_rays(rt_scene* scene, const rt_radiance_params* q, const double*
  *   with n > 0.  n = 0, or all four outputs NULL, is RT_OK and touches nothing. */
 int rt_radiance_grad(rt_scene* scene, const rt_radiance_params* q, const double* rays, const uint64_t* rng, const double* weights, int64_t n,
                      double* radiance, double* grad_textures, double* grad_materials, double* grad_background, rt_stats* stats);
+/* rt_radiance_grad_texels (additive since ABI 5): rt_radiance_grad with one more output, grad_texels (N x 3 f64, may be
+ * NULL; N and the global texel index as rt_scene_images_get states them): the gradient of phi with respect to the
+ * texels of the scene's images -- what recovering a texture map needs.  The lookup is a nearest-texel one whose result
+ * enters the path's product exactly where a solid colour does, and no scatter direction depends on it, so phi is the
+ * same kind of polynomial in the texel values.  Everything rt_radiance_grad documents holds unchanged -- arguments,
+ * definition, exact accumulation, buffer and stream rules, refusals -- with one definition changed:
+ *   the row of a lambertian, isotropic or diffuse_light value that resolved (directly or through checker levels) to an
+ *   RT_TEX_IMAGE or RT_TEX_BARY_IMAGE texture is the global texel the lookup read.
+ * The derivative is with respect to the texel's value, byte / 255 per channel; the three columns are the texel's first
+ *   three bytes (a fourth byte of a bpp 4 image is never read).  Texels of an image with bpp < 3 have no row and stay
+ *   +0.0: the lookup reads neighbouring texels' bytes there, so no single texel owns the value.  Every texel no path
+ *   read is +0.0.
+ * With grad_texels NULL the call is rt_radiance_grad: the same kernels, the same bits in every output.  With it, a
+ *   scene that has an image texture runs the texel form of its kernel (k_texel_grad), and the other outputs hold the
+ *   bits rt_radiance_grad gives.
+ * Workspace: beside rt_radiance_grad's parts, the texel accumulators, copies x N x 80 bytes, zeroed per call, with as
+ *   many copies as 256 MiB hold -- at least one, at most the other table's count -- or as option grad.texel_copies
+ *   says; no output bit depends on the count.  Allocated only when grad_texels is given.
+ * RT_E_INVALID, before any device work: every case of rt_radiance_grad, and with grad_texels given a scene whose T + M +
+ *   1 + N rows do not fit the 32-bit row of a vertex record (2^32 rows or more).  n = 0, or all five outputs NULL, is RT_OK
+ *   and touches nothing. */
+int rt_radiance_grad_texels(rt_scene* scene, const rt_radiance_params* q, const double* rays, const uint64_t* rng, const double* weights,
+                            int64_t n, double* radiance, double* grad_textures, double* grad_materials, double* grad_background,
+                            double* grad_texels, rt_stats* stats);
 /* rt_camera_rays (additive since ABI 5): rt_render's own camera rays as data -- the starting point of a custom camera, and
  * what makes rt_radiance_rays checkable against rt_render.  Entry (ly * width + lx) * k + j of rays_out (7 doubles) and
  * rng_out (one PCG state; may be NULL) holds the ray of local pixel (lx, ly), sample sample_base + j, and the generator's

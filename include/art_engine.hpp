@@ -193,6 +193,25 @@ inline void radiance_grad(const scene& world, const double* rays, const double* 
     check(rt_radiance_grad(world.objects.get(), &q, rays, rng, weights, n, radiance, grad_textures, grad_materials, grad_background, stats),
           "radiance_grad");
 }
+// ... and with respect to the texels of the world's image textures (rt_radiance_grad_texels): grad_texels (N x 3 doubles,
+// N the texels of every image in scene_images' order; may be nullptr, and the call is then the one above) receives the
+// derivative with respect to each texel's value, byte / 255 per channel.
+inline void radiance_grad(const scene& world, const double* rays, const double* weights, std::int64_t n, double* radiance, double* grad_textures,
+                          double* grad_materials, double* grad_background, double* grad_texels, const radiance_options& o = {},
+                          const std::uint64_t* rng = nullptr, rt_stats* stats = nullptr) {
+    rt_radiance_params q{};
+    q.flags = o.flags;
+    q.spp = o.spp;
+    q.max_depth = o.max_depth;
+    q.sample_base = o.sample_base;
+    q.seed = o.seed;
+    q.id_base = o.id_base;
+    q.stream = o.stream;
+    for (int k = 0; k < 3; ++k) q.background[k] = o.background.e[k];
+    check(rt_radiance_grad_texels(world.objects.get(), &q, rays, rng, weights, n, radiance, grad_textures, grad_materials, grad_background, grad_texels,
+                                  stats),
+          "radiance_grad");
+}
 // The renderer's own camera rays as data (rt_camera_rays): entry (y * width + x) * k + j of rays_out (7 doubles) and
 // rng_out (may be nullptr) is the ray render_engine starts at pixel (x, y) for sample sample_base + j with `seed`, and the
 // PCG state after the camera's draws -- so the in-order sum of radiance_rays over a pixel's entries is that pixel's sum.
@@ -314,6 +333,38 @@ inline void update_materials(const scene& world, const double* m, std::int64_t f
 inline void update_textures(const scene& world, const double* t, std::int64_t first, std::int64_t n, std::int32_t flags = 0, void* stream = nullptr,
                             double* ms = nullptr) {
     detail::scene_update(rt_scene_update_textures, "update_textures", world, t, first, n, flags, stream, ms);
+}
+// A compiled world's images (rt_scene_images_get): {w, h, bpp} per image in the order the world's images were made, and
+// (optional) each image's first global texel -- the rows of radiance_grad's texel gradient.  scene_texels: the h * w * bpp
+// bytes of one image, top row first, as the world holds them now.  update_texels: new bytes for rows [first_row, first_row
+// + n_rows) of one image in the same layout (rt_scene_update_texels); flags, stream and ms as update_triangles.
+inline std::vector<std::int32_t> scene_images(const scene& world, std::vector<std::int64_t>* first_texel = nullptr) {
+    const std::int64_t n = rt_scene_images_get(world.objects.get(), nullptr, nullptr, 0);
+    check(n < 0 ? static_cast<int>(n) : RT_OK, "scene_images");
+    std::vector<std::int32_t> desc(static_cast<std::size_t>(3 * n));
+    if (first_texel) first_texel->assign(static_cast<std::size_t>(n), 0);
+    if (n > 0) {
+        const std::int64_t got = rt_scene_images_get(world.objects.get(), desc.data(), first_texel ? first_texel->data() : nullptr, n);
+        check(got < 0 ? static_cast<int>(got) : RT_OK, "scene_images");
+    }
+    return desc;
+}
+inline std::vector<std::uint8_t> scene_texels(const scene& world, std::int32_t image) {
+    const std::int64_t bytes = rt_scene_texels_get(world.objects.get(), image, nullptr, 0);
+    check(bytes < 0 ? static_cast<int>(bytes) : RT_OK, "scene_texels");
+    std::vector<std::uint8_t> out(static_cast<std::size_t>(bytes));
+    if (bytes > 0) {
+        const std::int64_t got = rt_scene_texels_get(world.objects.get(), image, out.data(), bytes);
+        check(got < 0 ? static_cast<int>(got) : RT_OK, "scene_texels");
+    }
+    return out;
+}
+inline void update_texels(const scene& world, std::int32_t image, const std::uint8_t* texels, std::int64_t first_row, std::int64_t n_rows,
+                          std::int32_t flags = 0, void* stream = nullptr, double* ms = nullptr) {
+    rt_update_params u{};
+    u.flags = flags;
+    u.stream = stream;
+    check(rt_scene_update_texels(world.objects.get(), &u, image, texels, first_row, n_rows, ms), "update_texels");
 }
 // A compiled world's rects, boxes and objects (rt_scene_rects_get / _boxes_get / _objects_get): RT_RECT_DOUBLES (a0, a1,
 // b0, b1, k), RT_BOX_DOUBLES (min xyz, max xyz) and RT_OBJECT_DOUBLES (the parameters p: a translate's offset, a
